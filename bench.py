@@ -13,10 +13,16 @@ reference's yolox/core/launch.py:59-98 spawns its workers; the parent only waits
 from --gpus is an error.  At N > 1 every rank replays TWO HIP graphs per step -- (histogram, forward, backward, gradient
 packing) and (Adam, reset) -- with the one flat RCCL all-reduce launched eagerly between them: three host calls per step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up (choosing the launch form), times the --steps steps and prints ONE JSON line (rank 0) with the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step), the configuration and the last timed step's loss.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
+
+--full adds the figures that take runs of their own, after the timed region:
   roofline      achieved algorithmic GB/s of the dominant hand-written HIP kernel family, timed with HIP events
-                on the launch stream inside the timed region;
-  cpu_baseline  the CPU oracle (torch fp32 restatement of the reference) timed on this host, rank 0, N=1 only.
+                on the launch stream in eager steps right after the timed region;
+  roofline_eval, eval_forward_frames_per_s, launches_per_step, weight_average, canvas_640   (one GPU)
+  parity, cpu_baseline  the HIP path against the CPU oracle, and the oracle (torch fp32 restatement of the reference) timed on this
+                host, rank 0, N=1 only (--no-cpu-baseline drops both).
 """
 import argparse
 import json
@@ -107,7 +113,13 @@ def parse():
                          'T=5 RPD Gen1; 4 = SYOLOX-M 1Mpx stacked histogram T=3; 5 = SYOLOX-M N-Caltech101 T=7')
     ap.add_argument('--batch', type=int, default=None, help='samples per GPU (default: the configuration\'s: 64 for config 2, 32 for 3-5)')
     ap.add_argument('--events', type=int, default=200_000, help='events per sample')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the side figures after the timed region: kernel-family rooflines, the eval forward, launch counts, '
+                         'the step without the weight average, the 640x640 canvas, parity against the CPU oracle and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss terms; a fixed, seeded sample of the model state, gradients and '
+                         'weight average) to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no parity against the oracle, no CPU baseline')
     ap.add_argument('--cpu-batch', type=int, default=None)
     ap.add_argument('--h2d', action='store_true',
                     help='stream a fresh pinned host batch of raw input to the device every step on a side stream (the reference\'s '
@@ -601,6 +613,113 @@ def canvas_640_figure(dev, batch, events):
     return out
 
 
+def step_roofline(timer, timed_steps, ms_per_step, config):
+    """--full: the roofline object of the training step from the kernel families of the eager steps ``timer`` recorded right after the
+    timed region (``timed_steps`` of them), against the timed region's ``ms_per_step``"""
+    summ = timer.summary()
+    fam = {k: dict(calls=v['calls'], ms_per_step=round(v['ms'] / timed_steps, 4),
+                   GBps=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['ms'] > 0 else None,
+                   **({'TFLOPs': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1)} if v['flops'] > 0 else {}),
+                   roofline_frac=round(v['roof_ms'] / v['ms'], 3) if v['ms'] > 0 else None) for k, v in summ.items()}
+    dom = max(summ, key=lambda k: summ[k]['ms'])
+    d = summ[dom]
+    sec = d['ms'] * 1e-3
+    traffic, traffic_why = pmc_traffic(dom, 2 if dom in ('eas_bn_lif_bwd', 'eas_bn_silu_bwd') else 1, config)
+    common = {'kernel': dom, 'avg_launch_ms': round(d['ms'] / d['calls'], 4),
+              'traffic': traffic,
+              'traffic_source': ('committed rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes over this command (profiles/pmc_traffic_latest.json, '
+                                 'scripts/gpu_profile.sh; configs 2 and 3) on kernel sources whose hashes match this build\'s; not re-measured in this run'
+                                 if traffic is not None else traffic_why),
+              'algorithmic_bytes_per_call': round(d['bytes'] / d['calls']), 'hip_kernel_ms_per_step': fam,
+              'hip_share_of_step': round(sum(v['ms'] for v in summ.values()) / timed_steps / ms_per_step, 4),
+              'kernel_timing': 'HIP events on the launch stream, 3 eager steps of this process right after the timed region (all launches on one stream there)'
+                               + (f'; {timer.input_retimed} (the first kernel of a step, which starts on an idle queue there) re-timed in ten back-to-back calls' if getattr(timer, 'input_retimed', None) else '')}
+    if d['flops'] > 0:
+        # dense convolutions: bounded by the matrix cores.  achieved = algorithmic flops (2 x MAC of the fp32 convolution) per
+        # second against the dense f32 MFMA peak (the arithmetic the path reproduces); every fp32 product is formed from
+        # 3 (spike inputs) or 6 (general inputs) exact bf16 term products on v_mfma_f32_32x32x16_bf16, so the bf16 flops
+        # actually issued and their share of the dense bf16 peak are reported next to it.
+        achieved = d['flops'] / sec / 1e12
+        # ceiling of the exact-bf16-term scheme itself: the bf16 pipe divided by the term products per fp32 product
+        # (3 for spike inputs -> 833 TF, 6 for real-valued inputs -> 417 TF), weighted by this step's mix of the two
+        scheme_ceiling = BF16_MFMA_PEAK_TF * d['flops'] / d['issue_flops']
+        # peak = what bounds these kernels: the dense bf16 MFMA rate divided by the bf16 term products one exact fp32 product costs
+        # (rounds 1-2 quoted the 157.3 TFLOP/s f32-input MFMA peak here; the M-width configurations run ABOVE that rate, which
+        # is the point of the term scheme and makes it useless as a ceiling -- kept as vs_f32_mfma_peak)
+        roofline = {'bound': 'mfma', 'achieved': round(achieved, 1), 'peak': round(scheme_ceiling, 1), 'unit': 'TFLOP/s',
+                    'frac': round(achieved / scheme_ceiling, 4),
+                    'peak_is': 'bf16 term ceiling (not a hardware figure): the dense bf16 MFMA peak divided by the bf16 term products one exact fp32 product costs',
+                    'bf16_issue_frac': round(d['issue_flops'] / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
+                    'peak_note': 'dense bf16 MFMA peak 2500 TFLOP/s / bf16 term products per fp32 product (3 spike inputs, 6 real inputs), weighted by this step',
+                    'vs_f32_mfma_peak': round(achieved / F32_MFMA_PEAK_TF, 4), 'f32_mfma_peak_tflops': F32_MFMA_PEAK_TF,
+                    'scheme_ceiling_tflops': round(scheme_ceiling, 1), 'frac_of_scheme_ceiling': round(achieved / scheme_ceiling, 4),
+                    'mfma_bf16_issued_tflops': round(d['issue_flops'] / sec / 1e12, 1), 'mfma_bf16_peak_tflops': BF16_MFMA_PEAK_TF,
+                    'mfma_bf16_util': round(d['issue_flops'] / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
+                    'mfma_busy_measured': mfma_busy_measured(),
+                    # per launch max(algorithmic bytes / 8 TB/s, bf16 term flops / 2.5 PFLOP/s), summed over this family's launches,
+                    # over the measured time: the small-channel layers are HBM-bound, so the term ceiling alone overstates the headroom
+                    'frac_of_per_launch_roofline': round(d['roof_ms'] / d['ms'], 4),
+                    'algorithmic_GBps': round(d['bytes'] / sec / 1e9, 1)}
+    else:
+        achieved = d['bytes'] / sec / 1e9
+        roofline = {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                    'frac': round(achieved / HBM_PEAK_GBS, 4)}
+    roofline.update(common)
+    # the dominant HBM-bound family as well (the elementwise/BN/LIF kernels of the step)
+    hbm_fams = {k: v for k, v in summ.items() if v['flops'] == 0 and v['bytes'] > 0}
+    if hbm_fams:
+        hk = max(hbm_fams, key=lambda k: hbm_fams[k]['ms'])
+        hv = hbm_fams[hk]
+        h_traffic, h_why = pmc_traffic(hk, 2 if hk in ('eas_bn_lif_bwd', 'eas_bn_silu_bwd') else 1, config)
+        roofline['hbm_dominant'] = {'kernel': hk, 'achieved': round(hv['bytes'] / (hv['ms'] * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS,
+                                    'unit': 'GB/s', 'frac': round(hv['bytes'] / (hv['ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                    'traffic': h_traffic, **({'traffic_unavailable': h_why} if h_traffic is None else {}),
+                                    'algorithmic_bytes_per_call': round(hv['bytes'] / hv['calls'])}
+    return roofline
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _state_sample(named, picks):
+    """float32 vector of the (name, tensor) pairs in the given order: a tensor of up to 2048 elements whole, a larger one as a fixed
+    sample of 2048 + numel // 16 of its elements (ascending positions, drawn by a generator seeded with the tensor's name, so that a
+    parameter's sample sits at the same positions in every array that holds it; ``picks`` caches them by name and size)"""
+    import zlib
+    parts = []
+    for name, t in named:
+        flat = t.detach().reshape(-1).float()
+        n = flat.numel()
+        k = min(n, 2048 + n // 16)
+        if k < n:
+            if (name, n) not in picks:
+                pick = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, k, replace=False))
+                picks[name, n] = torch.from_numpy(pick).to(flat.device)
+            flat = flat[picks[name, n]]
+        parts.append(flat)
+    return torch.cat(parts).cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(out_dir, step):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- its loss terms (float64, one file each)
+    and, as fixed samples (float32, _state_sample), the model's floating-point state after the update, the parameter gradients of the
+    step (zeros where a parameter received none) and the weight average's state.  Written right after the timed region, before
+    anything else runs on the model."""
+    model = step.model
+    arrays = {k: np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+              for k, v in (step.outputs or {}).items()}
+    picks = {}
+    arrays['model_state'] = _state_sample([(k, v) for k, v in model.state_dict().items() if v.is_floating_point()], picks)
+    arrays['gradients'] = _state_sample([(k, p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in model.named_parameters()], picks)
+    if step.ema is not None:
+        arrays['ema_state'] = _state_sample([(k, v) for k, v in step.ema.ema.state_dict().items() if v.is_floating_point()], picks)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}'
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def main():
     args = parse()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -703,7 +822,6 @@ def main():
         # after the same number of training steps (tests/test_gpu_model.py compares their losses).
         for _ in range(4):
             one()
-    timer = ops.KernelTimer() if rank == 0 else None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -715,38 +833,44 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ops.check_tags('the timed steps')        # a tensor tagged "spikes" that was not: the measured arithmetic would not be the fp32 one
-    # Per-kernel durations behind `roofline`: HIP events around every C-ABI call, on the stream the kernels are launched on, in
-    # eager steps of this same process right after the timed region (same kernels, same data).  Not inside it: events cannot be
-    # recorded into a captured graph, and ~1400 event records per eager step would slow the timed region itself by ~10 %.
-    # With more than one rank every rank runs these steps (the all-reduces need all of them); rank 0 records.
-    timed_steps = 3
-    # (serial launches for these steps: the weight-gradient slab kernels of the timed region run on a side stream under the backward chain,
-    # where an event pair around one of them -- or around a chain kernel they share the chip with -- measures the overlap, not the kernel)
-    side_batch, ops.WGRAD_SIDE_BATCH = ops.WGRAD_SIDE_BATCH, 0
-    ops.set_timer(timer)
-    for _ in range(timed_steps):
-        step.eager()
-    torch.cuda.synchronize()
-    ops.set_timer(None)
-    ops.WGRAD_SIDE_BATCH = side_batch
-    # The first kernel of a step (raw input -> frames: K1 / the stacked-histogram reduction) starts on an idle queue in those eager steps,
-    # so its event pair also spans the host's submission latency (128 us recorded for a 65 us kernel).  Re-timed back to back: eleven calls,
-    # the first dropped, scaled to the three steps the other entries cover.
-    if rank == 0:
-        t_in = ops.KernelTimer()
-        ops.set_timer(t_in)
-        for _ in range(11):
-            step.inputs_fn()
+    final_loss = float(loss.detach())        # (before the side figures of --full: their steps and replays go on training the model)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step)
+    timer, timed_steps = None, 3
+    if args.full:
+        timer = ops.KernelTimer() if rank == 0 else None
+        # Per-kernel durations behind `roofline`: HIP events around every C-ABI call, on the stream the kernels are launched on, in
+        # eager steps of this same process right after the timed region (same kernels, same data).  Not inside it: events cannot be
+        # recorded into a captured graph, and ~1400 event records per eager step would slow the timed region itself by ~10 %.
+        # With more than one rank every rank runs these steps (the all-reduces need all of them); rank 0 records.
+        # (serial launches for these steps: the weight-gradient slab kernels of the timed region run on a side stream under the backward
+        # chain, where an event pair around one of them -- or around a chain kernel they share the chip with -- measures the overlap, not
+        # the kernel)
+        side_batch, ops.WGRAD_SIDE_BATCH = ops.WGRAD_SIDE_BATCH, 0
+        ops.set_timer(timer)
+        for _ in range(timed_steps):
+            step.eager()
         torch.cuda.synchronize()
         ops.set_timer(None)
-        for name, items in t_in.rec.items():
-            if name in timer.rec and len(items) == 11 and len(timer.rec[name]) == timed_steps:
-                timer.rec[name] = items[4:4 + timed_steps]           # calls from the middle of the run: the queue is full
-                timer.input_retimed = name
+        ops.WGRAD_SIDE_BATCH = side_batch
+        # The first kernel of a step (raw input -> frames: K1 / the stacked-histogram reduction) starts on an idle queue in those eager
+        # steps, so its event pair also spans the host's submission latency (128 us recorded for a 65 us kernel).  Re-timed back to back:
+        # eleven calls, the first dropped, scaled to the three steps the other entries cover.
+        if rank == 0:
+            t_in = ops.KernelTimer()
+            ops.set_timer(t_in)
+            for _ in range(11):
+                step.inputs_fn()
+            torch.cuda.synchronize()
+            ops.set_timer(None)
+            for name, items in t_in.rec.items():
+                if name in timer.rec and len(items) == 11 and len(timer.rec[name]) == timed_steps:
+                    timer.rec[name] = items[4:4 + timed_steps]           # calls from the middle of the run: the queue is full
+                    timer.input_retimed = name
     # inference side figure: eval-mode forward + reset_net of the same batch (no loss, no backward), replayed as a HIP graph like the
     # evaluator does (yolox/evaluators/event_evaluator.py), for the model as trained and after yolox.utils.fuse_model (tools/eval_event.py --fuse)
     eval_fps = eval_roofline = None
-    if rank == 0 and not multi and os.environ.get('EAS_BENCH_NO_EVAL') != '1':      # (development: profiles of the training step alone)
+    if args.full and rank == 0 and not multi and os.environ.get('EAS_BENCH_NO_EVAL') != '1':      # (development: profiles of the training step alone)
         import copy
         from spikingjelly.activation_based import functional
         from yolox.utils import fuse_model
@@ -795,18 +919,19 @@ def main():
                               'kernel_timing': 'HIP events on the launch stream, 3 eager eval forwards of this process'})
         model.train()
     # launches of one step (every rank runs the steps -- the exchange needs all of them --, rank 0 reports)
-    launches = count_launches(step, eas_snn_amd.hip_library()) if (rank == 0 and not multi) else None
+    launches = count_launches(step, eas_snn_amd.hip_library()) if (args.full and rank == 0 and not multi) else None
     # (side figures that record further graphs or start a child process: never under a profiler -- rocprofv3 follows the child, whose kernel
     # statistics would land next to, or over, this process's)
     profiled = 'rocprof' in os.environ.get('LD_PRELOAD', '') or any(k.startswith(('ROCPROFILER_', 'ROCPROF_')) for k in os.environ)
     ema_figure = None
-    if rank == 0 and not multi and step.graphs is not None and os.environ.get('EAS_BENCH_NO_EMA') != '1' and not profiled:
+    if args.full and rank == 0 and not multi and step.graphs is not None and os.environ.get('EAS_BENCH_NO_EMA') != '1' and not profiled:
         try:
             ema_figure = ema_off_side_figure(trainer, step, inputs_fn)
         except Exception as exc:
             ema_figure = {'error': f'{type(exc).__name__}: {exc}'[:300]}
     canvas640 = None
-    if rank == 0 and not multi and w['config'] == 2 and args.batch is None and os.environ.get('EAS_BENCH_NO_640') != '1' and not profiled:
+    if (args.full and rank == 0 and not multi and w['config'] == 2 and args.batch is None and os.environ.get('EAS_BENCH_NO_640') != '1'
+            and not profiled):
         # in a child process of its own (started like the ranks of launch_ranks, never an exec): a side figure must not be able to take the
         # headline line with it -- a failure is reported in its place
         import subprocess
@@ -821,69 +946,11 @@ def main():
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el)
-    assert torch.isfinite(loss), 'training step produced a non-finite loss'
+    assert np.isfinite(final_loss), 'training step produced a non-finite loss'
 
     if rank == 0:
         frames_total = batch * world * args.steps
-        summ = timer.summary()
-        fam = {k: dict(calls=v['calls'], ms_per_step=round(v['ms'] / timed_steps, 4),
-                       GBps=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['ms'] > 0 else None,
-                       **({'TFLOPs': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1)} if v['flops'] > 0 else {}),
-                       roofline_frac=round(v['roof_ms'] / v['ms'], 3) if v['ms'] > 0 else None) for k, v in summ.items()}
-        dom = max(summ, key=lambda k: summ[k]['ms'])
-        d = summ[dom]
-        sec = d['ms'] * 1e-3
-        traffic, traffic_why = pmc_traffic(dom, 2 if dom in ('eas_bn_lif_bwd', 'eas_bn_silu_bwd') else 1, w['config'])
-        common = {'kernel': dom, 'avg_launch_ms': round(d['ms'] / d['calls'], 4),
-                  'traffic': traffic,
-                  'traffic_source': ('committed rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes over this command (profiles/pmc_traffic_latest.json, '
-                                     'scripts/gpu_profile.sh; configs 2 and 3) on kernel sources whose hashes match this build\'s; not re-measured in this run'
-                                     if traffic is not None else traffic_why),
-                  'algorithmic_bytes_per_call': round(d['bytes'] / d['calls']), 'hip_kernel_ms_per_step': fam,
-                  'hip_share_of_step': round(sum(v['ms'] for v in summ.values()) / timed_steps / (elapsed / args.steps * 1e3), 4),
-                  'kernel_timing': 'HIP events on the launch stream, 3 eager steps of this process right after the timed region (all launches on one stream there)'
-                                   + (f'; {timer.input_retimed} (the first kernel of a step, which starts on an idle queue there) re-timed in ten back-to-back calls' if getattr(timer, 'input_retimed', None) else '')}
-        if d['flops'] > 0:
-            # dense convolutions: bounded by the matrix cores.  achieved = algorithmic flops (2 x MAC of the fp32 convolution) per
-            # second against the dense f32 MFMA peak (the arithmetic the path reproduces); every fp32 product is formed from
-            # 3 (spike inputs) or 6 (general inputs) exact bf16 term products on v_mfma_f32_32x32x16_bf16, so the bf16 flops
-            # actually issued and their share of the dense bf16 peak are reported next to it.
-            achieved = d['flops'] / sec / 1e12
-            # ceiling of the exact-bf16-term scheme itself: the bf16 pipe divided by the term products per fp32 product
-            # (3 for spike inputs -> 833 TF, 6 for real-valued inputs -> 417 TF), weighted by this step's mix of the two
-            scheme_ceiling = BF16_MFMA_PEAK_TF * d['flops'] / d['issue_flops']
-            # peak = what bounds these kernels: the dense bf16 MFMA rate divided by the bf16 term products one exact fp32 product costs
-            # (rounds 1-2 quoted the 157.3 TFLOP/s f32-input MFMA peak here; the M-width configurations run ABOVE that rate, which
-            # is the point of the term scheme and makes it useless as a ceiling -- kept as vs_f32_mfma_peak)
-            roofline = {'bound': 'mfma', 'achieved': round(achieved, 1), 'peak': round(scheme_ceiling, 1), 'unit': 'TFLOP/s',
-                        'frac': round(achieved / scheme_ceiling, 4),
-                        'peak_is': 'bf16 term ceiling (not a hardware figure): the dense bf16 MFMA peak divided by the bf16 term products one exact fp32 product costs',
-                        'bf16_issue_frac': round(d['issue_flops'] / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
-                        'peak_note': 'dense bf16 MFMA peak 2500 TFLOP/s / bf16 term products per fp32 product (3 spike inputs, 6 real inputs), weighted by this step',
-                        'vs_f32_mfma_peak': round(achieved / F32_MFMA_PEAK_TF, 4), 'f32_mfma_peak_tflops': F32_MFMA_PEAK_TF,
-                        'scheme_ceiling_tflops': round(scheme_ceiling, 1), 'frac_of_scheme_ceiling': round(achieved / scheme_ceiling, 4),
-                        'mfma_bf16_issued_tflops': round(d['issue_flops'] / sec / 1e12, 1), 'mfma_bf16_peak_tflops': BF16_MFMA_PEAK_TF,
-                        'mfma_bf16_util': round(d['issue_flops'] / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
-                        'mfma_busy_measured': mfma_busy_measured(),
-                        # per launch max(algorithmic bytes / 8 TB/s, bf16 term flops / 2.5 PFLOP/s), summed over this family's launches,
-                        # over the measured time: the small-channel layers are HBM-bound, so the term ceiling alone overstates the headroom
-                        'frac_of_per_launch_roofline': round(d['roof_ms'] / d['ms'], 4),
-                        'algorithmic_GBps': round(d['bytes'] / sec / 1e9, 1)}
-        else:
-            achieved = d['bytes'] / sec / 1e9
-            roofline = {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                        'frac': round(achieved / HBM_PEAK_GBS, 4)}
-        roofline.update(common)
-        # the dominant HBM-bound family as well (the elementwise/BN/LIF kernels of the step)
-        hbm_fams = {k: v for k, v in summ.items() if v['flops'] == 0 and v['bytes'] > 0}
-        if hbm_fams:
-            hk = max(hbm_fams, key=lambda k: hbm_fams[k]['ms'])
-            hv = hbm_fams[hk]
-            h_traffic, h_why = pmc_traffic(hk, 2 if hk in ('eas_bn_lif_bwd', 'eas_bn_silu_bwd') else 1, w['config'])
-            roofline['hbm_dominant'] = {'kernel': hk, 'achieved': round(hv['bytes'] / (hv['ms'] * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS,
-                                        'unit': 'GB/s', 'frac': round(hv['bytes'] / (hv['ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                        'traffic': h_traffic, **({'traffic_unavailable': h_why} if h_traffic is None else {}),
-                                        'algorithmic_bytes_per_call': round(hv['bytes'] / hv['calls'])}
+        roofline = step_roofline(timer, timed_steps, elapsed / args.steps * 1e3, w['config']) if args.full else None
         metric = ('event-frames/sec (T=3) SYOLOX-S Gen1 304x240' if w['config'] == 2 else f'event-frames/sec, BASELINE config {w["config"]}')
         line = {'metric': metric, 'value': round(frames_total / elapsed, 2),
                 'unit': 'event-frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -897,10 +964,12 @@ def main():
                                                            if ops.WGRAD_SIDE_BATCH > 0 else None),
                            'launch': launch, 'rccl_ranks': dist.get_world_size() if dist.is_initialized() else 1,
                            'launch_probe_ms_per_step': probe, 'host_enqueue_share_of_step': round(t_enq / t_tot, 3),
-                           'h2d_per_step': (h2d.describe() if h2d is not None else None)},
-                'roofline': roofline}
-        line['final_loss'] = float(loss.detach())
-        line['launches_per_step'] = launches
+                           'h2d_per_step': (h2d.describe() if h2d is not None else None)}}
+        if roofline is not None:
+            line['roofline'] = roofline
+        line['final_loss'] = final_loss
+        if args.full:
+            line['launches_per_step'] = launches
         if eval_roofline is not None:
             line['roofline_eval'] = eval_roofline
         if canvas640 is not None:
@@ -909,7 +978,7 @@ def main():
             line['eval_forward_frames_per_s'] = dict(eval_fps, batch=batch, note='model.eval() forward + reset_net on the same batch, one GPU, HIP-graph replay (as EventEvaluator); fuse_model: after yolox.utils.fuse_model (eval_event.py --fuse)')
         if ema_figure is not None:
             line['weight_average'] = ema_figure
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['parity'] = parity_against_oracle(w, model, step.raw_inputs, dev)
             line['cpu_baseline'] = cpu_baseline(w, args.cpu_batch or (8 if w['config'] == 2 else 2), args.events)
         print(json.dumps(line), flush=True)

@@ -785,6 +785,39 @@ def gen_model_train_m():
     print(f'    {name}: loss {float(out["total_loss"]):.5f}, {len(gn)} parameter gradients')
 
 
+# ----------------------------------------------------------------------------- Exp.merge (command-line overrides of an experiment)
+MERGE_DEFAULTS = dict(a=3, b=0.5, c='str', d=True, e=None, f=(256, 320), g=[1.0, 2.0], h=(), i=[], j=(0.1, 0.2), k=False)
+MERGE_CASES = [['a', '7'], ['a', '7.5'], ['b', '2'], ['c', 'True'], ['d', 'False'], ['e', 'xyz'], ['f', '(640,640)'], ['f', '[320, 480]'],
+               ['g', '[3,4]'], ['h', '(1,2)'], ['i', '[a,b]'], ['j', '(0.5, 1)'], ['k', '0'], ['zzz', '1'], ['a', '[1]'], ['f', '640,  512'],
+               ['b', '1e-3'], ['g', 'x'], ['f', '(a,b)'], ['a', '1', 'b', '2', 'a', '5']]
+
+
+def gen_merge():
+    """BaseExp.merge of the reference (yolox/exp/base_exp.py:67-90) on fixed defaults and overrides: ints, floats, strings, the
+    ``bool('False')`` quirk, None defaults, tuples / lists (brackets or not, empty defaults), unknown keys, a literal_eval fallback and
+    overrides that raise.  Per case: the exception's type name ('' when none), and per key it names the repr and type name of the
+    resulting attribute ('<absent>' when there is none) -- for tests/test_cpu_host.py::test_exp_merge_equals_the_reference_merge."""
+    from yolox.exp.base_exp import BaseExp
+    X = type('X', (BaseExp,), {n: (lambda self, *a, **k: None) for n in getattr(BaseExp, '__abstractmethods__', ())})
+    arrays = {'defaults/keys': np.array(list(MERGE_DEFAULTS)), 'defaults/repr': np.array([repr(v) for v in MERGE_DEFAULTS.values()])}
+    for n, cs in enumerate(MERGE_CASES):
+        obj = X()
+        for key, v in MERGE_DEFAULTS.items():
+            setattr(obj, key, v)
+        try:
+            obj.merge(list(cs))
+            err = ''
+        except Exception as exc:
+            err = type(exc).__name__
+        keys = sorted(set(cs[0::2]))
+        arrays[f'{n:02d}/override'] = np.array(cs)
+        arrays[f'{n:02d}/error'] = np.array(err)
+        arrays[f'{n:02d}/keys'] = np.array(keys)
+        arrays[f'{n:02d}/repr'] = np.array([repr(getattr(obj, k)) if hasattr(obj, k) else '<absent>' for k in keys])
+        arrays[f'{n:02d}/type'] = np.array([type(getattr(obj, k)).__name__ if hasattr(obj, k) else '<absent>' for k in keys])
+    save('exp_merge', **arrays)
+
+
 def main():
     torch.set_num_threads(8)
     setup_reference_imports()
@@ -792,7 +825,7 @@ def main():
     for w in which:
         print(f'[{w}]')
         {'events': gen_events, 'embeddings': gen_embeddings, 'lif': gen_lif_layer, 'blocks': gen_blocks,
-         'models': gen_models, 'reps': gen_event_reps, 'augment': gen_augment, 'patan': gen_patan, 'stacked_hist': gen_stacked_hist, 'energy': gen_energy, 'window': gen_window_search, 'model_train_m': gen_model_train_m, 'vrecord': gen_vrecord}[w]()
+         'models': gen_models, 'reps': gen_event_reps, 'augment': gen_augment, 'patan': gen_patan, 'stacked_hist': gen_stacked_hist, 'energy': gen_energy, 'window': gen_window_search, 'model_train_m': gen_model_train_m, 'vrecord': gen_vrecord, 'merge': gen_merge}[w]()
     assert not os.path.exists(os.path.join(REF, 'yolox', '__pycache__')), 'bytecode leaked into the reference'
 
 

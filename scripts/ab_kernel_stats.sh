@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 export EAS_BENCH_GRAPH=0 EAS_BENCH_NO_640=1 EAS_BENCH_NO_EMA=1
 for v in $A $B; do
   export $VAR=$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s_$v -- python3 $ROOT/bench.py --config $CFG --steps 5 --warmup 3 --no-cpu-baseline > $OUT/log_$v.txt 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s_$v -- python3 $ROOT/bench.py --full --config $CFG --steps 5 --warmup 3 --no-cpu-baseline > $OUT/log_$v.txt 2>&1
   find $OUT/s_$v -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_$v.csv \;
   rm -rf $OUT/s_$v
 done

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 # (side figures off: the 640x640 one runs in a child process the profiler would follow, writing a second kernel_stats.csv)
 export EAS_BENCH_GRAPH=0 EAS_BENCH_NO_EVAL=1 EAS_BENCH_NO_640=1 EAS_BENCH_NO_EMA=1
 STEPS=${1:-6}
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s -- python3 $ROOT/bench.py --steps $STEPS --warmup 3 --no-cpu-baseline > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s -- python3 $ROOT/bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline > $OUT/log.txt 2>&1
 find $OUT/s -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/s
 python3 - <<PY

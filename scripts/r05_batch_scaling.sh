@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/${1:-r05_scaling}
 mkdir -p $OUT
 cd $ROOT
 for b in 16 32 64; do
-  EAS_BENCH_NO_EVAL=1 EAS_BENCH_NO_640=1 timeout 600 python3 bench.py --no-cpu-baseline --batch $b > $OUT/bench_b$b.log 2>&1
+  EAS_BENCH_NO_EVAL=1 EAS_BENCH_NO_640=1 timeout 600 python3 bench.py --full --no-cpu-baseline --batch $b > $OUT/bench_b$b.log 2>&1
   tail -1 $OUT/bench_b$b.log > $OUT/bench_b$b.json.log
 done
 python3 - <<PY

@@ -9,7 +9,7 @@ cd $ROOT
 timeout 2400 python3 -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1
 echo "pytest rc=$?"
 tail -15 $OUT/gpu_tests.log
-timeout 900 python3 bench.py --no-cpu-baseline > $OUT/bench.log 2>&1
+timeout 900 python3 bench.py --full --no-cpu-baseline > $OUT/bench.log 2>&1
 echo "bench rc=$?"
 tail -1 $OUT/bench.log > $OUT/bench.json.log
 python3 - <<PY

@@ -9,7 +9,7 @@ RUNS=${2:-10}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-timeout 900 python3 bench.py > $OUT/bench.log 2> $OUT/bench.err
+timeout 900 python3 bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 echo "bench rc=$?"
 tail -1 $OUT/bench.log > $OUT/bench.json.log
 python3 - <<PY
@@ -26,7 +26,7 @@ PY
 python3 tests/parity_report.py $OUT/parity_teacher_forced.json > $OUT/parity_report.log 2>&1
 echo "parity_report rc=$? $(tail -1 $OUT/parity_report.log | cut -c1-400)"
 for c in 3 4 5; do
-  EAS_BENCH_NO_EVAL=0 timeout 900 python3 bench.py --config $c > $OUT/bench_config$c.log 2> $OUT/bench_config$c.err
+  EAS_BENCH_NO_EVAL=0 timeout 900 python3 bench.py --full --config $c > $OUT/bench_config$c.log 2> $OUT/bench_config$c.err
   echo "config $c rc=$? $(tail -1 $OUT/bench_config$c.log | cut -c1-260)"
   tail -1 $OUT/bench_config$c.log > $OUT/bench_config$c.json.log
 done

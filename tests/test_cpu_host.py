@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, load_golden
+from conftest import ROOT, load_golden, split_cases
 
 import eas_snn_amd  # noqa: E402  (puts compat/ on sys.path)
 
@@ -94,46 +94,36 @@ def test_exp_merge_type_coercion_quirks():
 
 
 def test_exp_merge_equals_the_reference_merge():
-    """``BaseExp.merge`` against the reference's own method (yolox/exp/base_exp.py:67-90, imported here where the reference tree exists) on the
-    same defaults and overrides: ints, floats, strings, the ``bool('False')`` quirk, None defaults, tuples / lists (brackets or not, empty
-    defaults), unknown keys, a literal_eval fallback, and overrides that raise -- same value, same type, same exception"""
-    ref_file = '/root/reference/yolox/exp/base_exp.py'
-    if not os.path.exists(ref_file):
-        pytest.skip('reference tree not present')
-    import importlib.util
+    """``BaseExp.merge`` against the results of the reference's own method (yolox/exp/base_exp.py:67-90), recorded by oracle/gen_golden.py
+    (tests/golden/exp_merge.npz) on the same defaults and overrides: ints, floats, strings, the ``bool('False')`` quirk, None defaults,
+    tuples / lists (brackets or not, empty defaults), unknown keys, a literal_eval fallback, and overrides that raise -- same value, same
+    type, same exception"""
+    import ast
     from yolox.exp.base_exp import BaseExp as Ours
-    prev = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True                       # nothing is ever written into the reference tree
-    try:
-        spec = importlib.util.spec_from_file_location('_ref_base_exp', ref_file)
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)                     # (its ``from yolox.utils import LRScheduler`` resolves to the compat namespace)
-    finally:
-        sys.dont_write_bytecode = prev
-
-    def concrete(base):
-        return type('X', (base,), {n: (lambda self, *a, **k: None) for n in getattr(base, '__abstractmethods__', ())})
-    R, O = concrete(ref.BaseExp), concrete(Ours)
-    defaults = dict(a=3, b=0.5, c='str', d=True, e=None, f=(256, 320), g=[1.0, 2.0], h=(), i=[], j=(0.1, 0.2), k=False)
-    cases = [['a', '7'], ['a', '7.5'], ['b', '2'], ['c', 'True'], ['d', 'False'], ['e', 'xyz'], ['f', '(640,640)'], ['f', '[320, 480]'],
-             ['g', '[3,4]'], ['h', '(1,2)'], ['i', '[a,b]'], ['j', '(0.5, 1)'], ['k', '0'], ['zzz', '1'], ['a', '[1]'], ['f', '640,  512'],
-             ['b', '1e-3'], ['g', 'x'], ['f', '(a,b)'], ['a', '1', 'b', '2', 'a', '5']]
-    for cs in cases:
-        r, o = R(), O()
+    O = type('X', (Ours,), {n: (lambda self, *a, **k: None) for n in getattr(Ours, '__abstractmethods__', ())})
+    rec = split_cases(load_golden('exp_merge'))
+    dflt = rec.pop('defaults')
+    defaults = {str(k): ast.literal_eval(str(v)) for k, v in zip(dflt['keys'], dflt['repr'])}
+    assert len(defaults) == 11 and len(rec) == 20
+    for name in sorted(rec):
+        case = rec[name]
+        cs = [str(t) for t in case['override']]
+        o = O()
         for key, v in defaults.items():
-            setattr(r, key, v)
             setattr(o, key, v)
-        errs = []
-        for obj in (r, o):
-            try:
-                obj.merge(list(cs))
-                errs.append(None)
-            except Exception as exc:
-                errs.append(type(exc).__name__)
-        assert errs[0] == errs[1], (cs, errs)
-        for key in set(cs[0::2]):
-            vr, vo = getattr(r, key, '<absent>'), getattr(o, key, '<absent>')
-            assert vr == vo and type(vr) is type(vo), (cs, key, vr, vo)
+        try:
+            o.merge(list(cs))
+            err = ''
+        except Exception as exc:
+            err = type(exc).__name__
+        assert err == str(case['error']), (cs, err, str(case['error']))
+        assert sorted(set(cs[0::2])) == [str(k) for k in case['keys']]
+        for key, r, t in zip(case['keys'], case['repr'], case['type']):
+            vo = getattr(o, str(key), '<absent>')
+            if str(t) == '<absent>':
+                assert vo == '<absent>', (cs, key, vo)
+            else:
+                assert vo == ast.literal_eval(str(r)) and type(vo).__name__ == str(t), (cs, key, vo, str(r), str(t))
     with pytest.raises(AssertionError):
         O().merge(['a'])
 
