@@ -29,8 +29,6 @@ class Context:
         self.small_dgrad = os.environ.get('EAS_SMALL_DGRAD', '1') != '0'
         self.defer_wgrad_reduce = _env_flag('EAS_DEFER_WGRAD_REDUCE', '0')
         self.wgrad_side_batch = int(os.environ.get('EAS_WGRAD_SIDE', '16'))   # 0: everything on the main stream; 16: swept on config 2 (12 / 15 / 17 / 20 / 24 lose 0.1-0.3 ms of its 0.37 ms)
-        self.wgrad_side_us = float(os.environ.get('EAS_WGRAD_SIDE_US', '0'))  # a batch also leaves once its estimated kernel time reaches this (0: count only)
-        self.wgrad_side_at = tuple(int(v) for v in os.environ.get('EAS_WGRAD_SIDE_AT', '').split(',') if v.strip())   # or: after these launch counts of the pass
         self.verify_small_int = False       # tests switch this on: every tagged tensor is checked (host sync) before it is used
         # ---- scopes
         self.state_writeback = True         # final membrane potentials are written back after a multi-step call (ops.no_state_writeback)
@@ -43,7 +41,7 @@ class Context:
         self.pack_gen = 0
         self.frozen = None                  # {'model', 'gen', 'inv'} while a ``frozen_weights`` block is open, else None
         self.pending_reduce = []            # (slab workspace kept alive, grad_w address, numel, slab count, [(parameter, address of its .grad, numel)])
-        self.side = {'stream': None, 'pending': [], 'keep': [], 'dirty': False, 'us': 0.0, 'seen': 0}     # weight-gradient side stream
+        self.side = {'stream': None, 'pending': [], 'keep': [], 'dirty': False}     # weight-gradient side stream
         self.deferred_counters = None       # inside ``deferred_counters``: the num_batches_tracked tensors to bump at exit
         self.call_log = None                # test infrastructure (``kernel_trace``): list of (C-ABI symbol, argument tuple) of every call made through _call
         # ---- taps

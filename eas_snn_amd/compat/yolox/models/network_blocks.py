@@ -276,9 +276,8 @@ class CSPLayer(nn.Module):
                 pair = [(self.conv1.bn, self.conv1.act), (self.conv2.bn, self.conv2.act)]
                 if not self.training and ops.fused_eval_ok(x, (c1, c2), pair):
                     # eval mode: the one convolution for both branches AND their two BN + LIF layers in one kernel
-                    packs = (getattr(self, '_eas_dual_packs', None) or {}).get('c12')
                     a, b = ops.conv_bn_lif_eval(x, (c1, c2), pair, cats=[None if len(self.m) else (buf, 0, sp_buf), (buf, h, sp_buf)],
-                                                planes=[want_a, sp_buf is not None], packs=ops.current_packs(packs))
+                                                planes=[want_a, sp_buf is not None], packs=ops.dual_packs_of(self, 'c12'))
                     if len(self.m):
                         for blk in self.m[:-1]:
                             a = blk(a)
@@ -316,9 +315,8 @@ class CSPLayer(nn.Module):
             norms = [self.conv1.eval_norm(), self.conv2.eval_norm()] if (dual and not self.training) else [None]
             if None not in norms and ops.fused_ann_eval_ok(x, (cs[0], cs[1]), norms):
                 # eval mode (also after fuse_model): the one convolution for both branches AND their BN + SiLU in one kernel
-                packs = (getattr(self, '_eas_dual_packs', None) or {}).get('c12')
                 a, b = ops.conv_bn_act_eval(x, (cs[0], cs[1]), norms, cats=[None if len(self.m) else (buf, 0), (buf, h)],
-                                            packs=ops.current_packs(packs))
+                                            packs=ops.dual_packs_of(self, 'c12'))
             elif dual and self.conv1.ann_fusable(x[:, :1]) and ops.conv_dual_ok(x, cs[0], cs[1]):
                 # conv1 and conv2 read the same x: ONE 1x1 convolution (weights packed from the two parameters), then the two BN + SiLU
                 # layers on the channel halves of its output; the input gradient is one convolution, no addition of two branch gradients

@@ -120,8 +120,7 @@ class YOLOXHead(nn.Module):
         norms = [a.eval_norm(), b.eval_norm()] if (ann_pair and not self.training) else [None]
         if None not in norms and ops.fused_ann_eval_ok(x, (a.conv, b.conv), norms):
             # eval mode (also after fuse_model): the one convolution for both towers AND their BN + SiLU in one kernel
-            packs = (getattr(self, '_eas_dual_packs', None) or {}).get(f'tower{k}')
-            ca, ra = ops.conv_bn_act_eval(x, (a.conv, b.conv), norms, packs=ops.current_packs(packs))
+            ca, ra = ops.conv_bn_act_eval(x, (a.conv, b.conv), norms, packs=ops.dual_packs_of(self, f'tower{k}'))
         elif ann_pair and a.ann_fusable(x[:, :1]) and b.ann_fusable(x[:, :1]) and ops.conv_dual_ok(x, a.conv, b.conv):
             sink = ops.conv_sink()
             if sink is not None:

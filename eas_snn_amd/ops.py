@@ -24,7 +24,7 @@ import types
 from . import ops_bn, ops_conv, ops_core, ops_lif, ops_sampler
 from ._ctx import ctx
 
-_PLUMBING = {'C', 'os', 'torch', '_lib', 'check', 'ptr', 'stream', 'opctx'}
+_PLUMBING = {'C', 'collections', 'os', 'torch', '_lib', 'check', 'ptr', 'stream', 'opctx'}
 for _m in (ops_core, ops_lif, ops_bn, ops_sampler, ops_conv):
     for _k, _v in vars(_m).items():
         if not _k.startswith('__') and _k not in _PLUMBING:
@@ -42,7 +42,7 @@ _ALIASES = {
     '_PLANES_SCOPE': 'planes_scope', '_INVSTD_SCOPE': 'invstd_scope', 'CONV_STATS': 'conv_stats', 'CONV_STATS_MAX_BLOCKS': 'conv_stats_max_blocks',
     '_WANT_CONV_STATS': 'want_conv_stats', '_CONV_STATS_SLOT': 'conv_stats_slot', 'FUSED_EVAL': 'fused_eval', '_REPLICAS': 'replicas',
     'ARSNN_FUSED': 'arsnn_fused', 'DEFER_WGRAD_REDUCE': 'defer_wgrad_reduce', '_PENDING_REDUCE': 'pending_reduce',
-    'WGRAD_SIDE_BATCH': 'wgrad_side_batch', 'WGRAD_SIDE_US': 'wgrad_side_us', 'WGRAD_SIDE_AT': 'wgrad_side_at', '_SIDE': 'side',
+    'WGRAD_SIDE_BATCH': 'wgrad_side_batch', '_SIDE': 'side',
     'VERIFY_SMALL_INT': 'verify_small_int', 'SMALL_DGRAD': 'small_dgrad', '_PACK_SCOPE': 'pack_scope', '_PACK_GEN': 'pack_gen', '_FROZEN': 'frozen',
     '_CONV_SINK': 'conv_sink', 'FUSED_ANN_EVAL': 'fused_ann_eval', '_DEFERRED': 'deferred_counters'}
 

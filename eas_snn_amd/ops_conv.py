@@ -1,6 +1,7 @@
 """Operator layer, dense convolutions on the matrix cores: forward / input gradient / weight gradient (eas_conv_*), weight packing and its
 scopes (``packed_weights``, ``frozen_weights``), dual convolutions, the weight-gradient side stream and deferred slab reductions, the
 fused eval-mode blocks (conv -> BN -> LIF, conv -> BN -> SiLU).  ``eas_snn_amd.ops`` re-exports everything here (``ops.<name>``)."""
+import collections
 import ctypes as C
 import os
 
@@ -100,6 +101,24 @@ def current_packs(packs):
     return packs if (packs is not None and opctx.pack_scope is not None and packs.get('gen') == opctx.pack_scope) else None
 
 
+def packs_of(conv):
+    """the packing of this nn.Conv2d's weight for the forward that is running now, or None (pack the weight as it is now)"""
+    return current_packs(getattr(conv, '_eas_packs', None))
+
+
+def dual_packs_of(owner, key):
+    """the packing of the concatenated weight of the pair registered as (owner, key) (owner.eas_dual_convs()) for the running forward, or None"""
+    return current_packs((getattr(owner, '_eas_dual_packs', None) or {}).get(key))
+
+
+def pack_mode(packs, mode, weight):
+    """this mode of a packing, or -- no packing, or one made without that mode -- pack now.  weight: the tensor, or the pair (wa, wb) of a
+    dual convolution (concatenated only when it has to be packed here)"""
+    if packs and mode in packs:
+        return packs[mode]
+    return conv_pack_weights(torch.cat(list(weight), 0) if isinstance(weight, tuple) else weight, mode)
+
+
 def dual_weights_ok(conv_a, conv_b):
     """two convolutions that read the same input and can run as one with concatenated weights (same geometry, no bias)"""
     conv_a, conv_b = _plain_conv(conv_a), _plain_conv(conv_b)
@@ -122,14 +141,12 @@ def conv_bn_lif_eval(x_seq, conv, layers, want_mean=False, residual=None, cats=N
     if isinstance(conv, tuple):
         ca, cb = _plain_conv(conv[0]), _plain_conv(conv[1])
         k, stride, Cout = ca.kernel_size[0], ca.stride[0], ca.out_channels + cb.out_channels
-        pk = packs[0] if packs else conv_pack_weights(torch.cat([ca.weight, cb.weight], 0), 0)
+        pk = pack_mode(packs, 0, (ca.weight, cb.weight))
     else:
         c = _plain_conv(conv)
         k, stride, Cout = c.kernel_size[0], c.stride[0], c.out_channels
-        pk = getattr(c, '_eas_packs', None)
-        pk = pk[0] if (pk is not None and opctx.pack_scope is not None and pk.get('gen') == opctx.pack_scope) else conv_pack_weights(c.weight, 0)
-    pad = k // 2
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        pk = pack_mode(packs_of(c), 0, c.weight)
+    Ho, Wo = conv_out_size(H, W, k, stride)
     HW = Ho * Wo
     base = getattr(x_seq, '_eas_base', None)
     d = _lib.EasConvBnLifEval()
@@ -224,7 +241,7 @@ def conv_bn_lif_eval(x_seq, conv, layers, want_mean=False, residual=None, cats=N
         outs.append(out)
     fl = 2.0 * T * N * Cout * HW * Cin * k * k / (T if d.x_shared else 1)
     nb = (2 if d.x_terms == 2 else 4) * (N if d.x_shared else T * N) * Cin * H * W + 2 * T * N * Cout * HW
-    _call('eas_conv_bn_lif_eval', nb, L.eas_conv_bn_lif_eval, C.byref(d), stream(), flops=fl, issue_flops=fl * (6 if d.x_terms == 3 else 3))
+    _call('eas_conv_bn_lif_eval', nb, L.eas_conv_bn_lif_eval, C.byref(d), stream(), flops=fl, issue_flops=fl * _term_products(d.x_terms))
     del keep
     if want_mean:
         return outs[0], rate
@@ -242,13 +259,24 @@ def conv_pack_weights(w, mode=0):
     return packed
 
 
+def conv_out_size(H, W, k, stride):
+    """(Ho, Wo) of a k x k convolution with padding k // 2"""
+    pad = k // 2
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def _term_products(x_terms):
+    """bf16 term products issued per multiply-accumulate (the ``issue_flops`` factor): 3 for a one-term input (spikes / small integers, as
+    fp32 or as spike planes), 6 for a real-valued input in three terms"""
+    return 6 if x_terms == 3 else 3
+
+
 def conv_fwd_packed(x, packed, bias, Cout, ksize, stride, x_terms, x_sp=None, act=0):
     """conv2d(x [NI,Cin,H,W], packed weights), padding ksize//2, on the matrix cores.  x_sp: x is a ghost and these are its spike planes
     [NI,Cin/8,H*W,8] (eas_conv_fwd_planes: same result, half the input bytes, no conversion)."""
     _dev(x, packed, bias)
     NI, Cin, Hi, Wi = x.shape
-    pad = ksize // 2
-    Ho, Wo = (Hi + 2 * pad - ksize) // stride + 1, (Wi + 2 * pad - ksize) // stride + 1
+    Ho, Wo = conv_out_size(Hi, Wi, ksize, stride)
     y = torch.empty((NI, Cout, Ho, Wo), dtype=torch.float32, device=packed.device)
     fl = 2.0 * y.numel() * Cin * ksize * ksize
     L = _lib.lib()
@@ -261,25 +289,25 @@ def conv_fwd_packed(x, packed, bias, Cout, ksize, stride, x_terms, x_sp=None, ac
             if 0 < nb <= opctx.conv_stats_max_blocks:
                 stats = torch.empty(Cout * nb * 2, dtype=torch.float64, device=y.device)
         _call('eas_conv_fwd', 2 * NI * Cin * Hi * Wi + 4 * y.numel(), L.eas_conv_fwd_planes, ptr(x_sp), ptr(packed), ptr(bias), ptr(y), NI, Cin, Cout,
-              Hi, Wi, ksize, stride, ptr(stats), nb if stats is not None else 0, stream(), flops=fl, issue_flops=fl * 3)
+              Hi, Wi, ksize, stride, ptr(stats), nb if stats is not None else 0, stream(), flops=fl, issue_flops=fl * _term_products(2))
         if stats is not None:
             opctx.conv_stats_slot = (y, nb, stats, y._version)
         return y
     x = _f32c(x)
     if act:             # y = act(conv + bias) from the epilogue (eas_conv_fwd_act: an eval-mode BaseConv with its BatchNorm folded in)
         _call('eas_conv_fwd', 4 * (x.numel() + y.numel()), L.eas_conv_fwd_act, ptr(x), ptr(packed), ptr(bias), ptr(y), NI, Cin, Cout, Hi, Wi,
-              ksize, stride, x_terms, int(act), _tag_flag(x, x_terms), stream(), flops=fl, issue_flops=fl * (3 if x_terms == 1 else 6))
+              ksize, stride, x_terms, int(act), _tag_flag(x, x_terms), stream(), flops=fl, issue_flops=fl * _term_products(x_terms))
         return y
     if opctx.want_conv_stats and bias is None:
         nb = _conv_stats_blocks(L, (NI, Cin, Cout, Hi, Wi, ksize, stride, x_terms))
         if 0 < nb <= opctx.conv_stats_max_blocks:
             stats = torch.empty(Cout * nb * 2, dtype=torch.float64, device=x.device)
             _call('eas_conv_fwd', 4 * (x.numel() + y.numel()), L.eas_conv_fwd_stats, ptr(x), ptr(packed), ptr(y), NI, Cin, Cout, Hi, Wi,
-                  ksize, stride, x_terms, _tag_flag(x, x_terms), ptr(stats), nb, stream(), flops=fl, issue_flops=fl * (3 if x_terms == 1 else 6))
+                  ksize, stride, x_terms, _tag_flag(x, x_terms), ptr(stats), nb, stream(), flops=fl, issue_flops=fl * _term_products(x_terms))
             opctx.conv_stats_slot = (y, nb, stats, y._version)
             return y
     _call('eas_conv_fwd', 4 * (x.numel() + y.numel()), L.eas_conv_fwd, ptr(x), ptr(packed), ptr(bias), ptr(y), NI, Cin, Cout, Hi, Wi,
-          ksize, stride, x_terms, _tag_flag(x, x_terms), stream(), flops=fl, issue_flops=fl * (3 if x_terms == 1 else 6))
+          ksize, stride, x_terms, _tag_flag(x, x_terms), stream(), flops=fl, issue_flops=fl * _term_products(x_terms))
     return y
 
 
@@ -324,23 +352,19 @@ class deferred_wgrad_reductions:
 
 
 
-def _wgrad_launch(job, keep, defer, issue_flops=0.0, nbytes=0.0):
+def _wgrad_launch(job, keep, defer):
     """run the slab-kernel launch ``job()`` now, or -- a deferred gradient with the side stream switched on -- with the next batch"""
-    if not (defer and (opctx.wgrad_side_batch > 0 or opctx.wgrad_side_us > 0 or opctx.wgrad_side_at) and opctx.defer_wgrad_reduce):
+    if not (defer and opctx.wgrad_side_batch > 0 and opctx.defer_wgrad_reduce):
         job()
         return
     opctx.side['pending'].append(job)
     opctx.side['keep'].extend(keep)
-    opctx.side['us'] += max(issue_flops / 1.3e15, nbytes / 5e12) * 1e6
-    opctx.side['seen'] += 1
-    if ((opctx.wgrad_side_batch > 0 and len(opctx.side['pending']) >= opctx.wgrad_side_batch) or (opctx.wgrad_side_us > 0 and opctx.side['us'] >= opctx.wgrad_side_us)
-            or opctx.side['seen'] in opctx.wgrad_side_at):
+    if len(opctx.side['pending']) >= opctx.wgrad_side_batch:
         _side_flush()
 
 
 def _side_flush():
     jobs, opctx.side['pending'] = opctx.side['pending'], []
-    opctx.side['us'] = 0.0
     if not jobs:
         return
     if opctx.side['stream'] is None:
@@ -358,10 +382,7 @@ def _side_join():
     if opctx.side['dirty']:
         torch.cuda.current_stream().wait_stream(opctx.side['stream'])
         opctx.side['dirty'] = False
-    if os.environ.get('EAS_WGRAD_SIDE_LOG') and opctx.side['seen']:
-        print(f"[eas] side stream: {opctx.side['seen']} slab launches in this pass", flush=True)
     opctx.side['keep'] = []
-    opctx.side['seen'] = 0
 
 
 def _flush_wgrad_reductions():
@@ -457,7 +478,7 @@ def conv_wgrad(x, gy, ksize, stride, x_terms, x_sp=None, defer=False, w=None, sp
 
         def job():
             got = _partial_call('eas_conv_wgrad', 2 * NI * Cin * Hi * Wi + 4 * gy.numel(), L.eas_conv_wgrad_planes_partial, ptr(x_sp), ptr(gy), ptr(ws),
-                                NI, Cin, Cout, Hi, Wi, ksize, stride, stream(), flops=fl, issue_flops=fl * 3)
+                                NI, Cin, Cout, Hi, Wi, ksize, stride, stream(), flops=fl, issue_flops=fl * _term_products(2))
             assert got == ns, (got, ns)
         keep = (x_sp, gy, ws)
     else:
@@ -466,44 +487,77 @@ def conv_wgrad(x, gy, ksize, stride, x_terms, x_sp=None, defer=False, w=None, sp
 
         def job():
             got = _partial_call('eas_conv_wgrad', 4 * (x.numel() + gy.numel()), L.eas_conv_wgrad_partial, ptr(x), ptr(gy), ptr(ws), NI, Cin, Cout,
-                                Hi, Wi, ksize, stride, x_terms, stream(), flops=fl, issue_flops=fl * (3 if x_terms == 1 else 6))
+                                Hi, Wi, ksize, stride, x_terms, stream(), flops=fl, issue_flops=fl * _term_products(x_terms))
             assert got == ns, (got, ns)
         keep = (x, gy, ws)
-    _wgrad_launch(job, keep, defer, fl * (3 if (x_sp is not None or x_terms == 1) else 6), 4.0 * gy.numel() + (2.0 if x_sp is not None else 4.0) * NI * Cin * Hi * Wi)
+    _wgrad_launch(job, keep, defer)
     _wgrad_finish(ws, gw, ns, defer, w, split)
     return gw
 
 
-def conv_eligible(x, conv):
+def _conv_form_ok(conv):
+    """what the matrix-core kernels ask of the convolution itself: dense, 1x1 at stride 1 or 3x3 at stride 1 / 2, zero padding k // 2,
+    input channels in whole 8-groups"""
     k = conv.kernel_size[0]
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.groups == 1 and conv.dilation == (1, 1)
-            and conv.kernel_size in ((1, 1), (3, 3)) and conv.stride in ((1, 1), (2, 2)) and conv.padding == (k // 2, k // 2)
-            and conv.padding_mode == 'zeros' and x.shape[1] % 8 == 0 and (k == 1 or x.shape[-1] % 2 == 0)
-            and not (k == 1 and conv.stride != (1, 1)))
+    return (conv.groups == 1 and conv.dilation == (1, 1) and conv.kernel_size in ((1, 1), (3, 3))
+            and conv.stride in ((1, 1), (2, 2)) and conv.padding == (k // 2, k // 2) and conv.padding_mode == 'zeros'
+            and conv.in_channels % 8 == 0 and not (k == 1 and conv.stride != (1, 1)))
 
 
-_FWD_SUPPORT = {}
+def _static_conv_ok(conv):
+    return type(conv) is torch.nn.Conv2d and _conv_form_ok(conv)
 
 
-def conv_fwd_supported(NI, Cin, Cout, Hi, Wi, k, stride, x_terms):
-    """geometry query of eas_conv_fwd (cached): False -> the layer keeps the library convolution"""
-    key = (NI, Cin, Cout, Hi, Wi, k, stride, x_terms)
-    r = _FWD_SUPPORT.get(key)
+def conv_eligible(x, conv):
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _conv_form_ok(conv) and x.shape[1] % 8 == 0
+            and (conv.kernel_size[0] == 1 or x.shape[-1] % 2 == 0))
+
+
+def dgrad_mode(k, stride, Cout):
+    """the static part of the input-gradient rule = the transposed packing a convolution's input gradient reads.  1: stride 1, eas_conv_fwd
+    on grad_y with the weights packed transposed + flipped (1x1: any channel count -- the 1/4/num_classes-channel prediction convolutions
+    included; 3x3: Cout in whole 8-groups); 2: 3x3 at stride 2, eas_conv_dgrad_s2; None: the library's input gradient"""
+    if stride == 1 and (k == 1 or Cout % 8 == 0):
+        return 1
+    if stride == 2 and k == 3 and Cout % 8 == 0:
+        return 2
+    return None
+
+
+# which kernels a dense convolution of one geometry runs on (``conv_route``)
+ConvRoute = collections.namedtuple('ConvRoute', 'Ho Wo fwd dgrad wgrad')
+_ROUTES = {}
+
+
+def conv_route(x_shape, Cout, k, stride, x_terms):
+    """The routing of conv2d(x [NI,Cin,H,W], w [Cout,Cin,k,k], stride, padding k // 2), asked of the library once per geometry and input form
+    (x_terms 1: one term, 2: spike planes, 3: three terms):
+      Ho, Wo   the output size
+      fwd      eas_conv_fwd has a tile (False: the layer keeps the library convolution)
+      dgrad    1 / 2: the input gradient runs on the kernel that reads this packing mode (``dgrad_mode``) and has a tile there; None: library
+      wgrad    the weight gradient runs on the matrix cores
+    The stem's small input gradient, ``needs_input_grad`` and the run-time fallback of eas_conv_dgrad_s2 stay with ``_ConvFn.backward``."""
+    NI, Cin, H, W = x_shape
+    key = (NI, Cin, Cout, H, W, k, stride, x_terms)
+    r = _ROUTES.get(key)
     if r is None:
-        r = _FWD_SUPPORT[key] = bool(_lib.lib().eas_conv_fwd_supported(*key))
+        L = _lib.lib()
+        Ho, Wo = conv_out_size(H, W, k, stride)
+        # both input-gradient kernels walk grad_y [NI,Cout,Ho,Wo] with the stride-1 tiles of eas_conv_fwd (stride 2: even Wo, two columns wider)
+        dgrad = dgrad_mode(k, stride, Cout)
+        if dgrad == 2 and Wo % 2:
+            dgrad = None
+        if dgrad and not L.eas_conv_fwd_supported(NI, Cout, Cin, Ho, Wo + (2 if dgrad == 2 else 0), k, 1, 3):
+            dgrad = None
+        wgrad = L.eas_conv_wgrad_workspace_floats(*key) > 0 and (k == 1 or (Cout % 8 == 0 and Wo % 2 == 0 and (Ho * Wo) % 4 == 0))
+        r = _ROUTES[key] = ConvRoute(Ho, Wo, bool(L.eas_conv_fwd_supported(*key)), dgrad, bool(wgrad))
     return r
 
 
 def _planes_conv_ok(x, w, stride):
     """forward and weight gradient of conv(x [NI,Cin,H,W] as spike planes, w) both have a planes kernel for this geometry"""
-    NI, Cin, H, W = x.shape
-    Cout, k = w.shape[0], w.shape[-1]
-    if not conv_fwd_supported(NI, Cin, Cout, H, W, k, stride, 2):
-        return False
-    pad = k // 2
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    return bool(_lib.lib().eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, k, stride, 2) > 0
-                and (k == 1 or (Cout % 8 == 0 and Wo % 2 == 0 and (Ho * Wo) % 4 == 0)))
+    r = conv_route(x.shape, w.shape[0], w.shape[-1], stride, 2)
+    return r.fwd and r.wgrad
 
 
 def channel_sum(g):
@@ -531,15 +585,15 @@ class _ConvFn(torch.autograd.Function):
         k, Cout = w.shape[-1], w.shape[0]
         if x_sp is not None:
             assert x_terms == 1
-        if conv_fwd_supported(x.shape[0], x.shape[1], Cout, x.shape[2], x.shape[3], k, stride, 2 if x_sp is not None else x_terms):
-            pk = packs[0] if packs and 0 in packs else conv_pack_weights(w, 0)
-            y = conv_fwd_packed(x, pk, bias, Cout, k, stride, x_terms, x_sp)
+        route = conv_route(x.shape, Cout, k, stride, 2 if x_sp is not None else x_terms)
+        if route.fwd:
+            y = conv_fwd_packed(x, pack_mode(packs, 0, w), bias, Cout, k, stride, x_terms, x_sp)
         else:       # no tile for this geometry (not reached by the EAS-SNN models): library forward
             if x_sp is not None:
                 raise _lib.EasHipError('no matrix-core tile for a convolution on spike planes')
             y = torch.ops.aten.convolution(x, w, bias, (stride, stride), (k // 2, k // 2), (1, 1), False, (0, 0), 1)
         ctx.save_for_backward(x, w, x_sp)
-        ctx.cfg = (k, stride, x_terms, bias is not None)
+        ctx.cfg = (k, stride, x_terms, bias is not None, route)
         ctx.packs = packs        # valid for the backward of this forward (same weights; autograd forbids changing them in between)
         ctx.tag = opctx.tag
         return y
@@ -547,22 +601,16 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, w, x_sp = ctx.saved_tensors
-        k, stride, x_terms, has_bias = ctx.cfg
+        k, stride, x_terms, has_bias, route = ctx.cfg
         packs = ctx.packs
         gy = _f32c(gy)
         gx = gw = gb = None
         Cin = w.shape[1]
         if opctx.timer is not None and ctx.tag is not None:
             set_tag(ctx.tag)
-        # the input gradient of a stride-1 convolution is eas_conv_fwd on grad_y with the weights packed transposed + flipped
-        # (1x1: any channel count -- the 1/4/num_classes-channel prediction convolutions included; 3x3: Cout in whole 8-groups)
-        own_d = (ctx.needs_input_grad[0] and stride == 1 and (k == 1 or w.shape[0] % 8 == 0)
-                 and conv_fwd_supported(gy.shape[0], w.shape[0], Cin, gy.shape[2], gy.shape[3], k, 1, 3))
-        own_w = ctx.needs_input_grad[1] and _lib.lib().eas_conv_wgrad_workspace_floats(
-            x.shape[0], Cin, w.shape[0], x.shape[2], x.shape[3], k, stride, 2 if x_sp is not None else x_terms) > 0 and (
-                k == 1 or (w.shape[0] % 8 == 0 and gy.shape[-1] % 2 == 0 and (gy.shape[-1] * gy.shape[-2]) % 4 == 0))
-        own_d2 = (ctx.needs_input_grad[0] and stride == 2 and k == 3 and w.shape[0] % 8 == 0
-                  and gy.shape[-1] % 2 == 0 and conv_fwd_supported(gy.shape[0], w.shape[0], Cin, gy.shape[2], gy.shape[3] + 2, k, 1, 3))
+        own_d = ctx.needs_input_grad[0] and route.dgrad == 1
+        own_d2 = ctx.needs_input_grad[0] and route.dgrad == 2
+        own_w = ctx.needs_input_grad[1] and route.wgrad
         small_d = (opctx.small_dgrad and ctx.needs_input_grad[0] and stride == 1 and k == 3 and w.dtype == torch.float32
                    and _lib.lib().eas_conv_dgrad_small_supported(gy.shape[0], Cin, w.shape[0], gy.shape[2], gy.shape[3]))
         if small_d:
@@ -575,12 +623,11 @@ class _ConvFn(torch.autograd.Function):
                   issue_flops=6 * 2.0 * gy.shape[0] * gy.shape[2] * gy.shape[3] * 96 * 16 * ksteps)
             own_d = True
         elif own_d:
-            pk = packs[1] if packs and 1 in packs else conv_pack_weights(w, 1)
-            gx = conv_fwd_packed(gy, pk, None, Cin, k, 1, 3)
+            gx = conv_fwd_packed(gy, pack_mode(packs, 1, w), None, Cin, k, 1, 3)
         elif own_d2:
             gx = torch.empty_like(x)
             fl = 2.0 * gy.numel() * Cin * 9
-            pk = packs[2] if packs and 2 in packs else conv_pack_weights(w, 2)
+            pk = pack_mode(packs, 2, w)
             try:
                 _call('eas_conv_fwd', 4 * (x.numel() + gy.numel()), _lib.lib().eas_conv_dgrad_s2, ptr(gy), ptr(pk), ptr(gx),
                       x.shape[0], Cin, w.shape[0], x.shape[2], x.shape[3], stream(), flops=fl, issue_flops=6 * fl)
@@ -601,15 +648,6 @@ class _ConvFn(torch.autograd.Function):
         if has_bias and ctx.needs_input_grad[2]:
             gb = channel_sum(gy)
         return gx, gw, gb, None, None, None, None
-
-
-def _static_conv_ok(conv):
-    if type(conv) is not torch.nn.Conv2d:
-        return False
-    k = conv.kernel_size[0]
-    return (conv.groups == 1 and conv.dilation == (1, 1) and conv.kernel_size in ((1, 1), (3, 3))
-            and conv.stride in ((1, 1), (2, 2)) and conv.padding == (k // 2, k // 2) and conv.padding_mode == 'zeros'
-            and conv.in_channels % 8 == 0 and not (k == 1 and conv.stride != (1, 1)))
 
 
 class frozen_weights:
@@ -684,8 +722,8 @@ def prepack_conv_weights(model):
         dev = convs[0].weight.device
         for c in convs:
             k, Cout, Cin = c.kernel_size[0], c.out_channels, c.in_channels
-            modes = [0] if fwd_only else ([0] + ([1] if c.stride == (1, 1) and (k == 1 or Cout % 8 == 0) else [])
-                                          + ([2] if c.stride == (2, 2) and k == 3 and Cout % 8 == 0 else []))
+            tmode = None if fwd_only else dgrad_mode(k, c.stride[0], Cout)
+            modes = [0] if tmode is None else [0, tmode]
             d = {}
             for m in modes:
                 d[m] = torch.empty(L.eas_conv_packed_weight_bytes(Cout, Cin, k, m), dtype=torch.uint8, device=dev)
@@ -724,8 +762,7 @@ class _ConvDualFn(torch.autograd.Function):
     def forward(ctx, x, wa, wb, x_terms, packs, x_sp=None):
         _dev(x, wa, wb)
         k, Ca, Cout = wa.shape[-1], wa.shape[0], wa.shape[0] + wb.shape[0]
-        pk = packs[0] if packs else conv_pack_weights(torch.cat([wa, wb], 0), 0)
-        y = conv_fwd_packed(x, pk, None, Cout, k, 1, x_terms, x_sp)
+        y = conv_fwd_packed(x, pack_mode(packs, 0, (wa, wb)), None, Cout, k, 1, x_terms, x_sp)
         ctx.save_for_backward(x, wa, wb, x_sp)
         ctx.cfg = (k, x_terms, Ca)
         ctx.packs = packs
@@ -738,8 +775,7 @@ class _ConvDualFn(torch.autograd.Function):
         gy = _f32c(gy)
         gx = ga = gb = None
         if ctx.needs_input_grad[0]:
-            pk = ctx.packs[1] if ctx.packs and 1 in ctx.packs else conv_pack_weights(torch.cat([wa, wb], 0), 1)
-            gx = conv_fwd_packed(gy, pk, None, x.shape[1], k, 1, 3)
+            gx = conv_fwd_packed(gy, pack_mode(ctx.packs, 1, (wa, wb)), None, x.shape[1], k, 1, 3)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             # ONE weight gradient for the two parameters: its slab reduction waits for the end of the backward pass with all the others
             # (each parameter adopts its row block of the one tensor as .grad) where that is sound for both, else it runs now
@@ -762,11 +798,8 @@ def conv_dual_ok(x, conv_a, conv_b):
         return False
     if any(c._forward_hooks or c._forward_pre_hooks for c in (conv_a, conv_b)) or torch.nn.modules.module._global_forward_hooks:
         return False
-    NI, _, H, W = x.shape
-    xt = 2 if planes_of(x) is not None else (1 if is_small_int(x) else 3)
-    L = _lib.lib()
-    return bool(conv_fwd_supported(NI, Cin, Cout, H, W, k, 1, xt) and conv_fwd_supported(NI, Cout, Cin, H, W, k, 1, 3)
-                and L.eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, k, 1, xt) > 0 and (k == 1 or (W % 2 == 0 and (H * W) % 4 == 0)))
+    r = conv_route(x.shape, Cout, k, 1, 2 if planes_of(x) is not None else (1 if is_small_int(x) else 3))
+    return r.fwd and r.dgrad == 1 and r.wgrad
 
 
 def conv2d_dual(x, conv_a, conv_b, owner=None, key=None):
@@ -774,11 +807,7 @@ def conv2d_dual(x, conv_a, conv_b, owner=None, key=None):
     ``packed_weights`` left the packing of the concatenated weight (owner.eas_dual_convs())."""
     small = is_small_int(x)
     _verify_tags(x, small)
-    packs = None
-    if owner is not None:
-        packs = (getattr(owner, '_eas_dual_packs', None) or {}).get(key)
-        if packs is not None and (opctx.pack_scope is None or packs.get('gen') != opctx.pack_scope):
-            packs = None        # not inside the forward that made this packing: pack the weights as they are now
+    packs = dual_packs_of(owner, key)     # None outside the forward that made the packing: the weights are packed as they are now
     return _ConvDualFn.apply(x, conv_a.weight, conv_b.weight, 1 if small else 3, packs, planes_of(x) if small else None)
 
 
@@ -859,12 +888,10 @@ def conv_act_eval(x, conv, act='silu'):
     small = is_small_int(x)
     xd = dense(x)
     xt = 1 if small else 3
-    if not conv_fwd_supported(xd.shape[0], xd.shape[1], conv.out_channels, xd.shape[2], xd.shape[3], k, s_, xt):
+    if not conv_route(xd.shape, conv.out_channels, k, s_, xt).fwd:
         return None
     _verify_tags(xd, small)
-    packs = getattr(conv, '_eas_packs', None)
-    pk = packs[0] if (packs is not None and opctx.pack_scope is not None and packs.get('gen') == opctx.pack_scope) else conv_pack_weights(conv.weight, 0)
-    return conv_fwd_packed(xd, pk, conv.bias, conv.out_channels, k, s_, xt, act=1)
+    return conv_fwd_packed(xd, pack_mode(packs_of(conv), 0, conv.weight), conv.bias, conv.out_channels, k, s_, xt, act=1)
 
 
 # ------------------------------------------------------------------------------------------------ fused real-valued eval block (conv -> BN -> SiLU, ONE kernel)
@@ -909,7 +936,7 @@ def fused_ann_eval_ok(x, conv, norms):
     if is_small_int(x):
         return False        # the epilogue is instantiated for real-valued inputs (three bf16 terms): what the ANN neck / head read
     cout = sum(c.out_channels for c in convs)
-    return conv_fwd_supported(x.shape[0], x.shape[1], cout, x.shape[2], x.shape[3], c0.kernel_size[0], c0.stride[0], 3)
+    return conv_route(x.shape, cout, c0.kernel_size[0], c0.stride[0], 3).fwd
 
 
 _UNIT_AFFINE = {}
@@ -924,45 +951,34 @@ def _unit_affine(C_, device):
     return t
 
 
-def conv_bn_act_eval(x, conv, bns, cats=None, packs=None, act='silu'):
-    """act(bn(conv(x))) in one kernel (caller checked ``fused_ann_eval_ok``).  conv / bns: one convolution and its BatchNorm, or two that read
-    the same input (``packs``: the packing of their concatenated weight made by ``packed_weights``, or None); a bias tensor in place of a
-    BatchNorm = a block folded by ``fuse_model`` (act(conv(x) + bias)).  cats[i] = (buffer [NI,Ctot,H,W], first channel) or None.  Returns one
-    tensor per range (a view into the buffer where given)."""
-    L = _lib.lib()
-    convs = conv if isinstance(conv, tuple) else (conv,)
-    cats = cats or [None] * len(bns)
+def _fill_conv_bn_act_eval(d, x, convs, norms, pk, keep, cats=None, act=1):
+    """Fill the EasConvBnActEval descriptor ``d`` for act(norm(conv(x))) with the packed weight ``pk`` of ``convs`` (one convolution, or two
+    that run as one) and one output range per entry of ``norms`` (an eval-mode BatchNorm2d, or the bias tensor of a block folded by
+    ``fuse_model``).  cats[i] = (buffer [NI,Ctot,Ho,Wo], first channel) or None.  Returns the output tensor of every range (a view into the
+    buffer where given); what the descriptor points to is appended to ``keep``."""
     c0 = convs[0]
     k, stride = c0.kernel_size[0], c0.stride[0]
     Cout = sum(c.out_channels for c in convs)
     NI, Cin, H, W = x.shape
-    pad = k // 2
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    if len(convs) == 2:
-        pk = packs[0] if packs else conv_pack_weights(torch.cat([convs[0].weight, convs[1].weight], 0), 0)
-    else:
-        pk = getattr(c0, '_eas_packs', None)
-        pk = pk[0] if (pk is not None and opctx.pack_scope is not None and pk.get('gen') == opctx.pack_scope) else conv_pack_weights(c0.weight, 0)
-    d = _lib.EasConvBnActEval()
+    Ho, Wo = conv_out_size(H, W, k, stride)
     xd = _f32c(x)
-    keep = [pk, xd]
-    d.x, d.x_terms = ptr(xd), 3
-    d.packed_w = ptr(pk)
+    keep += [pk, xd]
+    d.x, d.x_terms, d.packed_w = ptr(xd), 3, ptr(pk)
     d.NI, d.Cin, d.Cout, d.Hi, d.Wi, d.ksize, d.stride = NI, Cin, Cout, H, W, k, stride
-    d.act = 1 if act == 'silu' else 0
-    d.csplit = convs[0].out_channels
+    d.act = act
+    d.csplit = c0.out_channels
     outs = []
-    for i, bn in enumerate(bns):
+    for i, nm in enumerate(norms):
         r = d.range[i]
         Cr = convs[i].out_channels if len(convs) > 1 else Cout
-        if torch.is_tensor(bn):          # folded block: z = fma(acc, 1 * 1, bias - 0 * 1) = acc + bias
+        if torch.is_tensor(nm):          # folded block: z = fma(acc, 1 * 1, bias - 0 * 1) = acc + bias
             ones, zeros = _unit_affine(Cr, x.device)
-            r.gamma, r.beta, r.mean, r.invstd = ptr(ones), ptr(bn), ptr(zeros), ptr(ones)
+            r.gamma, r.beta, r.mean, r.invstd = ptr(ones), ptr(nm), ptr(zeros), ptr(ones)
         else:
-            invstd = _eval_invstd(bn.running_var, bn.eps)
+            invstd = _eval_invstd(nm.running_var, nm.eps)
             keep.append(invstd)
-            r.gamma, r.beta, r.mean, r.invstd = ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(invstd)
-        cat = cats[i]
+            r.gamma, r.beta, r.mean, r.invstd = ptr(nm.weight), ptr(nm.bias), ptr(nm.running_mean), ptr(invstd)
+        cat = cats[i] if cats else None
         if cat is not None:
             buf, c0_ = cat[0], int(cat[1])
             assert buf.is_contiguous() and buf.dtype == torch.float32 and tuple(buf.shape) == (NI, buf.shape[1], Ho, Wo)
@@ -972,9 +988,25 @@ def conv_bn_act_eval(x, conv, bns, cats=None, packs=None, act='silu'):
             out = torch.empty((NI, Cr, Ho, Wo), dtype=torch.float32, device=x.device)
             r.out, r.out_ctot, r.out_c0 = ptr(out), Cr, 0
         outs.append(out)
-    fl = 2.0 * NI * Cout * Ho * Wo * Cin * k * k
-    nb = 4 * NI * Cin * H * W + 4 * NI * Cout * Ho * Wo
-    _call('eas_conv_fwd', nb, L.eas_conv_bn_act_eval, C.byref(d), None, stream(), flops=fl, issue_flops=fl * 6)
+    return outs
+
+
+def conv_bn_act_eval(x, conv, bns, cats=None, packs=None, act='silu'):
+    """act(bn(conv(x))) in one kernel (caller checked ``fused_ann_eval_ok``).  conv / bns: one convolution and its BatchNorm, or two that read
+    the same input (``packs``: the packing of their concatenated weight made by ``packed_weights``, or None); a bias tensor in place of a
+    BatchNorm = a block folded by ``fuse_model`` (act(conv(x) + bias)).  cats[i] = (buffer [NI,Ctot,H,W], first channel) or None.  Returns one
+    tensor per range (a view into the buffer where given)."""
+    convs = conv if isinstance(conv, tuple) else (conv,)
+    if len(convs) == 2:
+        pk = pack_mode(packs, 0, (convs[0].weight, convs[1].weight))
+    else:
+        pk = pack_mode(packs_of(convs[0]), 0, convs[0].weight)
+    d = _lib.EasConvBnActEval()
+    keep = []
+    outs = _fill_conv_bn_act_eval(d, x, convs, bns, pk, keep, cats, 1 if act == 'silu' else 0)
+    n_out = sum(o.numel() for o in outs)
+    fl = 2.0 * n_out * d.Cin * d.ksize * d.ksize
+    _call('eas_conv_fwd', 4 * (x.numel() + n_out), _lib.lib().eas_conv_bn_act_eval, C.byref(d), None, stream(), flops=fl, issue_flops=fl * _term_products(3))
     del keep
     return outs if len(bns) > 1 else outs[0]
 
@@ -996,7 +1028,4 @@ def conv2d(x, conv, small_int=None):
     if planes_of(x) is not None and not (small_int and _planes_conv_ok(x, conv.weight, conv.stride[0])):
         x = dense(x)            # no planes form of this geometry: the fp32 form of the same kernels
     _verify_tags(x, small_int)
-    packs = getattr(conv, '_eas_packs', None)
-    if packs is not None and (opctx.pack_scope is None or packs.get('gen') != opctx.pack_scope):
-        packs = None            # not inside the forward that made this packing: pack the weight as it is now
-    return _ConvFn.apply(x, conv.weight, conv.bias, conv.stride[0], 1 if small_int else 3, packs, planes_of(x) if small_int else None)
+    return _ConvFn.apply(x, conv.weight, conv.bias, conv.stride[0], 1 if small_int else 3, packs_of(conv), planes_of(x) if small_int else None)

@@ -12,6 +12,7 @@ import os
 import torch
 
 from . import _lib, ops
+from ._ctx import ctx as opctx
 from ._lib import check, ptr, stream
 
 ENABLED = os.environ.get('EAS_HEAD_GROUP', '1') == '1'      # development switch: 0 = the per-level operators
@@ -72,12 +73,47 @@ def _launch_conv_group(xs, pks, biases, ys, stats, k, accumulate=False):
     ops._call('eas_conv_fwd', nbytes, _lib.lib().eas_conv_fwd_group, arr, n, k, 3, stream(), flops=fl, issue_flops=6 * fl)
 
 
-def _pack_of(conv, mode):
-    """the packing of ``conv.weight`` made by ``ops.packed_weights`` for the running forward, or a fresh one"""
-    packs = getattr(conv, '_eas_packs', None)
-    if packs is not None and ops._PACK_SCOPE is not None and packs.get('gen') == ops._PACK_SCOPE and mode in packs:
-        return packs
-    return None
+def _wgrad_group(xs, gys, k, targets):
+    """[grad_w_i] of the stride-1 k x k convolutions of real-valued xs[i] given grad_y gys[i]: the slab kernels of all problems in one grid,
+    the fixed-order reductions with the step's other weight gradients at the end of the backward pass (ops._wgrad_finish).  targets[i] =
+    (defer, w, split) as ``ops.conv_wgrad`` takes them.  A set of problems the group plan does not take (some weights frozen) runs one by one."""
+    ns = _wgrad_plan(tuple((x.shape[0], x.shape[1], gy.shape[1], x.shape[2], x.shape[3]) for x, gy in zip(xs, gys)), k)
+    if ns is None:
+        return [ops.conv_wgrad(x, gy, k, 1, 3, None, defer=df, w=w, split=sp) for x, gy, (df, w, sp) in zip(xs, gys, targets)]
+    m = len(xs)
+    arr = (_lib.EasWgradProblem * m)()
+    wss = []
+    nbytes, fl = 0, 0.0
+    for q, x, gy, s_ in zip(arr, xs, gys, ns):
+        ws = torch.empty(s_ * gy.shape[1] * x.shape[1] * k * k, dtype=torch.float32, device=x.device)
+        wss.append(ws)
+        q.x, q.grad_y, q.workspace = ptr(x), ptr(gy), ptr(ws)
+        q.NI, q.Cin, q.Cout, q.Hi, q.Wi = x.shape[0], x.shape[1], gy.shape[1], x.shape[2], x.shape[3]
+        nbytes += 4 * (x.numel() + gy.numel())
+        fl += 2.0 * gy.numel() * x.shape[1] * k * k
+
+    def job():
+        ops._call('eas_conv_wgrad', nbytes, _lib.lib().eas_conv_wgrad_group_partial, arr, m, k, 3, stream(), flops=fl, issue_flops=6 * fl)
+    ops._wgrad_launch(job, list(xs) + list(gys) + wss, all(df for df, _, _ in targets))
+    gws = []
+    for x, gy, ws, s_, (df, w, sp) in zip(xs, gys, wss, ns, targets):
+        gw = torch.empty((gy.shape[1], x.shape[1], k, k), dtype=torch.float32, device=x.device)
+        ops._wgrad_finish(ws, gw, s_, df, w, sp)
+        gws.append(gw)
+    return gws
+
+
+def _bias_grad_group(gys):
+    """[gy.sum((0, 2, 3))] of all problems as one launch (``ops.channel_sum`` per problem)"""
+    m = len(gys)
+    arr = (_lib.EasChannelSumProblem * m)()
+    gbs = []
+    for q, gy in zip(arr, gys):
+        gb = torch.empty(gy.shape[1], dtype=torch.float32, device=gy.device)
+        gbs.append(gb)
+        q.g, q.out, q.N, q.C, q.HW = ptr(gy), ptr(gb), gy.shape[0], gy.shape[1], gy.shape[2] * gy.shape[3]
+    check(_lib.lib().eas_channel_sum_group(arr, m, stream()), 'eas_channel_sum_group')
+    return gbs
 
 
 class _ConvGroupFn(torch.autograd.Function):
@@ -95,12 +131,7 @@ class _ConvGroupFn(torch.autograd.Function):
         biases = tensors[(3 if dual else 2) * n:(4 if dual else 3) * n] if has_bias else None
         packs = cfg['packs']
         couts = [was[i].shape[0] + (wbs[i].shape[0] if dual else 0) for i in range(n)]
-        pks = []
-        for i in range(n):
-            if packs[i] is not None and 0 in packs[i]:
-                pks.append(packs[i][0])
-            else:
-                pks.append(ops.conv_pack_weights(torch.cat([was[i], wbs[i]], 0) if dual else was[i], 0))
+        pks = [ops.pack_mode(packs[i], 0, (was[i], wbs[i]) if dual else was[i]) for i in range(n)]
         ys = [torch.empty((x.shape[0], co, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device) for x, co in zip(xs, couts)]
         stats = None
         if want_stats:
@@ -109,7 +140,7 @@ class _ConvGroupFn(torch.autograd.Function):
         _launch_conv_group(xs, pks, biases, ys, stats, k)
         ctx.save_for_backward(*xs, *was, *(wbs or ()))
         ctx.cfg = cfg
-        ctx.tag = ops._TAG
+        ctx.tag = opctx.tag
         if want_stats:
             ctx.mark_non_differentiable(*stats)
             return tuple(ys) + tuple(stats)
@@ -123,7 +154,7 @@ class _ConvGroupFn(torch.autograd.Function):
         xs, was = saved[:n], saved[n:2 * n]
         wbs = saved[2 * n:3 * n] if dual else None
         packs = cfg['packs']
-        if ops._TIMER is not None and ctx.tag is not None:
+        if opctx.timer is not None and ctx.tag is not None:
             ops.set_tag(ctx.tag)
         gys = [ops._f32c(g) if g is not None else torch.zeros((x.shape[0], was[i].shape[0] + (wbs[i].shape[0] if dual else 0)) + tuple(x.shape[2:]),
                                                                dtype=torch.float32, device=x.device)
@@ -133,59 +164,23 @@ class _ConvGroupFn(torch.autograd.Function):
         # ---- input gradients: the same convolution on grad_y with the weights packed transposed + flipped
         need_x = [i for i in range(n) if ctx.needs_input_grad[1 + i]]
         if need_x:
-            pks = []
-            for i in need_x:
-                if packs[i] is not None and 1 in packs[i]:
-                    pks.append(packs[i][1])
-                else:
-                    pks.append(ops.conv_pack_weights(torch.cat([was[i], wbs[i]], 0) if dual else was[i], 1))
+            pks = [ops.pack_mode(packs[i], 1, (was[i], wbs[i]) if dual else was[i]) for i in need_x]
             gxs = [torch.empty_like(xs[i]) for i in need_x]
             _launch_conv_group([gys[i] for i in need_x], pks, None, gxs, None, k)
             for i, gx in zip(need_x, gxs):
                 out[i] = gx
-        # ---- weight gradients: the slab kernels of all problems in one grid, the fixed-order reductions with the step's other weight
-        # gradients at the end of the backward pass (ops._wgrad_finish)
+        # ---- weight gradients (of a pair: ONE gradient, handed out as its two row blocks; deferred only when both parameters take theirs)
         need_w = [i for i in range(n) if ctx.needs_input_grad[1 + n + i] or (dual and ctx.needs_input_grad[1 + 2 * n + i])]
         if need_w:
-            geoms = tuple((xs[i].shape[0], xs[i].shape[1], gys[i].shape[1], xs[i].shape[2], xs[i].shape[3]) for i in need_w)
-            ns = _wgrad_plan(geoms, k)
-            gws = []
-            if ns is not None:
-                m = len(need_w)
-                arr = (_lib.EasWgradProblem * m)()
-                wss = []
-                nbytes, fl = 0, 0.0
-                for q, i, s_ in zip(arr, need_w, ns):
-                    x, gy = xs[i], gys[i]
-                    ws = torch.empty(s_ * gy.shape[1] * x.shape[1] * k * k, dtype=torch.float32, device=x.device)
-                    wss.append(ws)
-                    q.x, q.grad_y, q.workspace = ptr(x), ptr(gy), ptr(ws)
-                    q.NI, q.Cin, q.Cout, q.Hi, q.Wi = x.shape[0], x.shape[1], gy.shape[1], x.shape[2], x.shape[3]
-                    nbytes += 4 * (x.numel() + gy.numel())
-                    fl += 2.0 * gy.numel() * x.shape[1] * k * k
-                defers = [(ops._can_defer(was[i]) and (not dual or (ctx.needs_input_grad[1 + n + i] and ctx.needs_input_grad[1 + 2 * n + i]
-                                                                    and ops._can_defer(wbs[i])))) for i in need_w]
-
-                def job(arr=arr, m=m, nbytes=nbytes, fl=fl):
-                    ops._call('eas_conv_wgrad', nbytes, _lib.lib().eas_conv_wgrad_group_partial, arr, m, k, 3, stream(), flops=fl, issue_flops=6 * fl)
-                ops._wgrad_launch(job, [xs[i] for i in need_w] + [gys[i] for i in need_w] + wss, all(defers), 6 * fl, nbytes)
-                for i, ws, s_, df in zip(need_w, wss, ns, defers):
-                    gw = torch.empty((gys[i].shape[1], xs[i].shape[1], k, k), dtype=torch.float32, device=ws.device)
-                    if dual:
-                        both = ctx.needs_input_grad[1 + n + i] and ctx.needs_input_grad[1 + 2 * n + i]
-                        ops._wgrad_finish(ws, gw, s_, df, (was[i], wbs[i]) if both else None, was[i].shape[0] if both else None)
-                    else:
-                        ops._wgrad_finish(ws, gw, s_, df, was[i])
-                    gws.append(gw)
-            else:       # a subset of the problems (some weights frozen) the group plan does not take: one by one
-                for i in need_w:
-                    if dual:
-                        both = ctx.needs_input_grad[1 + n + i] and ctx.needs_input_grad[1 + 2 * n + i]
-                        gws.append(ops.conv_wgrad(xs[i], gys[i], k, 1, 3, None, defer=both and ops._can_defer(was[i]) and ops._can_defer(wbs[i]),
-                                                  w=(was[i], wbs[i]) if both else None, split=was[i].shape[0] if both else None))
-                    else:
-                        gws.append(ops.conv_wgrad(xs[i], gys[i], k, 1, 3, None, defer=ops._can_defer(was[i]), w=was[i]))
-            for i, gw in zip(need_w, gws):
+            targets = []
+            for i in need_w:
+                if dual:
+                    both = ctx.needs_input_grad[1 + n + i] and ctx.needs_input_grad[1 + 2 * n + i]
+                    targets.append((both and ops._can_defer(was[i]) and ops._can_defer(wbs[i]), (was[i], wbs[i]) if both else None,
+                                    was[i].shape[0] if both else None))
+                else:
+                    targets.append((ops._can_defer(was[i]), was[i], None))
+            for i, gw in zip(need_w, _wgrad_group([xs[i] for i in need_w], [gys[i] for i in need_w], k, targets)):
                 if dual:
                     ca = was[i].shape[0]
                     out[n + i], out[2 * n + i] = gw[:ca], gw[ca:]
@@ -196,16 +191,7 @@ class _ConvGroupFn(torch.autograd.Function):
             b0 = (3 if dual else 2) * n
             need_b = [i for i in range(n) if ctx.needs_input_grad[1 + b0 + i]]
             if need_b:
-                m = len(need_b)
-                arr = (_lib.EasChannelSumProblem * m)()
-                gbs = []
-                for q, i in zip(arr, need_b):
-                    gy = gys[i]
-                    gb = torch.empty(gy.shape[1], dtype=torch.float32, device=gy.device)
-                    gbs.append(gb)
-                    q.g, q.out, q.N, q.C, q.HW = ptr(gy), ptr(gb), gy.shape[0], gy.shape[1], gy.shape[2] * gy.shape[3]
-                check(_lib.lib().eas_channel_sum_group(arr, m, stream()), 'eas_channel_sum_group')
-                for i, gb in zip(need_b, gbs):
+                for i, gb in zip(need_b, _bias_grad_group([gys[i] for i in need_b])):
                     out[b0 + i] = gb
         return (None,) + tuple(out)
 
@@ -247,17 +233,10 @@ def conv_group(xs, items, k, want_stats, owners=None):
     n = len(xs)
     dual = isinstance(items[0], tuple)
     has_bias = (items[0][0] if dual else items[0]).bias is not None
-    packs = []
-    for i, it in enumerate(items):
-        if dual:
-            d = None
-            if owners is not None and owners[i] is not None:
-                d = (getattr(owners[i][0], '_eas_dual_packs', None) or {}).get(owners[i][1])
-                if d is not None and (ops._PACK_SCOPE is None or d.get('gen') != ops._PACK_SCOPE):
-                    d = None
-            packs.append(d)
-        else:
-            packs.append(_pack_of(it, 0))
+    if dual:
+        packs = [ops.dual_packs_of(*ow) if ow is not None else None for ow in (owners or [None] * n)]
+    else:
+        packs = [ops.packs_of(it) for it in items]
     tensors = list(xs) + [(it[0] if dual else it).weight for it in items]
     if dual:
         tensors += [it[1].weight for it in items]
@@ -379,7 +358,7 @@ class _PredGroupFn(torch.autograd.Function):
         bs = tensors[5 * n:8 * n]
         xs = cf + rf + rf
         packs = cfg['packs']
-        pks = [packs[i][0] if packs[i] is not None and 0 in packs[i] else ops.conv_pack_weights(ws[i], 0) for i in range(3 * n)]
+        pks = [ops.pack_mode(packs[i], 0, ws[i]) for i in range(3 * n)]
         ys = [torch.empty((x.shape[0], w.shape[0], x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device) for x, w in zip(xs, ws)]
         _launch_conv_group(xs, pks, bs, ys, None, 1)
         ctx.save_for_backward(*cf, *rf, *ws)
@@ -413,44 +392,11 @@ class _PredGroupFn(torch.autograd.Function):
                     nbytes += 4 * (gx.numel() + gy_a.numel() + (gy_b.numel() if gy_b is not None else 0))
             ops._call('eas_conv_fwd', nbytes, _lib.lib().eas_pred_dgrad_group, arr, 2 * n, stream())
         else:
-            pk1 = [packs[i][1] if packs[i] is not None and 1 in packs[i] else ops.conv_pack_weights(ws[i], 1) for i in range(3 * n)]
+            pk1 = [ops.pack_mode(packs[i], 1, ws[i]) for i in range(3 * n)]
             _launch_conv_group(gys[:2 * n], pk1[:2 * n], None, gcf + grf, None, 1)
             _launch_conv_group(gys[2 * n:], pk1[2 * n:], None, grf, None, 1, accumulate=True)
-        geoms = tuple((x.shape[0], x.shape[1], g.shape[1], x.shape[2], x.shape[3]) for x, g in zip(xs, gys))
-        ns = _wgrad_plan(geoms, 1)
-        gws = []
-        if ns is not None:
-            m = 3 * n
-            arr = (_lib.EasWgradProblem * m)()
-            wss = []
-            nbytes, fl = 0, 0.0
-            for q, x, gy, s_ in zip(arr, xs, gys, ns):
-                wsb = torch.empty(s_ * gy.shape[1] * x.shape[1], dtype=torch.float32, device=x.device)
-                wss.append(wsb)
-                q.x, q.grad_y, q.workspace = ptr(x), ptr(gy), ptr(wsb)
-                q.NI, q.Cin, q.Cout, q.Hi, q.Wi = x.shape[0], x.shape[1], gy.shape[1], x.shape[2], x.shape[3]
-                nbytes += 4 * (x.numel() + gy.numel())
-                fl += 2.0 * gy.numel() * x.shape[1]
-            defers = [ops._can_defer(w) for w in ws]
-
-            def job(arr=arr, m=m, nbytes=nbytes, fl=fl):
-                ops._call('eas_conv_wgrad', nbytes, _lib.lib().eas_conv_wgrad_group_partial, arr, m, 1, 3, stream(), flops=fl, issue_flops=6 * fl)
-            ops._wgrad_launch(job, list(xs) + list(gys) + wss, all(defers), 6 * fl, nbytes)
-            for w, gy, x, wsb, s_, df in zip(ws, gys, xs, wss, ns, defers):
-                gw = torch.empty((gy.shape[1], x.shape[1], 1, 1), dtype=torch.float32, device=x.device)
-                ops._wgrad_finish(wsb, gw, s_, df, w)
-                gws.append(gw)
-        else:
-            for w, gy, x in zip(ws, gys, xs):
-                gws.append(ops.conv_wgrad(x, gy, 1, 1, 3, None, defer=ops._can_defer(w), w=w))
-        m = 3 * n
-        arr = (_lib.EasChannelSumProblem * m)()
-        gbs = []
-        for q, gy in zip(arr, gys):
-            gb = torch.empty(gy.shape[1], dtype=torch.float32, device=gy.device)
-            gbs.append(gb)
-            q.g, q.out, q.N, q.C, q.HW = ptr(gy), ptr(gb), gy.shape[0], gy.shape[1], gy.shape[2] * gy.shape[3]
-        check(_lib.lib().eas_channel_sum_group(arr, m, stream()), 'eas_channel_sum_group')
+        gws = _wgrad_group(xs, gys, 1, [(ops._can_defer(w), w, None) for w in ws])
+        gbs = _bias_grad_group(gys)
         return (None,) + tuple(gcf) + tuple(grf) + tuple(gws) + tuple(gbs)
 
 
@@ -476,8 +422,7 @@ def pred_group(cls_feats, reg_feats, cls_preds, reg_preds, obj_preds):
     """(cls_outs, reg_outs, obj_outs) of all levels from one launch (caller checked ``pred_group_ok``)"""
     n = len(cls_feats)
     convs = list(cls_preds) + list(reg_preds) + list(obj_preds)
-    packs = [_pack_of(c, 0) for c in convs]
-    cfg = dict(n=n, packs=packs)
+    cfg = dict(n=n, packs=[ops.packs_of(c) for c in convs])
     res = _PredGroupFn.apply(cfg, *cls_feats, *reg_feats, *[c.weight for c in convs], *[c.bias for c in convs])
     return list(res[:n]), list(res[n:2 * n]), list(res[2 * n:])
 
@@ -506,41 +451,16 @@ def conv_bn_act_eval_group(xs, items, norms, k, owners=None):
     nbytes, fl = 0, 0.0
     for i, (d, x, it, nm) in enumerate(zip(arr, xs, items, norms)):
         convs = it if isinstance(it, tuple) else (it,)
-        c0 = convs[0]
-        NI, Cin, H, W = x.shape
-        Cout = sum(c.out_channels for c in convs)
         if len(convs) == 2:
-            packs = None
-            if owners is not None and owners[i] is not None:
-                packs = (getattr(owners[i][0], '_eas_dual_packs', None) or {}).get(owners[i][1])
-                packs = ops.current_packs(packs)
-            pk = packs[0] if packs else ops.conv_pack_weights(torch.cat([convs[0].weight, convs[1].weight], 0), 0)
+            packs = ops.dual_packs_of(*owners[i]) if owners is not None and owners[i] is not None else None
+            pk = ops.pack_mode(packs, 0, (convs[0].weight, convs[1].weight))
         else:
-            pk = _pack_of(c0, 0)
-            pk = pk[0] if pk is not None else ops.conv_pack_weights(c0.weight, 0)
-        xd = ops._f32c(x)
-        keep += [pk, xd]
-        d.x, d.x_terms, d.packed_w = ptr(xd), 3, ptr(pk)
-        d.NI, d.Cin, d.Cout, d.Hi, d.Wi, d.ksize, d.stride = NI, Cin, Cout, H, W, k, 1
-        d.act = 1
-        d.csplit = convs[0].out_channels
-        outs = []
-        for j, bn in enumerate(nm):
-            r = d.range[j]
-            Cr = convs[j].out_channels if len(convs) > 1 else Cout
-            if torch.is_tensor(bn):              # a block folded by fuse_model: z = acc * 1 + bias
-                ones, zeros = ops._unit_affine(Cr, x.device)
-                r.gamma, r.beta, r.mean, r.invstd = ptr(ones), ptr(bn), ptr(zeros), ptr(ones)
-            else:
-                invstd = ops._eval_invstd(bn.running_var, bn.eps)
-                keep.append(invstd)
-                r.gamma, r.beta, r.mean, r.invstd = ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(invstd)
-            out = torch.empty((NI, Cr, H, W), dtype=torch.float32, device=x.device)
-            r.out, r.out_ctot, r.out_c0 = ptr(out), Cr, 0
-            outs.append(out)
+            pk = ops.pack_mode(ops.packs_of(convs[0]), 0, convs[0].weight)
+        outs = ops._fill_conv_bn_act_eval(d, x, convs, nm, pk, keep)
         results.append(outs if len(nm) > 1 else outs[0])
-        fl += 2.0 * NI * Cout * H * W * Cin * k * k
-        nbytes += 4 * NI * (Cin + Cout) * H * W
+        n_out = sum(o.numel() for o in outs)
+        fl += 2.0 * n_out * d.Cin * k * k
+        nbytes += 4 * (x.numel() + n_out)
     ops._call('eas_conv_fwd', nbytes, _lib.lib().eas_conv_bn_act_eval_group, arr, n, stream(), flops=fl, issue_flops=6 * fl)
     del keep
     return results
@@ -560,10 +480,7 @@ def pred_eval_ok(xs, convs):
 
 def conv_bias_group(xs, convs):
     """[conv_i(x_i) + bias_i] of plain 1x1 convolutions in one launch, no autograd (the prediction convolutions of the eval-mode head)"""
-    pks = []
-    for c in convs:
-        pk = _pack_of(c, 0)
-        pks.append(pk[0] if pk is not None else ops.conv_pack_weights(c.weight, 0))
+    pks = [ops.pack_mode(ops.packs_of(c), 0, c.weight) for c in convs]
     xs = [ops._f32c(x) for x in xs]
     ys = [torch.empty((x.shape[0], c.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device) for x, c in zip(xs, convs)]
     _launch_conv_group(xs, pks, [c.bias for c in convs], ys, None, 1)

@@ -28,7 +28,7 @@ for idx, (name, NI_, Cin, Cout, H, W, k, s, sp) in enumerate(shapes):
     pk = ops.conv_pack_weights(w, 0)
     x_sp = ops.to_planes(x) if (sp and Cin % 8 == 0) else None
     xt = 1 if sp else 3
-    if not ops.conv_fwd_supported(NI_, Cin, Cout, H, W, k, s, 2 if x_sp is not None else xt):
+    if not ops.conv_route(x.shape, Cout, k, s, 2 if x_sp is not None else xt).fwd:
         print(name, 'unsupported')
         continue
     for _ in range(2):
