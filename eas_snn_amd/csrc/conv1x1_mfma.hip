@@ -18,9 +18,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // loads of lanes without a pixel / channel groups past Cin read these zeros (stride 0) instead of being masked
 __device__ __attribute__((aligned(32))) float eas_c1_zero_page[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-// pixel blocks (grid.x) of the last launch / geometry query of this thread: the statistics partials per channel
-thread_local int tl_c1_blocks = 0;
-
 // C1GeomCore: what the plain tiles read (the grouped launch carries up to twelve by value); C1Geom adds the fused eval epilogues' descriptors
 struct C1GeomCore {
     int NI, Cin, Cout, HW;
@@ -42,6 +39,17 @@ struct C1Geom : C1GeomCore {
     EasBnActEpiDev bna;               // BatchNorm (running statistics) + activation in the plain epilogue (eas_conv_bn_act_eval); on = 0: plain store
 };
 
+// the tile geometry of a layer; the descriptors of the epilogues stay zero (off)
+C1GeomCore c1_geom(int NI, int Cin, int Cout, int HW) {
+    C1GeomCore g{};
+    g.NI = NI; g.Cin = Cin; g.Cout = Cout; g.HW = HW;
+    g.tiles_per_img = (HW + 31) / 32;
+    g.total_tiles = NI * g.tiles_per_img;
+    g.MT = (Cout + 31) / 32;
+    g.KSTEPS = (Cin + 15) / 16;
+    return g;
+}
+
 // statistics epilogue of the 1x1 kernels: 4 waves of a block = 4 pixel groups of the same WM * 32 channels
 template <int WM, int WN, typename ACC, typename G>
 __device__ __forceinline__ void c1_stats(const ACC (&acc)[WM][WN], const long (&yoff)[WN], double* red, const G& g, int mt0, int bx) {
@@ -55,14 +63,15 @@ __device__ __forceinline__ void c1_stats(const ACC (&acc)[WM][WN], const long (&
         eas_conv_stats_store(red, WM * 64, 4, (int)threadIdx.x, mt0 * 32 + (int)threadIdx.x, g.Cout, g.stats, g.stats_nb, bx);
 }
 
-template <int XT, typename TIN = float>
-__device__ __forceinline__ void to_terms(const TIN (&v)[8], bf16x8 (&b)[XT]) {
+// the exact bf16 terms of N fp32 values: XT = 1 for values that are bf16 already, else hi + mid + lo
+template <int XT, int N, typename V>
+__device__ __forceinline__ void to_terms(const V& v, __bf16 __attribute__((ext_vector_type(N))) (&b)[XT]) {
     if constexpr (XT == 1) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) b[0][j] = (__bf16)(float)v[j];
+        for (int j = 0; j < N; ++j) b[0][j] = (__bf16)(float)v[j];
     } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < N; ++j) {
             const __bf16 hi = (__bf16)v[j];
             const float r1 = v[j] - (float)hi;
             const __bf16 mid = (__bf16)r1;
@@ -74,25 +83,54 @@ __device__ __forceinline__ void to_terms(const TIN (&v)[8], bf16x8 (&b)[XT]) {
     }
 }
 
+// The exact product of A (three bf16 terms) and B (XT terms) as MFMAs on one accumulator, smallest partial products first.  This order
+// of additions PER ACCUMULATOR is what makes the kernel forms bit-identical to each other and must not change; the order in which
+// independent accumulators are issued is scheduling and is each caller's own.
+template <int XT>
+__device__ __forceinline__ void mma_term(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[XT], int q) {
+    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // XT == 1: (a2,b) (a1,b) (a0,b)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[XT == 1 ? 2 - q : PA[q]], b[XT == 1 ? 0 : PB[q]], acc, 0, 0, 0);
+}
+template <int XT>
+__device__ __forceinline__ void mma_terms(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[XT]) {
+#pragma unroll
+    for (int q = 0; q < (XT == 1 ? 3 : 6); ++q) mma_term<XT>(acc, a, b, q);
+}
+
+// what a lane holds of one pixel tile and k-step before the multiply: fp32, 8 channels; spike planes, the finished operand
+template <bool PL> struct c1_raw { typedef float type[8]; };
+template <> struct c1_raw<true> { typedef bf16x8 type; };
+
 // RAGK: Cin is not a multiple of 8 (the input gradient of the 1/4/num_classes-channel prediction convolutions, whose "input" is
 // grad_y): channel validity is then tested per channel instead of per 8-channel group.
 // PL: x is given as spike planes (bf16 [NI][Cin/8][HW][8], one exact term): a lane's 8 channels of its pixel are ONE 16-byte load and
 // already the MFMA operand -- no conversion, an eighth of the load instructions, half the bytes.
+// SHA: where the weight fragments (the A operand) come from.  false: every wave reads its own from global memory (L1 / L2).  true, for
+// layers with many input channels and few pixels (dark5: 256..1024 channels on 15 360 pixels): there the direct form is bound by the
+// texture path, not by HBM or the matrix cores: every wave fetches its own copy of the weight fragments (WM x 3 KB per k-step) -- 64 KB
+// per k-step and CU against 768 cycles of MFMA work.  So the four waves of a block (same output channels, different pixels) share them:
+// the block loads each k-step's WM x 3 fragments once (coalesced 16-byte loads), double-buffers them in LDS and every wave reads its
+// operands with conflict-free ds_read_b128.  One barrier per k-step.
 // bx / by: the block's pixel-block and channel-group index (blockIdx.x / .y of a launch of one problem; a grouped launch maps its
 // flat grid onto (problem, block) first -- conv1x1_group_kernel)
-template <int XT, int WM, int WN, bool RAGK, bool PL, int LM, typename G>
+template <int XT, int WM, int WN, bool RAGK, bool PL, int LM, bool SHA, typename G>
 __device__ __forceinline__ void c1_body(const float* __restrict__ x, const bf16x8* __restrict__ wp, const float* __restrict__ bias,
                                         float* __restrict__ y, const G& g, const int bx, const int by) {
     static_assert(!PL || (XT == 1 && !RAGK), "spike planes are one exact bf16 term in whole 8-channel groups");
+    static_assert(!SHA || !RAGK, "block-shared weight fragments: whole 8-channel groups");
     static_assert(LM == 0 || LM == 1 || LM == 3, "1x1: plain, time-major fused neuron epilogue, or BatchNorm + activation epilogue");
     constexpr bool TM = LM == 1;
-    typedef float TIN;
+    typedef typename c1_raw<PL>::type RAW;
     const bf16x8* xp = reinterpret_cast<const bf16x8*>(x);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int mt0 = by * WM;
     const int tile0 = (bx * 4 + wave) * (TM ? 1 : WN);
-    if (tile0 >= g.total_tiles && !g.stats) return;      // with statistics every wave reaches the block reduction (its lanes hold no pixel)
+    // A wave past the last tile leaves at once; with statistics every wave reaches the block reduction (its lanes hold no pixel).  The
+    // shared form must bring every wave to the barriers of its channel loop and has no such exit.
+    if constexpr (!SHA) {
+        if (tile0 >= g.total_tiles && !g.stats) return;
+    }
 
     // per-lane pixel of each N-tile
     long xoff[WN];    // element offset of (img, channel 8h, pixel) ; -1: no pixel
@@ -123,118 +161,145 @@ __device__ __forceinline__ void c1_body(const float* __restrict__ x, const bf16x
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
 
+    // the A operand.  Direct: ap[m] = this lane's piece of M-tile m's fragments.  Shared: staging piece q = it*256 + tid -> fragment
+    // f = q / 64 (= term * WM + m), lane q % 64, of the double-buffered LDS array -- which exists in the shared instances only (the
+    // direct ones must not pay its 6 KB x WM of LDS)
+    constexpr int NFRAG = WM * 3;                                    // 1 KB fragments per k-step
+    constexpr int NLD = SHA ? (NFRAG * 64 + 255) / 256 : 1;          // 16-byte staging loads per thread and k-step
     const size_t a_term = (size_t)g.MT * g.KSTEPS * 64;
-    const bf16x8* ap[WM];
+    const bf16x8* ap[SHA ? 1 : WM];
+    const bf16x8* asrc[NLD];
+    bf16x8 (*As)[NFRAG][64] = nullptr;
+    if constexpr (SHA) {
+        __shared__ bf16x8 a_lds[2][NFRAG][64];
+        As = a_lds;
 #pragma unroll
-    for (int m = 0; m < WM; ++m) {
-        const int mt = (mt0 + m) < g.MT ? (mt0 + m) : g.MT - 1;
-        ap[m] = wp + (size_t)mt * g.KSTEPS * 64 + lane;
-    }
-
-    if constexpr (PL) {
-        // planes: group 2 * ks + h of this lane's pixel per N-tile; lanes without a pixel / groups past Cin read the zero page
-        auto pfetch = [&](bf16x8 (&raw)[WN], int ks) {
-            const bool ch_ok = ks * 16 + 8 * h < g.Cin;
-#pragma unroll
-            for (int n = 0; n < WN; ++n) {
-                const bool ok = ch_ok && xoff[n] >= 0;
-                raw[n] = *(ok ? xp + xoff[n] + (long)ks * 2 * g.HW : reinterpret_cast<const bf16x8*>(eas_c1_zero_page));
-            }
-        };
-        auto pstep = [&](const bf16x8 (&raw)[WN], int ks) {
-            bf16x8 a[WM][3];
-#pragma unroll
-            for (int m = 0; m < WM; ++m)
-#pragma unroll
-                for (int t = 0; t < 3; ++t) a[m][t] = ap[m][t * a_term + (size_t)ks * 64];
-#pragma unroll
-            for (int n = 0; n < WN; ++n)
-#pragma unroll
-                for (int m = 0; m < WM; ++m) {
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], raw[n], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], raw[n], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], raw[n], acc[m][n], 0, 0, 0);
-                }
-        };
-        bf16x8 p0[WN], p1[WN];
-        pfetch(p0, 0);
-        int ks = 0;
-        for (; ks + 1 < g.KSTEPS; ks += 2) {
-            pfetch(p1, ks + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            pstep(p0, ks);
-            pfetch(p0, ks + 2 < g.KSTEPS ? ks + 2 : ks + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            pstep(p1, ks + 1);
+        for (int it = 0; it < NLD; ++it) {
+            int q = it * 256 + tid;
+            q = q < NFRAG * 64 ? q : NFRAG * 64 - 1;
+            const int f = q >> 6, t = f / WM, m = f - t * WM;
+            const int mt = (mt0 + m) < g.MT ? (mt0 + m) : g.MT - 1;
+            asrc[it] = wp + t * a_term + (size_t)mt * g.KSTEPS * 64 + (q & 63);
         }
-        if (ks < g.KSTEPS) pstep(p0, ks);
     } else {
-    // raw x of k-step ks: 8 channels (ks*16 + 8h + j) of this lane's pixel per N-tile.  Lanes without a pixel and channel
-    // groups past Cin (Cin % 8 == 0) read the zero page with stride 0: unconditional loads, no per-element masking
-    auto fetch = [&](TIN (&raw)[WN][8], int ks) {
+#pragma unroll
+        for (int m = 0; m < WM; ++m) {
+            const int mt = (mt0 + m) < g.MT ? (mt0 + m) : g.MT - 1;
+            ap[m] = wp + (size_t)mt * g.KSTEPS * 64 + lane;
+        }
+    }
+    // two register sets: the fragments of k-step s + 2 are requested while step s multiplies and are written to LDS a whole step later --
+    // with one set the commit waited for the load issued just before the step's few MFMAs (WM * WN * 3 or 6 of them: 200-800 cycles
+    // against an L2 / HBM round trip), i.e. every k-step of these many-channel, few-pixel layers ended in an exposed load latency
+    bf16x8 areg0[NLD], areg1[NLD];
+    auto a_fetch = [&](bf16x8 (&areg)[NLD], int ks) {
+        const int kc = ks < g.KSTEPS ? ks : g.KSTEPS - 1;
+#pragma unroll
+        for (int it = 0; it < NLD; ++it) areg[it] = asrc[it][(size_t)kc * 64];
+    };
+    auto a_commit = [&](const bf16x8 (&areg)[NLD], int buf) {
+#pragma unroll
+        for (int it = 0; it < NLD; ++it) {
+            const int q = it * 256 + tid;
+            if (q < NFRAG * 64) (&As[buf][0][0])[q] = areg[it];
+        }
+    };
+
+    // raw x of k-step ks per N-tile.  fp32: 8 channels (ks*16 + 8h + j) of this lane's pixel; planes: group 2 * ks + h of it.  Lanes
+    // without a pixel and channel groups past Cin (Cin % 8 == 0) read the zero page with stride 0: unconditional loads, no per-element masking
+    auto x_fetch = [&](RAW (&raw)[WN], int ks) {
         const int ch0 = ks * 16 + 8 * h;
         const bool ch_ok = ch0 < g.Cin;
-        const TIN* zero = reinterpret_cast<const TIN*>(eas_c1_zero_page);
 #pragma unroll
         for (int n = 0; n < WN; ++n) {
             const bool ok = ch_ok && xoff[n] >= 0;
-            const TIN* src = ok ? x + xoff[n] + (long)ks * 16 * g.HW : zero;
-            const long cs = ok ? (long)g.HW : 0;
-            if constexpr (RAGK) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) raw[n][j] = *((ok && ch0 + j < g.Cin) ? src + j * cs : zero);
+            if constexpr (PL) {
+                raw[n] = *(ok ? xp + xoff[n] + (long)ks * 2 * g.HW : reinterpret_cast<const bf16x8*>(eas_c1_zero_page));
             } else {
+                const float* src = ok ? x + xoff[n] + (long)ks * 16 * g.HW : eas_c1_zero_page;
+                const long cs = ok ? (long)g.HW : 0;
+                if constexpr (RAGK) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) raw[n][j] = src[j * cs];
+                    for (int j = 0; j < 8; ++j) raw[n][j] = *((ok && ch0 + j < g.Cin) ? src + j * cs : eas_c1_zero_page);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) raw[n][j] = src[j * cs];
+                }
             }
         }
     };
-    auto step = [&](TIN (&raw)[WN][8], int ks) {
+    auto operand = [&](const RAW& raw, bf16x8 (&b)[XT]) {
+        if constexpr (PL) {
+            b[0] = raw;
+        } else {
+            if constexpr (XT == 1) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bad |= __float_as_uint(raw[j]);       // exact in bf16 <=> low 16 pattern bits zero
+            }
+            to_terms<XT, 8>(raw, b);
+        }
+    };
+    // k-step ks, whose shared fragments are in LDS buffer buf.  Issue order of the independent accumulators -- direct: pixel tile
+    // outermost, the terms of one accumulator back to back; shared: term outermost, the accumulators innermost
+    auto step = [&](const RAW (&raw)[WN], int ks, int buf) {
         bf16x8 a[WM][3];
 #pragma unroll
         for (int m = 0; m < WM; ++m)
 #pragma unroll
-            for (int t = 0; t < 3; ++t) a[m][t] = ap[m][t * a_term + (size_t)ks * 64];
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            bf16x8 b[XT];
-            if constexpr (XT == 1 && !PL) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) bad |= __float_as_uint(raw[n][j]);       // exact in bf16 <=> low 16 pattern bits zero
+            for (int t = 0; t < 3; ++t) {
+                if constexpr (SHA) a[m][t] = As[buf][t * WM + m][lane];
+                else a[m][t] = ap[m][t * a_term + (size_t)ks * 64];
             }
-            to_terms<XT, TIN>(raw[n], b);
+        if constexpr (SHA) {
+            bf16x8 b[WN][XT];
 #pragma unroll
-            for (int m = 0; m < WM; ++m) {
-                if constexpr (XT == 1) {
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b[0], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b[0], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[0], acc[m][n], 0, 0, 0);
-                } else {
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b[0], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[2], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b[1], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b[0], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[1], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[0], acc[m][n], 0, 0, 0);
-                }
+            for (int n = 0; n < WN; ++n) operand(raw[n], b[n]);
+#pragma unroll
+            for (int q = 0; q < (XT == 1 ? 3 : 6); ++q)
+#pragma unroll
+                for (int m = 0; m < WM; ++m)
+#pragma unroll
+                    for (int n = 0; n < WN; ++n) mma_term<XT>(acc[m][n], a[m], b[n], q);
+        } else {
+#pragma unroll
+            for (int n = 0; n < WN; ++n) {
+                bf16x8 b[XT];
+                operand(raw[n], b);
+#pragma unroll
+                for (int m = 0; m < WM; ++m) mma_terms<XT>(acc[m][n], a[m], b);
             }
         }
     };
 
     // channel loop, two raw buffers: the loads of k-step s+1 are in flight while k-step s is converted and multiplied
-    TIN r0[WN][8], r1[WN][8];
-    fetch(r0, 0);
+    RAW r0[WN], r1[WN];
+    if constexpr (SHA) a_fetch(areg0, 0);
+    x_fetch(r0, 0);
+    if constexpr (SHA) {
+        a_commit(areg0, 0);
+        a_fetch(areg1, 1);
+        __syncthreads();
+    }
     int ks = 0;
     for (; ks + 1 < g.KSTEPS; ks += 2) {
-        fetch(r1, ks + 1);
+        if constexpr (SHA) a_fetch(areg0, ks + 2);
+        x_fetch(r1, ks + 1);
         __builtin_amdgcn_sched_barrier(0);
-        step(r0, ks);
-        fetch(r0, ks + 2 < g.KSTEPS ? ks + 2 : ks + 1);
+        step(r0, ks, 0);
+        if constexpr (SHA) {
+            a_commit(areg1, 1);                          // step ks + 1 (requested a whole step ago)
+            __syncthreads();
+            a_fetch(areg1, ks + 3);
+        }
+        x_fetch(r0, ks + 2 < g.KSTEPS ? ks + 2 : ks + 1);
         __builtin_amdgcn_sched_barrier(0);
-        step(r1, ks + 1);
+        step(r1, ks + 1, 1);
+        if constexpr (SHA) {
+            a_commit(areg0, 0);                          // step ks + 2
+            __syncthreads();
+        }
     }
-    if (ks < g.KSTEPS) step(r0, ks);
-    }
+    if (ks < g.KSTEPS) step(r0, ks, 0);
 
     if constexpr (XT == 1 && !PL) {
         if (g.inexact && (bad & 0xffffu)) atomicOr(g.inexact, 1);      // a tensor tagged "spikes / small integers" was not
@@ -279,7 +344,9 @@ __device__ __forceinline__ void c1_body(const float* __restrict__ x, const bf16x
         for (int n = 0; n < WN; ++n) {
             if (yoff[n] < 0) continue;
             float* yp = y + yoff[n] + (long)co0 * g.HW;
-            if (g.accum) {        // block-uniform: y += (the second reader of a tensor adds its input gradient to the first one's)
+            // block-uniform: y += (the second reader of a tensor adds its input gradient to the first one's).  Only eas_conv1x1_group sets
+            // accum, and it launches the direct form only: the shared instances do not carry the read-modify-write path
+            if (!SHA && g.accum) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
                     if (full || co0 + (e & 3) + 8 * (e >> 2) < g.Cout) yp[(long)((e & 3) + 8 * (e >> 2)) * g.HW] += acc[m][n][e] + bv[e];
@@ -304,7 +371,14 @@ __device__ __forceinline__ void c1_body(const float* __restrict__ x, const bf16x
 template <int XT, int WM, int WN, bool RAGK = false, bool PL = false, int LM = 0>
 __global__ __launch_bounds__(256, 2) void conv1x1_mfma_kernel(const float* __restrict__ x, const bf16x8* __restrict__ wp,
                                                               const float* __restrict__ bias, float* __restrict__ y, C1Geom g) {
-    c1_body<XT, WM, WN, RAGK, PL, LM, C1Geom>(x, wp, bias, y, g, (int)blockIdx.x, (int)blockIdx.y);
+    c1_body<XT, WM, WN, RAGK, PL, LM, false, C1Geom>(x, wp, bias, y, g, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// the form with block-shared weight fragments (c1_body SHA)
+template <int XT, int WM, int WN, bool PL = false, int LM = 0>
+__global__ __launch_bounds__(256, 2) void conv1x1_mfma_sharedA_kernel(const float* __restrict__ x, const bf16x8* __restrict__ wp,
+                                                                      const float* __restrict__ bias, float* __restrict__ y, C1Geom g) {
+    c1_body<XT, WM, WN, false, PL, LM, true, C1Geom>(x, wp, bias, y, g, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // Grouped launch (include/eas_hip.h eas_conv_fwd_group, ksize 1): problem p owns pixel blocks [first[p], first[p + 1]) of grid.x
@@ -328,304 +402,58 @@ __global__ __launch_bounds__(256, 2) void conv1x1_group_kernel(const C1GroupArgs
         if ((int)blockIdx.x >= a.first[i]) p = i;
     p = __builtin_amdgcn_readfirstlane(p);
     if ((int)blockIdx.y * WM >= a.g[p].MT) return;        // grid.y covers the widest problem
-    c1_body<XT, WM, WN, RAGK, false, LM, G>(a.x[p], a.wp[p], a.bias[p], a.y[p], a.g[p], (int)blockIdx.x - a.first[p], (int)blockIdx.y);
+    c1_body<XT, WM, WN, RAGK, false, LM, false, G>(a.x[p], a.wp[p], a.bias[p], a.y[p], a.g[p], (int)blockIdx.x - a.first[p], (int)blockIdx.y);
 }
 
-// Variant for layers with many input channels and few pixels (dark5: 256..1024 channels on 15 360 pixels).  There the direct
-// kernel is bound by the texture path, not by HBM or the matrix cores: every wave fetches its own copy of the weight fragments
-// (WM x 3 KB per k-step) -- 64 KB per k-step and CU against 768 cycles of MFMA work.  Here the four waves of a block (same
-// output channels, different pixels) share them: the block loads each k-step's WM x 3 fragments once (coalesced 16-byte
-// loads), double-buffers them in LDS and every wave reads its operands with conflict-free ds_read_b128.  One barrier per k-step.
-template <int XT, int WM, int WN, bool PL = false, int LM = 0>
-__global__ __launch_bounds__(256, 2) void conv1x1_mfma_sharedA_kernel(const float* __restrict__ x, const bf16x8* __restrict__ wp,
-                                                                      const float* __restrict__ bias, float* __restrict__ y, C1Geom g) {
-    static_assert(!PL || XT == 1, "spike planes are one exact bf16 term");
-    static_assert(LM == 0 || LM == 1 || LM == 3, "1x1: plain, time-major fused neuron epilogue, or BatchNorm + activation epilogue");
-    constexpr bool TM = LM == 1;
-    typedef float TIN;
-    const bf16x8* xp = reinterpret_cast<const bf16x8*>(x);
-    constexpr int NFRAG = WM * 3;                        // 1 KB fragments per k-step
-    constexpr int NLD = (NFRAG * 64 + 255) / 256;        // 16-byte staging loads per thread and k-step
-    __shared__ bf16x8 As[2][NFRAG][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int mt0 = blockIdx.y * WM;
-    const int tile0 = (blockIdx.x * 4 + wave) * (TM ? 1 : WN);
+// one launch of one layer.  y == NULL (and no fused neuron epilogue, which writes through g.lif): geometry query
+struct C1Args {
+    const float* x;
+    const bf16x8* wp;
+    const float* bias;
+    float* y;
+    C1Geom g;
+    hipStream_t st;
+    bool query;
+};
 
-    long xoff[WN], yoff[WN];
-    int l_img[LM == 1 ? WN : 1], l_pix[LM == 1 ? WN : 1];
-    bool l_ok[LM == 1 ? WN : 1];
-#pragma unroll
-    for (int n = 0; n < WN; ++n) {
-        const int t = TM ? tile0 : tile0 + n;             // time-major: tile n = time step n of the same spatial tile
-        const int smp = t / g.tiles_per_img, p = (t - smp * g.tiles_per_img) * 32 + r;
-        const int img = TM ? n * g.NI + smp : smp;
-        const bool ok = t < g.total_tiles && p < g.HW;
-        xoff[n] = ok ? (PL ? ((long)img * (g.Cin / 8) + h) * g.HW + p : ((long)img * g.Cin + 8 * h) * g.HW + p) : -1;
-        yoff[n] = ok ? (long)img * g.Cout * g.HW + p : -1;
-        if constexpr (LM == 1) {
-            l_img[n] = smp;
-            l_pix[n] = p;
-            l_ok[n] = ok;
-        }
-    }
-    f32x16 acc[WM][WN];
-    unsigned bad = 0;
-#pragma unroll
-    for (int m = 0; m < WM; ++m)
-#pragma unroll
-        for (int n = 0; n < WN; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
-
-    // staging piece q = it*256 + tid -> fragment f = q / 64 (= term * WM + m), lane q % 64
-    const size_t a_term = (size_t)g.MT * g.KSTEPS * 64;
-    const bf16x8* asrc[NLD];
-#pragma unroll
-    for (int it = 0; it < NLD; ++it) {
-        int q = it * 256 + tid;
-        q = q < NFRAG * 64 ? q : NFRAG * 64 - 1;
-        const int f = q >> 6, t = f / WM, m = f - t * WM;
-        const int mt = (mt0 + m) < g.MT ? (mt0 + m) : g.MT - 1;
-        asrc[it] = wp + t * a_term + (size_t)mt * g.KSTEPS * 64 + (q & 63);
-    }
-    // two register sets: the fragments of k-step s + 2 are requested while step s multiplies and are written to LDS a whole step later --
-    // with one set the commit waited for the load issued just before the step's few MFMAs (WM * WN * 3 or 6 of them: 200-800 cycles
-    // against an L2 / HBM round trip), i.e. every k-step of these many-channel, few-pixel layers ended in an exposed load latency
-    bf16x8 areg0[NLD], areg1[NLD];
-    auto a_fetch = [&](bf16x8 (&areg)[NLD], int ks) {
-        const int kc = ks < g.KSTEPS ? ks : g.KSTEPS - 1;
-#pragma unroll
-        for (int it = 0; it < NLD; ++it) areg[it] = asrc[it][(size_t)kc * 64];
-    };
-    auto a_commit = [&](const bf16x8 (&areg)[NLD], int buf) {
-#pragma unroll
-        for (int it = 0; it < NLD; ++it) {
-            const int q = it * 256 + tid;
-            if (q < NFRAG * 64) (&As[buf][0][0])[q] = areg[it];
-        }
-    };
-    auto x_fetch = [&](TIN (&raw)[WN][8], int ks) {
-        const bool ch_ok = ks * 16 + 8 * h < g.Cin;
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            const bool ok = ch_ok && xoff[n] >= 0;
-            const TIN* src = ok ? x + xoff[n] + (long)ks * 16 * g.HW : reinterpret_cast<const TIN*>(eas_c1_zero_page);
-            const long cs = ok ? (long)g.HW : 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) raw[n][j] = src[j * cs];
-        }
-    };
-    auto step = [&](TIN (&raw)[WN][8], int buf) {
-        bf16x8 a[WM][3];
-#pragma unroll
-        for (int m = 0; m < WM; ++m)
-#pragma unroll
-            for (int t = 0; t < 3; ++t) a[m][t] = As[buf][t * WM + m][lane];
-        bf16x8 b[WN][XT];
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            if constexpr (XT == 1 && !PL) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) bad |= __float_as_uint(raw[n][j]);       // exact in bf16 <=> low 16 pattern bits zero
-            }
-            to_terms<XT, TIN>(raw[n], b[n]);
-        }
-        if constexpr (XT == 1) {
-#pragma unroll
-            for (int ta = 2; ta >= 0; --ta)
-#pragma unroll
-                for (int m = 0; m < WM; ++m)
-#pragma unroll
-                    for (int n = 0; n < WN; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][ta], b[n][0], acc[m][n], 0, 0, 0);
-        } else {
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int m = 0; m < WM; ++m)
-#pragma unroll
-                    for (int n = 0; n < WN; ++n)
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][PA[q]], b[n][PB[q]], acc[m][n], 0, 0, 0);
-        }
-    };
-
-    if constexpr (PL) {
-        auto p_fetch = [&](bf16x8 (&raw)[WN], int ks) {
-            const bool ch_ok = ks * 16 + 8 * h < g.Cin;
-#pragma unroll
-            for (int n = 0; n < WN; ++n) {
-                const bool ok = ch_ok && xoff[n] >= 0;
-                raw[n] = *(ok ? xp + xoff[n] + (long)ks * 2 * g.HW : reinterpret_cast<const bf16x8*>(eas_c1_zero_page));
-            }
-        };
-        auto p_step = [&](const bf16x8 (&raw)[WN], int buf) {
-            bf16x8 a[WM][3];
-#pragma unroll
-            for (int m = 0; m < WM; ++m)
-#pragma unroll
-                for (int t = 0; t < 3; ++t) a[m][t] = As[buf][t * WM + m][lane];
-#pragma unroll
-            for (int ta = 2; ta >= 0; --ta)
-#pragma unroll
-                for (int m = 0; m < WM; ++m)
-#pragma unroll
-                    for (int n = 0; n < WN; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][ta], raw[n], acc[m][n], 0, 0, 0);
-        };
-        bf16x8 q0[WN], q1[WN];
-        a_fetch(areg0, 0);
-        p_fetch(q0, 0);
-        a_commit(areg0, 0);
-        a_fetch(areg1, 1);
-        __syncthreads();
-        int ks = 0;
-        for (; ks + 1 < g.KSTEPS; ks += 2) {
-            a_fetch(areg0, ks + 2);
-            p_fetch(q1, ks + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            p_step(q0, 0);
-            a_commit(areg1, 1);                          // step ks + 1 (requested a whole step ago)
-            __syncthreads();
-            const int kn = ks + 2 < g.KSTEPS ? ks + 2 : ks + 1;
-            a_fetch(areg1, ks + 3);
-            p_fetch(q0, kn);
-            __builtin_amdgcn_sched_barrier(0);
-            p_step(q1, 1);
-            a_commit(areg0, 0);                          // step ks + 2
-            __syncthreads();
-        }
-        if (ks < g.KSTEPS) p_step(q0, 0);
-    } else {
-    TIN r0[WN][8], r1[WN][8];
-    a_fetch(areg0, 0);
-    x_fetch(r0, 0);
-    a_commit(areg0, 0);
-    a_fetch(areg1, 1);
-    __syncthreads();
-    int ks = 0;
-    for (; ks + 1 < g.KSTEPS; ks += 2) {
-        a_fetch(areg0, ks + 2);
-        x_fetch(r1, ks + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        step(r0, 0);
-        a_commit(areg1, 1);                              // step ks + 1 (requested a whole step ago)
-        __syncthreads();
-        const int kn = ks + 2 < g.KSTEPS ? ks + 2 : ks + 1;
-        a_fetch(areg1, ks + 3);
-        x_fetch(r0, kn);
-        __builtin_amdgcn_sched_barrier(0);
-        step(r1, 1);
-        a_commit(areg0, 0);                              // step ks + 2
-        __syncthreads();
-    }
-    if (ks < g.KSTEPS) step(r0, 0);
-    }
-
-    if constexpr (XT == 1 && !PL) {
-        if (g.inexact && (bad & 0xffffu)) atomicOr(g.inexact, 1);      // a tensor tagged "spikes / small integers" was not
-    }
-
-    if (g.stats) {
-        __shared__ __align__(16) double red[4 * WM * 64 + 2 * EAS_STATS_SCRATCH];      // [wave][WM * 32][2] doubles, then the waves' float patches
-        c1_stats<WM, WN>(acc, yoff, red, g, mt0, (int)blockIdx.x);
-    }
-
-    if constexpr (LM == 1) {
-#pragma unroll
-        for (int m = 0; m < WM; ++m)
-            if (mt0 + m < g.MT) eas_lif_epilogue<WN, LM>(acc[m], g.lif, mt0 + m, h, l_img, l_pix, l_ok);
-        return;
-    }
-
-    if constexpr (LM == 3) {      // BatchNorm (running statistics) + activation on the accumulators (eas_conv_bn_act_eval)
-#pragma unroll
-        for (int m = 0; m < WM; ++m)
-            if (mt0 + m < g.MT) eas_bnact_epilogue<WN>(acc[m], g.bna, mt0 + m, h, yoff, (long)g.HW);
-        return;
-    }
-#pragma unroll
-    for (int m = 0; m < WM; ++m) {
-        if (mt0 + m >= g.MT) continue;
-        const int co0 = (mt0 + m) * 32 + 4 * h;
-        const bool full = (mt0 + m) * 32 + 32 <= g.Cout;
-        float bv[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) bv[e] = 0.0f;
-        if (bias) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int co = co0 + (e & 3) + 8 * (e >> 2);
-                bv[e] = co < g.Cout ? bias[co] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            if (yoff[n] < 0) continue;
-            float* yp = y + yoff[n] + (long)co0 * g.HW;
-            if (g.act) {          // block-uniform: the activation's transcendental never runs for the plain convolution
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (full || co0 + (e & 3) + 8 * (e >> 2) < g.Cout) yp[(long)((e & 3) + 8 * (e >> 2)) * g.HW] = eas_epi_silu(acc[m][n][e] + bv[e]);
-            } else if (full) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) yp[(long)((e & 3) + 8 * (e >> 2)) * g.HW] = acc[m][n][e] + bv[e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (co0 + (e & 3) + 8 * (e >> 2) < g.Cout) yp[(long)((e & 3) + 8 * (e >> 2)) * g.HW] = acc[m][n][e] + bv[e];
-            }
-        }
-    }
+// launches the instance (or only sizes its grid: query) and returns the pixel blocks (grid.x) -- the statistics partials per channel -- or
+// an error code (< 0).  A block's four waves hold WN pixel tiles each; time-major (LM = 1) they are four SPATIAL tiles, each wave all
+// T = WN time steps of its tile
+template <bool SHA, int XT, int WM, int WN, bool RAGK, bool PL, int LM>
+int launch_c1(const C1Args& a) {
+    constexpr int TPB = 4 * (LM == 1 ? 1 : WN);
+    const dim3 grid((a.g.total_tiles + TPB - 1) / TPB, (a.g.MT + WM - 1) / WM);
+    if (a.query) return (int)grid.x;
+    if (a.g.stats && (int)grid.x != a.g.stats_nb) return EAS_ERR_INVALID_ARG;
+    if constexpr (SHA) EAS_LAUNCH((conv1x1_mfma_sharedA_kernel<XT, WM, WN, PL, LM>), grid, dim3(256), 0, a.st, a.x, a.wp, a.bias, a.y, a.g);
+    else EAS_LAUNCH((conv1x1_mfma_kernel<XT, WM, WN, RAGK, PL, LM>), grid, dim3(256), 0, a.st, a.x, a.wp, a.bias, a.y, a.g);
+    return (int)grid.x;
 }
 
-template <int XT, int WM, int WN, bool PL = false, int LM = 0>
-int launch_c1_shared(const float* x, const bf16x8* wp, const float* bias, float* y, C1Geom g, hipStream_t st) {
-    dim3 grid((g.total_tiles + 4 * WN - 1) / (4 * WN), (g.MT + WM - 1) / WM);
-    tl_c1_blocks = (int)grid.x;
-    if (!y) return EAS_OK;            // geometry query
-    if (g.stats && (int)grid.x != g.stats_nb) return EAS_ERR_INVALID_ARG;
-    EAS_LAUNCH((conv1x1_mfma_sharedA_kernel<XT, WM, WN, PL, LM>), grid, dim3(256), 0, st, x, wp, bias, y, g);
-    return EAS_OK;
+// wave tile (wm, wn) -> kernel instance, once per kernel form; the plain (LM = 0) and the BatchNorm-epilogue (LM = 3) paths share them
+template <int XT, bool RAGK, bool PL, int LM>
+int launch_c1_direct(int wm, int wn, const C1Args& a) {
+    if constexpr (!RAGK) {      // ragged input channels: one pixel tile per wave only
+        if (wm == 4 && wn == 2) return launch_c1<false, XT, 4, 2, false, PL, LM>(a);
+        if (wm == 2 && wn == 2) return launch_c1<false, XT, 2, 2, false, PL, LM>(a);
+        if (wm == 1 && wn == 2) return launch_c1<false, XT, 1, 2, false, PL, LM>(a);
+    }
+    if (wm == 4) return launch_c1<false, XT, 4, 1, RAGK, PL, LM>(a);
+    if (wm == 2) return launch_c1<false, XT, 2, 1, RAGK, PL, LM>(a);
+    return launch_c1<false, XT, 1, 1, RAGK, PL, LM>(a);
+}
+template <int XT, bool PL, int LM>
+int launch_c1_shared(int sm, int sn, const C1Args& a) {
+    if (sm == 4 && sn == 2) return launch_c1<true, XT, 4, 2, false, PL, LM>(a);
+    if (sm == 4) return launch_c1<true, XT, 4, 1, false, PL, LM>(a);
+    if (sn == 2) return launch_c1<true, XT, 2, 2, false, PL, LM>(a);
+    return launch_c1<true, XT, 2, 1, false, PL, LM>(a);
 }
 
-template <int XT, int WM, int WN, bool RAGK = false, bool PL = false, int LM = 0>
-int launch_c1(const float* x, const bf16x8* wp, const float* bias, float* y, C1Geom g, hipStream_t st) {
-    dim3 grid((g.total_tiles + 4 * WN - 1) / (4 * WN), (g.MT + WM - 1) / WM);
-    tl_c1_blocks = (int)grid.x;
-    if (!y) return EAS_OK;            // geometry query
-    if (g.stats && (int)grid.x != g.stats_nb) return EAS_ERR_INVALID_ARG;
-    EAS_LAUNCH((conv1x1_mfma_kernel<XT, WM, WN, RAGK, PL, LM>), grid, dim3(256), 0, st, x, wp, bias, y, g);
-    return EAS_OK;
-}
-
-// fused eval step on spike planes, time-major: a block's four waves = four SPATIAL 32-pixel tiles, each wave all T = WN time steps of its tile
-template <int WM, int WN, bool SHARED>
-int launch_c1_lif(const float* x, const bf16x8* wp, C1Geom g, hipStream_t st, bool query) {
-    if (query) return EAS_OK;
-    dim3 grid((g.total_tiles + 3) / 4, (g.MT + WM - 1) / WM);
-    if constexpr (SHARED) EAS_LAUNCH((conv1x1_mfma_sharedA_kernel<1, WM, WN, true, 1>), grid, dim3(256), 0, st, x, wp, (const float*)nullptr, (float*)nullptr, g);
-    else EAS_LAUNCH((conv1x1_mfma_kernel<1, WM, WN, false, true, 1>), grid, dim3(256), 0, st, x, wp, (const float*)nullptr, (float*)nullptr, g);
-    return EAS_OK;
-}
-
-}  // namespace
-
-// wave-tile choice and launch for a 1x1 convolution; PL: x is a spike-plane tensor (x_terms 1)
+// wave-tile choice and launch for a 1x1 convolution; PL: x is a spike-plane tensor (x_terms 1).  Returns launch_c1's
 template <bool PL>
-static int conv1x1_dispatch_t(const float* x, const void* packed_w, const float* bias, float* y, int NI, int Cin, int Cout, int HW, int x_terms,
-                              hipStream_t st, double* stats = nullptr, int stats_nb = 0, int* inexact = nullptr, int act = 0,
-                              const EasBnActEpiDev* bna = nullptr) {
-    C1Geom g{};
-    g.stats = stats; g.stats_nb = stats_nb;
-    g.inexact = inexact;
-    g.act = act;
-    if (bna) g.bna = *bna;
-    g.NI = NI; g.Cin = Cin; g.Cout = Cout; g.HW = HW;
-    g.tiles_per_img = (HW + 31) / 32;
-    g.total_tiles = NI * g.tiles_per_img;
-    g.MT = (Cout + 31) / 32;
-    g.KSTEPS = (Cin + 15) / 16;
-    const bf16x8* wp = (const bf16x8*)packed_w;
+int conv1x1_dispatch_t(const C1Args& a, int x_terms, bool bna) {
+    const C1Geom& g = a.g;
     // wave tile = WM channel tiles x WN pixel tiles.  Large layers: all output channels in one wave when they fit (x is then read
     // once per 128 output channels), 2 pixel tiles per wave.  Layers with few pixels and many channels (dark5: 15 360 pixels, up
     // to 1024 -> 512 channels) would leave most CUs with one 4-wave block or none: shrink the wave tile until the grid has at
@@ -635,20 +463,16 @@ static int conv1x1_dispatch_t(const float* x, const void* packed_w, const float*
     static const long want = eas_dev_env("EAS_C1_BLOCKS") ? atol(eas_dev_env("EAS_C1_BLOCKS")) : 512;
     if (blocks(wm, wn) < want) wn = 1;
     while (blocks(wm, wn) < want && wm > 1) wm >>= 1;
-    if (bna && (PL || x_terms != 3 || Cin % 8 != 0)) return EAS_ERR_UNSUPPORTED;     // the BatchNorm + activation epilogue: real-valued fp32 inputs
+    if (bna && (PL || x_terms != 3 || g.Cin % 8 != 0)) return EAS_ERR_UNSUPPORTED;     // the BatchNorm + activation epilogue: real-valued fp32 inputs
     if constexpr (PL) {
-        if (Cin % 8 != 0 || x_terms != 1) return EAS_ERR_UNSUPPORTED;
-    } else if (Cin % 8 != 0) {     // ragged input channels: the direct kernel with per-channel validity (few channels: one pixel tile per wave)
-        if (x_terms == 1) {
-            if (g.MT >= 4) return launch_c1<1, 4, 1, true>(x, wp, bias, y, g, st);
-            return g.MT >= 2 ? launch_c1<1, 2, 1, true>(x, wp, bias, y, g, st) : launch_c1<1, 1, 1, true>(x, wp, bias, y, g, st);
-        }
-        if (g.MT >= 4) return launch_c1<3, 4, 1, true>(x, wp, bias, y, g, st);
-        return g.MT >= 2 ? launch_c1<3, 2, 1, true>(x, wp, bias, y, g, st) : launch_c1<3, 1, 1, true>(x, wp, bias, y, g, st);
+        if (g.Cin % 8 != 0 || x_terms != 1) return EAS_ERR_UNSUPPORTED;
+    } else if (g.Cin % 8 != 0) {     // ragged input channels: the direct kernel with per-channel validity (few channels: one pixel tile per wave)
+        const int rm = g.MT >= 4 ? 4 : (g.MT >= 2 ? 2 : 1);
+        return x_terms == 1 ? launch_c1_direct<1, true, false, 0>(rm, 1, a) : launch_c1_direct<3, true, false, 0>(rm, 1, a);
     }
     // many input channels (>= 256): weight-fragment traffic, not HBM, bounds the direct kernel -> block-shared fragments
     static const int shared_min = eas_dev_env("EAS_C1_SHARED_MIN_CIN") ? atoi(eas_dev_env("EAS_C1_SHARED_MIN_CIN")) : 256;
-    if (Cin >= shared_min && g.MT >= 4) {
+    if (g.Cin >= shared_min && g.MT >= 4) {
         // wave tile of the shared form: shrink it while the grid has fewer than ~2 blocks per CU
         int sm = 4, sn = 2;
         static const char* force = eas_dev_env("EAS_C1_SHARED_SHAPE");     // development: "42", "41", "22", "21"
@@ -658,82 +482,53 @@ static int conv1x1_dispatch_t(const float* x, const void* packed_w, const float*
             if (blocks(sm, sn) < want_s) sn = 1;
             if (blocks(sm, sn) < want_s) sm = 2;
         }
-#define EAS_C1S(XT_)                                                                                \
-    do {                                                                                            \
-        if (sm == 4 && sn == 2) return launch_c1_shared<XT_, 4, 2, PL>(x, wp, bias, y, g, st);      \
-        if (sm == 4) return launch_c1_shared<XT_, 4, 1, PL>(x, wp, bias, y, g, st);                 \
-        if (sn == 2) return launch_c1_shared<XT_, 2, 2, PL>(x, wp, bias, y, g, st);                 \
-        return launch_c1_shared<XT_, 2, 1, PL>(x, wp, bias, y, g, st);                              \
-    } while (0)
         if constexpr (!PL) {
-            if (bna) {
-                if (sm == 4 && sn == 2) return launch_c1_shared<3, 4, 2, false, 3>(x, wp, bias, y, g, st);
-                if (sm == 4) return launch_c1_shared<3, 4, 1, false, 3>(x, wp, bias, y, g, st);
-                if (sn == 2) return launch_c1_shared<3, 2, 2, false, 3>(x, wp, bias, y, g, st);
-                return launch_c1_shared<3, 2, 1, false, 3>(x, wp, bias, y, g, st);
-            }
+            if (bna) return launch_c1_shared<3, false, 3>(sm, sn, a);
         }
-        if (x_terms == 1) EAS_C1S(1);
-        if constexpr (!PL) EAS_C1S(3);
-#undef EAS_C1S
+        if (x_terms == 1) return launch_c1_shared<1, PL, 0>(sm, sn, a);
+        if constexpr (!PL) return launch_c1_shared<3, false, 0>(sm, sn, a);
     }
-#define EAS_C1(XT_)                                                                                 \
-    do {                                                                                            \
-        if (wm == 4 && wn == 2) return launch_c1<XT_, 4, 2, false, PL>(x, wp, bias, y, g, st);      \
-        if (wm == 2 && wn == 2) return launch_c1<XT_, 2, 2, false, PL>(x, wp, bias, y, g, st);      \
-        if (wm == 1 && wn == 2) return launch_c1<XT_, 1, 2, false, PL>(x, wp, bias, y, g, st);      \
-        if (wm == 4) return launch_c1<XT_, 4, 1, false, PL>(x, wp, bias, y, g, st);                 \
-        if (wm == 2) return launch_c1<XT_, 2, 1, false, PL>(x, wp, bias, y, g, st);                 \
-        return launch_c1<XT_, 1, 1, false, PL>(x, wp, bias, y, g, st);                              \
-    } while (0)
     if constexpr (!PL) {
-        if (bna) {
-            if (wm == 4 && wn == 2) return launch_c1<3, 4, 2, false, false, 3>(x, wp, bias, y, g, st);
-            if (wm == 2 && wn == 2) return launch_c1<3, 2, 2, false, false, 3>(x, wp, bias, y, g, st);
-            if (wm == 1 && wn == 2) return launch_c1<3, 1, 2, false, false, 3>(x, wp, bias, y, g, st);
-            if (wm == 4) return launch_c1<3, 4, 1, false, false, 3>(x, wp, bias, y, g, st);
-            if (wm == 2) return launch_c1<3, 2, 1, false, false, 3>(x, wp, bias, y, g, st);
-            return launch_c1<3, 1, 1, false, false, 3>(x, wp, bias, y, g, st);
-        }
+        if (bna) return launch_c1_direct<3, false, false, 3>(wm, wn, a);
     }
-    if (x_terms == 1) EAS_C1(1);
-    if constexpr (!PL) EAS_C1(3);
-#undef EAS_C1
+    if (x_terms == 1) return launch_c1_direct<1, false, PL, 0>(wm, wn, a);
+    if constexpr (!PL) return launch_c1_direct<3, false, false, 0>(wm, wn, a);
     return EAS_ERR_UNSUPPORTED;
 }
+
+}  // namespace
 
 // called by eas_conv_fwd (conv_mfma.hip) for ksize == 1, stride == 1; planes != 0: x is a spike-plane tensor
 int eas_conv1x1_dispatch(const float* x, const void* packed_w, const float* bias, float* y, int NI, int Cin, int Cout, int HW, int x_terms,
                          hipStream_t st, double* stats, int stats_nb, int* nb_out, int planes, int* inexact, int act, const void* bna) {
-    tl_c1_blocks = 0;
-    const EasBnActEpiDev* b = (const EasBnActEpiDev*)bna;
-    const int rc = planes ? conv1x1_dispatch_t<true>(x, packed_w, bias, y, NI, Cin, Cout, HW, 1, st, stats, stats_nb, nullptr, act, b)
-                          : conv1x1_dispatch_t<false>(x, packed_w, bias, y, NI, Cin, Cout, HW, x_terms, st, stats, stats_nb, inexact, act, b);
-    if (nb_out) *nb_out = tl_c1_blocks;
-    return rc;
+    C1Args a{x, (const bf16x8*)packed_w, bias, y, {}, st, !y};
+    static_cast<C1GeomCore&>(a.g) = c1_geom(NI, Cin, Cout, HW);
+    a.g.stats = stats; a.g.stats_nb = stats_nb;
+    a.g.inexact = planes ? nullptr : inexact;
+    a.g.act = act;
+    if (bna) a.g.bna = *(const EasBnActEpiDev*)bna;
+    const int nb = planes ? conv1x1_dispatch_t<true>(a, 1, bna != nullptr) : conv1x1_dispatch_t<false>(a, x_terms, bna != nullptr);
+    if (nb_out) *nb_out = nb < 0 ? 0 : nb;
+    return nb < 0 ? nb : EAS_OK;
 }
 
 // 1x1 layer of the fused eval step (eas_conv_bn_lif_eval, conv_mfma.hip): spike planes in, distinct frames per step, T = 3 or 5
 int eas_conv1x1_lif_dispatch(const void* x, const void* packed_w, const EasLifEpiDev& lif, int Cin, int x_terms, int x_shared, hipStream_t st, bool query) {
     if (x_terms != 2 || x_shared || Cin % 8 != 0 || (lif.T != 3 && lif.T != 5)) return EAS_ERR_UNSUPPORTED;
-    C1Geom g{};
-    g.NI = lif.N; g.Cin = Cin; g.Cout = lif.Cout; g.HW = lif.HW;
-    g.tiles_per_img = (lif.HW + 31) / 32;
-    g.total_tiles = lif.N * g.tiles_per_img;            // spatial tiles
-    g.MT = (lif.Cout + 31) / 32;
-    g.KSTEPS = (Cin + 15) / 16;
+    C1Args a{(const float*)x, (const bf16x8*)packed_w, nullptr, nullptr, {}, st, query};
+    C1Geom& g = a.g;
+    static_cast<C1GeomCore&>(g) = c1_geom(lif.N, Cin, lif.Cout, lif.HW);      // total_tiles: spatial tiles
     g.lif = lif;
-    const bf16x8* wp = (const bf16x8*)packed_w;
-    const float* xf = (const float*)x;
     auto blocks = [&](int m) { return (long)((g.total_tiles + 3) / 4) * ((g.MT + m - 1) / m); };
     // channel tiles per wave: two (T = 3: 6 accumulator tiles, T = 5: 10; four M-tiles x 3 steps spill) while the grid keeps ~2 blocks per CU
     int wm = g.MT >= 2 ? 2 : 1;
     while (wm > 1 && blocks(wm) < 512) wm >>= 1;
     static const int shared_min = eas_dev_env("EAS_C1_SHARED_MIN_CIN") ? atoi(eas_dev_env("EAS_C1_SHARED_MIN_CIN")) : 256;
-    if (Cin >= shared_min && g.MT >= 2 && wm >= 2)
-        return lif.T == 3 ? launch_c1_lif<2, 3, true>(xf, wp, g, st, query) : launch_c1_lif<2, 5, true>(xf, wp, g, st, query);
-    if (lif.T == 3) return wm == 2 ? launch_c1_lif<2, 3, false>(xf, wp, g, st, query) : launch_c1_lif<1, 3, false>(xf, wp, g, st, query);
-    return wm == 2 ? launch_c1_lif<2, 5, false>(xf, wp, g, st, query) : launch_c1_lif<1, 5, false>(xf, wp, g, st, query);
+    int nb;
+    if (Cin >= shared_min && g.MT >= 2 && wm >= 2) nb = lif.T == 3 ? launch_c1<true, 1, 2, 3, false, true, 1>(a) : launch_c1<true, 1, 2, 5, false, true, 1>(a);
+    else if (lif.T == 3) nb = wm == 2 ? launch_c1<false, 1, 2, 3, false, true, 1>(a) : launch_c1<false, 1, 1, 3, false, true, 1>(a);
+    else nb = wm == 2 ? launch_c1<false, 1, 2, 5, false, true, 1>(a) : launch_c1<false, 1, 1, 5, false, true, 1>(a);
+    return nb < 0 ? nb : EAS_OK;
 }
 
 // Grouped 1x1 launch (eas_conv_fwd_group, conv_group.hip): one wave-tile shape for all problems -- channel tiles per wave from the
@@ -741,24 +536,19 @@ int eas_conv1x1_lif_dispatch(const void* x, const void* packed_w, const EasLifEp
 // (the ~2 blocks per CU rule of the single launch).  The direct kernel only (the block-shared weight fragments of the >= 256-channel
 // layers are a different block shape; in a group those layers are the small riders).
 namespace {
-template <int XT, int WM, int WN, bool RAGK>
-int launch_c1_group(const C1GroupArgs& a, int grid_y, hipStream_t st) {
-    EAS_LAUNCH((conv1x1_group_kernel<XT, WM, WN, RAGK>), dim3(a.first[a.n], grid_y), dim3(256), 0, st, a);
-    return EAS_OK;
-}
-// the same launch with the BatchNorm / activation epilogue (grouped eas_conv_bn_act_eval)
-template <int WM, int WN>
-int launch_c1_group_bna(const C1GroupArgs& a, const EasBnActEpiDev* bna, const int* order, int grid_y, hipStream_t st) {
-    C1GroupArgsT<C1GeomBna> b{};
-    for (int i = 0; i < a.n; ++i) {
-        static_cast<C1GeomCore&>(b.g[i]) = a.g[i];
-        b.g[i].bna = bna[order[i]];
-        b.x[i] = a.x[i]; b.wp[i] = a.wp[i]; b.bias[i] = nullptr; b.y[i] = a.y[i];
+// instantiated shapes: (4,2) (4,1) (2,1) (1,1); ragged input channels: (4,1) (1,1).  LM = 3, G = C1GeomBna: the BatchNorm / activation
+// epilogue (grouped eas_conv_bn_act_eval)
+template <bool RAGK, int LM, typename G>
+int launch_c1_group(int wm, int wn, const C1GroupArgsT<G>& a, int grid_y, hipStream_t st) {
+    auto go = [&](auto kern) {
+        EAS_LAUNCH(kern, dim3(a.first[a.n], grid_y), dim3(256), 0, st, a);
+        return EAS_OK;
+    };
+    if constexpr (!RAGK) {
+        if (wm == 4 && wn == 2) return go(conv1x1_group_kernel<3, 4, 2, false, LM, G>);
+        if (wm == 2) return go(conv1x1_group_kernel<3, 2, 1, false, LM, G>);
     }
-    for (int i = 0; i <= a.n; ++i) b.first[i] = a.first[i];
-    b.n = a.n;
-    EAS_LAUNCH((conv1x1_group_kernel<3, WM, WN, false, 3, C1GeomBna>), dim3(b.first[b.n], grid_y), dim3(256), 0, st, b);
-    return EAS_OK;
+    return wm == 4 ? go(conv1x1_group_kernel<3, 4, 1, RAGK, LM, G>) : go(conv1x1_group_kernel<3, 1, 1, RAGK, LM, G>);
 }
 }  // namespace
 
@@ -771,11 +561,7 @@ int eas_conv1x1_group(const EasConvProblem* pr, int n, int x_terms, hipStream_t 
     for (int p = 0; p < n; ++p) {
         C1GeomCore& g = a.g[p];
         const EasConvProblem& q = pr[p];
-        g.NI = q.NI; g.Cin = q.Cin; g.Cout = q.Cout; g.HW = q.Hi * q.Wi;
-        g.tiles_per_img = (g.HW + 31) / 32;
-        g.total_tiles = q.NI * g.tiles_per_img;
-        g.MT = (q.Cout + 31) / 32;
-        g.KSTEPS = (q.Cin + 15) / 16;
+        g = c1_geom(q.NI, q.Cin, q.Cout, q.Hi * q.Wi);
         g.stats = q.stats;
         g.accum = q.accumulate ? 1 : 0;
         if (q.stats && q.accumulate) return EAS_ERR_INVALID_ARG;
@@ -792,7 +578,7 @@ int eas_conv1x1_group(const EasConvProblem* pr, int n, int x_terms, hipStream_t 
     int wm = mt_min >= 4 ? 4 : (mt_min >= 2 ? 2 : 1), wn = ragk ? 1 : 2;
     if (blocks(wm, wn) < 512) wn = 1;
     while (blocks(wm, wn) < 512 && wm > 1) wm >>= 1;
-    if (wm == 2 && wn == 2) wn = 1;          // instantiated shapes: (4,2) (4,1) (2,1) (1,1); ragged input channels: (4,1) (1,1)
+    if (wm == 2 && wn == 2) wn = 1;          // to the instantiated shapes (launch_c1_group)
     if (wm == 1) wn = 1;
     if (ragk && wm == 2) wm = 1;
     // Grid order: the problems with the longest channel loops first.  Blocks start in blockIdx order and a block's duration goes with its
@@ -815,17 +601,19 @@ int eas_conv1x1_group(const EasConvProblem* pr, int n, int x_terms, hipStream_t 
     }
     b.first[n] = bx;
     b.n = n;
-    a = b;
     if (query) return EAS_OK;
     const int gy = (mt_max + wm - 1) / wm;
-    if (bna) {
-        if (ragk) return EAS_ERR_UNSUPPORTED;
-        if (wm == 4) return wn == 2 ? launch_c1_group_bna<4, 2>(a, bna, order, gy, st) : launch_c1_group_bna<4, 1>(a, bna, order, gy, st);
-        return wm == 2 ? launch_c1_group_bna<2, 1>(a, bna, order, gy, st) : launch_c1_group_bna<1, 1>(a, bna, order, gy, st);
+    if (!bna) return ragk ? launch_c1_group<true, 0>(wm, wn, b, gy, st) : launch_c1_group<false, 0>(wm, wn, b, gy, st);
+    if (ragk) return EAS_ERR_UNSUPPORTED;
+    C1GroupArgsT<C1GeomBna> c{};
+    for (int i = 0; i < n; ++i) {
+        static_cast<C1GeomCore&>(c.g[i]) = b.g[i];
+        c.g[i].bna = bna[order[i]];
+        c.x[i] = b.x[i]; c.wp[i] = b.wp[i]; c.bias[i] = nullptr; c.y[i] = b.y[i];
     }
-    if (ragk) return wm == 4 ? launch_c1_group<3, 4, 1, true>(a, gy, st) : launch_c1_group<3, 1, 1, true>(a, gy, st);
-    if (wm == 4) return wn == 2 ? launch_c1_group<3, 4, 2, false>(a, gy, st) : launch_c1_group<3, 4, 1, false>(a, gy, st);
-    return wm == 2 ? launch_c1_group<3, 2, 1, false>(a, gy, st) : launch_c1_group<3, 1, 1, false>(a, gy, st);
+    for (int i = 0; i <= n; ++i) c.first[i] = b.first[i];
+    c.n = n;
+    return launch_c1_group<false, 3>(wm, wn, c, gy, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -859,6 +647,19 @@ __device__ __forceinline__ bf16x8 w1_tr_frag(const unsigned char* p0, const unsi
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
+// LDS image of one chunk buffer of conv1x1_wgrad_body (an instance has two): three terms of grad_y, then XT of x
+struct W1Lds {
+    int pitch;       // bytes per channel row and term
+    int a_term, b_term;
+    int buf;
+};
+constexpr W1Lds w1_lds(int XT, int WVM, int WVN, int NT, int KS, bool XPL) {
+    const int KC = 16 * KS, pitch = KC * 2 + 16;
+    const int a_term = 32 * WVM * pitch;
+    const int b_term = XPL ? WVN * NT * KC * 64 : 32 * WVN * NT * pitch;      // planes: [32-channel plane][KC pixels][64 B]
+    return {pitch, a_term, b_term, 3 * a_term + XT * b_term};
+}
+
 // bx / by: the block's pixel slice (and slab) and its (co, ci) block -- blockIdx.x / .y of a launch of one layer, or what the grouped
 // launch (conv1x1_wgrad_group_kernel) derives from its flat grid
 template <int XT, int WVM, int WVN, int NT, int KS, bool XPL>
@@ -868,11 +669,9 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const void* __restrict__ x_, 
     const float* x = reinterpret_cast<const float*>(x_);
     const bf16x8* xp = reinterpret_cast<const bf16x8*>(x_);
     constexpr int KC = 16 * KS;                 // pixels per chunk
-    constexpr int PITCH = KC * 2 + 16;          // bytes per channel row and term
     constexpr int RA = 32 * WVM, RB = 32 * WVN * NT;
-    constexpr int A_TERM = RA * PITCH;
-    constexpr int B_TERM = XPL ? (RB / 32) * KC * 64 : RB * PITCH;      // planes: [32-channel plane][KC pixels][64 B]
-    constexpr int BUF = 3 * A_TERM + XT * B_TERM;
+    constexpr W1Lds LDS = w1_lds(XT, WVM, WVN, NT, KS, XPL);
+    constexpr int PITCH = LDS.pitch, A_TERM = LDS.a_term, B_TERM = LDS.b_term, BUF = LDS.buf;
     constexpr int V4R = KC / 4;                 // float4 loads per channel row and chunk
     constexpr int ITEMS_A = RA * V4R;
     constexpr int ITEMS_B = XPL ? (RB / 8) * KC : RB * V4R;             // planes: (8-channel group, pixel) pairs of 16 bytes
@@ -945,25 +744,16 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const void* __restrict__ x_, 
                 *(f32x4*)(buf + it_lofs[it]) = L[it];           // the 8 channels of a pixel, as they are
                 continue;
             }
-            bf16x4 t0, t1, t2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float v = L[it][j];
-                const __bf16 hi = (__bf16)v;
-                const float r1 = v - (float)hi;
-                const __bf16 mid = (__bf16)r1;
-                t0[j] = hi;
-                t1[j] = mid;
-                t2[j] = (__bf16)(r1 - (float)mid);
-            }
+            bf16x4 t[3];
+            to_terms<3, 4>(L[it], t);
             unsigned char* dst = buf + it_lofs[it];
-            *(bf16x4*)dst = t0;
+            *(bf16x4*)dst = t[0];
             if (it_isa[it]) {
-                *(bf16x4*)(dst + A_TERM) = t1;
-                *(bf16x4*)(dst + 2 * A_TERM) = t2;
+                *(bf16x4*)(dst + A_TERM) = t[1];
+                *(bf16x4*)(dst + 2 * A_TERM) = t[2];
             } else if (XT == 3) {
-                *(bf16x4*)(dst + B_TERM) = t1;
-                *(bf16x4*)(dst + 2 * B_TERM) = t2;
+                *(bf16x4*)(dst + B_TERM) = t[1];
+                *(bf16x4*)(dst + 2 * B_TERM) = t[2];
             }
         }
     };
@@ -1002,18 +792,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const void* __restrict__ x_, 
 #pragma unroll
                     for (int t = 0; t < XT; ++t) b[t] = *(const bf16x8*)(cur + b_frag + n * 32 * PITCH + t * B_TERM + ks * 32);
                 }
-                if constexpr (XT == 1) {
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[n], 0, 0, 0);
-                } else {
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[n], 0, 0, 0);
-                }
+                mma_terms<XT>(acc[n], a, b);
             }
         }
         if (more) commit(smem + (par ^ 1) * BUF);
@@ -1069,46 +848,72 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_group_kernel(const W1GroupA
     else conv1x1_wgrad_body<XT, WVM, WVN, NT, 1, false>(a.x[p], a.gy[p], a.slabs[p], a.g[p], smem, bx, by);
 }
 
-struct W1Plan { int wvm, wvn, nt, ks, slices; };
+// block shape: all four waves busy whatever Cout is
+struct W1Shape { int wvm, wvn, nt; };
+W1Shape w1_shape(int Cout) {
+    if (Cout > 64) return {4, 1, 4};
+    if (Cout > 32) return {2, 2, 2};
+    return {1, 4, 1};
+}
 
-// blocks of a kernel instance a CU holds at once (registers, waves and its dynamic LDS), cached per instance
-template <int XT, int WVM, int WVN, int NT, int KS, bool XPL>
-int resident_w1() {
+struct W1Plan { W1Shape sh; int ks, slices; };
+
+// First call per kernel instance: raises its dynamic-LDS limit and asks how many of its blocks a CU holds at once (registers, waves and
+// lds bytes), cached.  0: the limit could not be raised, the instance cannot be launched
+template <auto KERN>
+int w1_resident(size_t lds) {
     static int nb = 0;
     if (nb > 0) return nb;
-    auto kern = conv1x1_wgrad_lds_kernel<XT, WVM, WVN, NT, KS, XPL>;
-    constexpr int PITCH = 16 * KS * 2 + 16;
-    constexpr int B_TERM = XPL ? WVN * NT * 16 * KS * 64 : 32 * WVN * NT * PITCH;
-    const size_t lds = (size_t)2 * (3 * 32 * WVM * PITCH + XT * B_TERM);
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 0;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kern, 256, lds) != hipSuccess || n < 1) n = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)KERN, 256, lds) != hipSuccess || n < 1) n = 2;
     nb = n;
     return nb;
 }
 
-// block shape: all four waves busy whatever Cout is.  Pixel slices: every block walks per_slice chunks and the launch takes
-// ceil(slices * yz / slots) rounds of the chip's block slots (256 CUs x the blocks of the kernel instance a CU really holds); the slice
-// count with the fewest chunk periods wins, ties go to fewer slabs (the old rule aimed at 512 blocks whatever the instance: 540 blocks on
-// 512 slots are two rounds)
+struct W1Call {
+    const void* x;
+    const float* gy;
+    float* slabs;
+    W1Geom g;
+    int slices;
+    hipStream_t st;
+};
+
+// one instance of the single-layer kernel: its resident blocks per CU (c == NULL, for the plan; 2 when unknown) or its launch
+template <int XT, int WVM, int WVN, int NT, int KS, bool XPL>
+int w1_instance(const W1Call* c) {
+    constexpr auto kern = conv1x1_wgrad_lds_kernel<XT, WVM, WVN, NT, KS, XPL>;
+    constexpr size_t lds = (size_t)2 * w1_lds(XT, WVM, WVN, NT, KS, XPL).buf;
+    const int res = w1_resident<kern>(lds);
+    if (!c) return res > 0 ? res : 2;
+    if (res == 0) return EAS_ERR_LAUNCH;
+    dim3 grid(c->slices, ((c->g.Cout + 32 * WVM - 1) / (32 * WVM)) * c->g.ci_blocks);
+    EAS_LAUNCH(kern, grid, dim3(256), lds, c->st, c->x, c->gy, c->slabs, c->g);
+    return EAS_OK;
+}
+int w1_select(const W1Shape& sh, int ks, int x_terms, bool planes, const W1Call* c) {
+#define EAS_W1(XT_, M_, N_, T_, PL_) (ks == 2 ? w1_instance<XT_, M_, N_, T_, 2, PL_>(c) : w1_instance<XT_, M_, N_, T_, 1, PL_>(c))
+#define EAS_W1_SHAPE(XT_, PL_) (sh.wvm == 4 ? EAS_W1(XT_, 4, 1, 4, PL_) : (sh.wvm == 2 ? EAS_W1(XT_, 2, 2, 2, PL_) : EAS_W1(XT_, 1, 4, 1, PL_)))
+    if (planes) return EAS_W1_SHAPE(1, true);
+    return x_terms == 1 ? EAS_W1_SHAPE(1, false) : EAS_W1_SHAPE(3, false);
+#undef EAS_W1_SHAPE
+#undef EAS_W1
+}
+
+// Pixel slices: every block walks per_slice chunks and the launch takes ceil(slices * yz / slots) rounds of the chip's block slots
+// (256 CUs x the blocks of the kernel instance a CU really holds); the slice count with the fewest chunk periods wins, ties go to
+// fewer slabs (the old rule aimed at 512 blocks whatever the instance: 540 blocks on 512 slots are two rounds)
 W1Plan w1_plan(W1Geom& g, int NI, int Cin, int Cout, int HW, int x_terms, bool planes) {
     W1Plan p;
-    if (Cout > 64) { p.wvm = 4; p.wvn = 1; p.nt = 4; }
-    else if (Cout > 32) { p.wvm = 2; p.wvn = 2; p.nt = 2; }
-    else { p.wvm = 1; p.wvn = 4; p.nt = 1; }
+    p.sh = w1_shape(Cout);
     p.ks = HW % 32 == 0 ? 2 : 1;
     g.NI = NI; g.Cin = Cin; g.Cout = Cout; g.HW = HW;
-    const int RA = 32 * p.wvm, RB = 32 * p.wvn * p.nt;
+    const int RA = 32 * p.sh.wvm, RB = 32 * p.sh.wvn * p.sh.nt;
     g.ci_blocks = (Cin + RB - 1) / RB;
     const int yz = ((Cout + RA - 1) / RA) * g.ci_blocks;
     const int total_chunks = NI * (HW / (16 * p.ks));
-    int res = 2;
-#define EAS_W1R(XT_, M_, N_, T_, PL_) (p.ks == 2 ? resident_w1<XT_, M_, N_, T_, 2, PL_>() : resident_w1<XT_, M_, N_, T_, 1, PL_>())
-#define EAS_W1R_SHAPE(XT_, PL_) (p.wvm == 4 ? EAS_W1R(XT_, 4, 1, 4, PL_) : (p.wvm == 2 ? EAS_W1R(XT_, 2, 2, 2, PL_) : EAS_W1R(XT_, 1, 4, 1, PL_)))
-    if (planes) res = EAS_W1R_SHAPE(1, true);
-    else res = x_terms == 1 ? EAS_W1R_SHAPE(1, false) : EAS_W1R_SHAPE(3, false);
-#undef EAS_W1R_SHAPE
-#undef EAS_W1R
+    const int res = w1_select(p.sh, p.ks, x_terms, planes, nullptr);
     static const int force = eas_dev_env("EAS_W1_BLOCKS") ? atoi(eas_dev_env("EAS_W1_BLOCKS")) : 0;      // development: the old rule with this target
     int best = 1;
     if (force > 0) {
@@ -1129,20 +934,21 @@ W1Plan w1_plan(W1Geom& g, int NI, int Cin, int Cout, int HW, int x_terms, bool p
     return p;
 }
 
-template <int XT, int WVM, int WVN, int NT, int KS, bool XPL = false>
-int launch_w1_lds(const void* x, const float* gy, float* slabs, W1Geom g, int slices, hipStream_t st) {
-    auto kern = conv1x1_wgrad_lds_kernel<XT, WVM, WVN, NT, KS, XPL>;
-    constexpr int PITCH = 16 * KS * 2 + 16;
-    constexpr int B_TERM = XPL ? WVN * NT * 16 * KS * 64 : 32 * WVN * NT * PITCH;
-    const size_t lds = (size_t)2 * (3 * 32 * WVM * PITCH + XT * B_TERM);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
-        attr_set = true;
-    }
-    dim3 grid(slices, ((g.Cout + 32 * WVM - 1) / (32 * WVM)) * g.ci_blocks);
-    EAS_LAUNCH(kern, grid, dim3(256), lds, st, x, gy, slabs, g);
+// the grouped kernel of a block shape: its resident blocks per CU (res_out != NULL) or its launch.  Its LDS is sized for the 32-pixel
+// chunks (KS = 2); the 16-pixel bodies use less
+template <int WVM, int WVN, int NT>
+int w1_group_instance(const W1GroupArgs& a, int blocks, hipStream_t st, int* res_out) {
+    constexpr auto kern = conv1x1_wgrad_group_kernel<3, WVM, WVN, NT>;
+    constexpr size_t lds = (size_t)2 * w1_lds(3, WVM, WVN, NT, 2, false).buf;
+    const int res = w1_resident<kern>(lds);
+    if (res == 0) return EAS_ERR_LAUNCH;
+    if (res_out) { *res_out = res; return EAS_OK; }
+    EAS_LAUNCH(kern, dim3(blocks), dim3(256), lds, st, a);
     return EAS_OK;
+}
+int w1_group_select(const W1Shape& sh, const W1GroupArgs& a, int blocks, hipStream_t st, int* res_out) {
+    if (sh.wvm == 4) return w1_group_instance<4, 1, 4>(a, blocks, st, res_out);
+    return sh.wvm == 2 ? w1_group_instance<2, 2, 2>(a, blocks, st, res_out) : w1_group_instance<1, 4, 1>(a, blocks, st, res_out);
 }
 
 }  // namespace
@@ -1157,52 +963,27 @@ int eas_conv1x1_wgrad_slices(int NI, int Cin, int Cout, int HW, int x_terms, int
 // planes != 0: x is a spike-plane tensor (one term)
 int eas_conv1x1_wgrad_dispatch(const void* x, const float* gy, float* slabs, int NI, int Cin, int Cout, int HW, int x_terms, hipStream_t st,
                                int planes) {
-    W1Geom g{};
+    W1Call c{x, gy, slabs, {}, 0, st};
     if (HW % 16 != 0 || (planes && Cin % 8 != 0)) return EAS_ERR_UNSUPPORTED;
-    const W1Plan p = w1_plan(g, NI, Cin, Cout, HW, x_terms, planes != 0);
-#define EAS_W1(XT_, M_, N_, T_, PL_) (p.ks == 2 ? launch_w1_lds<XT_, M_, N_, T_, 2, PL_>(x, gy, slabs, g, p.slices, st) : launch_w1_lds<XT_, M_, N_, T_, 1, PL_>(x, gy, slabs, g, p.slices, st))
-#define EAS_W1_SHAPE(XT_, PL_) (p.wvm == 4 ? EAS_W1(XT_, 4, 1, 4, PL_) : (p.wvm == 2 ? EAS_W1(XT_, 2, 2, 2, PL_) : EAS_W1(XT_, 1, 4, 1, PL_)))
-    if (planes) return EAS_W1_SHAPE(1, true);
-    return x_terms == 1 ? EAS_W1_SHAPE(1, false) : EAS_W1_SHAPE(3, false);
-#undef EAS_W1_SHAPE
-#undef EAS_W1
+    const W1Plan p = w1_plan(c.g, NI, Cin, Cout, HW, x_terms, planes != 0);
+    c.slices = p.slices;
+    return w1_select(p.sh, p.ks, x_terms, planes != 0, &c);
 }
 
 // the slab kernels of several 1x1 layers as one grid: one block shape (all layers on the same side of the 32 / 64 output-channel
 // bounds), a common number of 16-pixel chunks per block (see group_tau in conv_wgrad_mfma.hip: same rule)
-namespace {
-template <int WVM, int WVN, int NT>
-int launch_w1_group(const W1GroupArgs& a, int blocks, hipStream_t st, int* res_out) {
-    auto kern = conv1x1_wgrad_group_kernel<3, WVM, WVN, NT>;
-    constexpr int PITCH = 16 * 2 * 2 + 16;            // sized for the 32-pixel chunks (KS = 2); the 16-pixel bodies use less
-    const size_t lds = (size_t)2 * (3 * 32 * WVM * PITCH + 3 * 32 * WVN * NT * PITCH);
-    static int res = 0;
-    if (res == 0) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, lds) != hipSuccess || nb < 1) nb = 2;
-        res = nb;
-    }
-    if (res_out) { *res_out = res; return EAS_OK; }
-    EAS_LAUNCH(kern, dim3(blocks), dim3(256), lds, st, a);
-    return EAS_OK;
-}
-}  // namespace
-
 int eas_conv1x1_wgrad_group(const EasWgradProblem* pr, int n, int x_terms, hipStream_t st, int* slabs_out, bool query) {
     if (n > kMaxW1Group || x_terms != 3) return EAS_ERR_UNSUPPORTED;
     W1GroupArgs a{};
     int yz[kMaxW1Group], nc[kMaxW1Group];
-    const int cls0 = pr[0].Cout > 64 ? 2 : (pr[0].Cout > 32 ? 1 : 0);
-    const int wvm = cls0 == 2 ? 4 : (cls0 == 1 ? 2 : 1), wvn = cls0 == 2 ? 1 : (cls0 == 1 ? 2 : 4), nt = cls0 == 2 ? 4 : (cls0 == 1 ? 2 : 1);
-    const int RA = 32 * wvm, RB = 32 * wvn * nt;
+    const W1Shape sh = w1_shape(pr[0].Cout);
+    const int RA = 32 * sh.wvm, RB = 32 * sh.wvn * sh.nt;
     for (int p = 0; p < n; ++p) {
         const EasWgradProblem& q = pr[p];
         if (q.NI <= 0 || q.Cin <= 0 || q.Cout <= 0 || q.Hi <= 0 || q.Wi <= 0) return EAS_ERR_INVALID_ARG;
         if (!query && (!q.x || !q.grad_y || !q.workspace)) return EAS_ERR_INVALID_ARG;
         const int HW = q.Hi * q.Wi;
-        const int cls = q.Cout > 64 ? 2 : (q.Cout > 32 ? 1 : 0);
-        if (HW % 16 != 0 || cls != cls0) return EAS_ERR_UNSUPPORTED;
+        if (HW % 16 != 0 || w1_shape(q.Cout).wvm != sh.wvm) return EAS_ERR_UNSUPPORTED;
         W1Geom& g = a.g[p];
         g.NI = q.NI; g.Cin = q.Cin; g.Cout = q.Cout; g.HW = HW;
         g.ci_blocks = (q.Cin + RB - 1) / RB;
@@ -1212,7 +993,7 @@ int eas_conv1x1_wgrad_group(const EasWgradProblem* pr, int n, int x_terms, hipSt
         a.x[p] = q.x; a.gy[p] = q.grad_y; a.slabs[p] = q.workspace;
     }
     int res = 2;
-    int rc = cls0 == 2 ? launch_w1_group<4, 1, 4>(a, 0, st, &res) : (cls0 == 1 ? launch_w1_group<2, 2, 2>(a, 0, st, &res) : launch_w1_group<1, 4, 1>(a, 0, st, &res));
+    const int rc = w1_group_select(sh, a, 0, st, &res);
     if (rc != EAS_OK) return rc;
     // common chunks per block (the rule of group_tau, conv_wgrad_mfma.hip)
     static const int slot_pct_g = eas_dev_env("EAS_WG_SLOT_PCT") ? atoi(eas_dev_env("EAS_WG_SLOT_PCT")) : 100;      // development
@@ -1239,5 +1020,5 @@ int eas_conv1x1_wgrad_group(const EasWgradProblem* pr, int n, int x_terms, hipSt
     a.first[n] = blocks;
     a.n = n;
     if (query) return EAS_OK;
-    return cls0 == 2 ? launch_w1_group<4, 1, 4>(a, blocks, st, nullptr) : (cls0 == 1 ? launch_w1_group<2, 2, 2>(a, blocks, st, nullptr) : launch_w1_group<1, 4, 1>(a, blocks, st, nullptr));
+    return w1_group_select(sh, a, blocks, st, nullptr);
 }
