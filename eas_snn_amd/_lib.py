@@ -203,6 +203,14 @@ PROTOTYPES = {
     'eas_conv_wgrad_partial': (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     'eas_conv_wgrad_planes_partial': (C.c_int, [_P] * 3 + [C.c_int] * 7 + [_P]),
     'eas_conv_wgrad_reduce_many': (C.c_int, [_P, C.c_int, _P]),
+    'eas_dwconv_supported': (C.c_int, [C.c_int] * 6),
+    'eas_dwconv_fwd_stats_blocks': (C.c_int, [C.c_int] * 6),
+    'eas_dwconv_fwd': (C.c_int, [_P] * 4 + [C.c_int] * 5 + [_P, C.c_int, _P]),
+    'eas_dwconv_fwd_planes': (C.c_int, [_P] * 4 + [C.c_int] * 5 + [_P, C.c_int, _P]),
+    'eas_dwconv_dgrad': (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P]),
+    'eas_dwconv_wgrad_workspace_floats': (C.c_int64, [C.c_int] * 5),
+    'eas_dwconv_wgrad': (C.c_int, [_P] * 4 + [C.c_int] * 5 + [_P]),
+    'eas_dwconv_wgrad_planes': (C.c_int, [_P] * 4 + [C.c_int] * 5 + [_P]),
     'eas_spp_pool_fwd': (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 6 + [_P]),
     'eas_spp_pool_bwd': (C.c_int, [_P, _P, _P, C.c_int64] + [C.c_int] * 6 + [_P]),
     'eas_spp_pool_planes_fwd': (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 6 + [_P]),

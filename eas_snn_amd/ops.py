@@ -12,6 +12,7 @@ No CPU path: CPU tensors raise.
   ops_bn       conv output -> BatchNorm -> (P)LIF over T, the CSPLayer branch pair, BatchNorm + SiLU
   ops_sampler  K3: the adaptive sampler and the simpler embeddings
   ops_conv     dense convolutions on the matrix cores, weight packing and its scopes, weight-gradient side stream, fused eval blocks
+  ops_dwconv   depthwise 3x3 convolutions (DWConv.dconv of the depthwise=True models): forward, input gradient, weight gradient
   ops_events   K1 and the other event representations          ops_glue   SPP, upsample + concatenate, Focus
   ops_det      post-processing, SimOTA, detection loss         ops_group  grouped (multi-problem) launches (imported on its own)
 
@@ -21,11 +22,11 @@ forwards them to the context (``_ALIASES``)."""
 import sys
 import types
 
-from . import ops_bn, ops_conv, ops_core, ops_lif, ops_sampler
+from . import ops_bn, ops_conv, ops_core, ops_dwconv, ops_lif, ops_sampler
 from ._ctx import ctx
 
 _PLUMBING = {'C', 'collections', 'os', 'torch', '_lib', 'check', 'ptr', 'stream', 'opctx'}
-for _m in (ops_core, ops_lif, ops_bn, ops_sampler, ops_conv):
+for _m in (ops_core, ops_lif, ops_bn, ops_sampler, ops_dwconv, ops_conv):
     for _k, _v in vars(_m).items():
         if not _k.startswith('__') and _k not in _PLUMBING:
             globals()[_k] = _v
@@ -44,7 +45,7 @@ _ALIASES = {
     'ARSNN_FUSED': 'arsnn_fused', 'DEFER_WGRAD_REDUCE': 'defer_wgrad_reduce', '_PENDING_REDUCE': 'pending_reduce',
     'WGRAD_SIDE_BATCH': 'wgrad_side_batch', '_SIDE': 'side',
     'VERIFY_SMALL_INT': 'verify_small_int', 'SMALL_DGRAD': 'small_dgrad', '_PACK_SCOPE': 'pack_scope', '_PACK_GEN': 'pack_gen', '_FROZEN': 'frozen',
-    '_CONV_SINK': 'conv_sink', 'FUSED_ANN_EVAL': 'fused_ann_eval', '_DEFERRED': 'deferred_counters'}
+    '_CONV_SINK': 'conv_sink', 'FUSED_ANN_EVAL': 'fused_ann_eval', '_DEFERRED': 'deferred_counters', 'DWCONV': 'dwconv'}
 
 
 class _OpsModule(types.ModuleType):

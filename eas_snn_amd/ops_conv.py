@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from ._ctx import ctx as opctx
 from ._lib import check, ptr, stream
+from .ops_dwconv import dwconv2d, dwconv_eligible
 from .ops_core import FLAG_DECAY_INPUT, FLAG_FIRE_STRICT, FLAG_HARD_RESET, _call, _conv_stats_blocks, _dev, _eval_invstd, _f32c, _invstd_of_eval_model, _tag_flag, _timer_add, _timer_mark, _verify_tags, clear_conv_stats, dense, ghost, is_small_int, mark_small_int, new_planes, planes_of, set_tag, to_planes
 
 def conv2d_weight(x, weight, stride=1, small_int=None):
@@ -1012,7 +1013,7 @@ def conv_bn_act_eval(x, conv, bns, cats=None, packs=None, act='silu'):
 
 
 def conv2d(x, conv, small_int=None):
-    """``conv(x)`` for an ``nn.Conv2d`` on the matrix-core kernels where eligible (else ATen/MIOpen).
+    """``conv(x)`` for an ``nn.Conv2d`` on the matrix-core kernels (dense) or the depthwise 3x3 kernels where eligible (else ATen/MIOpen).
     A module that carries forward hooks (RecordHook in energy_estimation, event_evaluator.py:519-523; thop in
     get_model_info) is called the ordinary way so that the hooks fire."""
     if opctx.conv_sink is not None:
@@ -1020,6 +1021,8 @@ def conv2d(x, conv, small_int=None):
         opctx.conv_sink(conv, x, opctx.replicas)
     if conv._forward_hooks or conv._forward_pre_hooks or torch.nn.modules.module._global_forward_hooks:
         return conv(dense(x))
+    if opctx.dwconv and dwconv_eligible(x, conv):
+        return dwconv2d(x, conv, small_int)         # one 3x3 filter per channel (DWConv.dconv): the eas_dwconv kernels
     if not conv_eligible(x, conv):
         x = dense(x)
         return conv._conv_forward(x, conv.weight, conv.bias)

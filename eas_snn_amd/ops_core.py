@@ -369,7 +369,8 @@ def check_tags(what='this run'):
 
 # One backend: every dense 1x1 / 3x3 convolution of the step -- forward, input gradient, weight gradient -- runs on the
 # hand-written matrix-core kernels (eas_conv_fwd / eas_conv_dgrad_s2 / eas_conv_wgrad).  The library convolution remains only for
-# geometries those kernels do not cover at all (grouped / dilated / odd-width / other kernel sizes: none in the EAS-SNN models).
+# geometries those kernels do not cover at all (dilated / odd-width / other kernel sizes, grouped other than the depthwise 3x3 of ops_dwconv:
+# none in the EAS-SNN models).
 
 
 

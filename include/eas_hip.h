@@ -540,6 +540,37 @@ int eas_conv_wgrad_planes_partial(const void* x_planes, const float* grad_y, flo
                                   int stride, eas_stream_t stream);
 int eas_conv_wgrad_reduce_many(const EasWgradReduceJob* jobs, int njobs, eas_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution: groups == Cin == Cout == C, padding 1, dilation 1, stride 1 or 2 -- the `dconv` half of DWConv
+ * (yolox/models/network_blocks.py:59-76, always ksize 3), i.e. every block of the depthwise=True models (YOLOX-nano family).
+ * w [C][1][3][3] fp32, bias [C] or NULL, y [NI][C][Ho][Wo] fp32 with Ho = (Hi - 1) / stride + 1 (same for Wo).  No matrix cores: vector
+ * FMA from an LDS image of the input rows (zero halo), 8 channels x a band of output rows per block (csrc/dwconv.hip).
+ * x_form 1: x fp32 [NI][C][Hi][Wi], any C; x_form 2: x as SPIKE PLANES [NI][C/8][Hi*Wi][8] bf16, C % 8 == 0, 16-byte aligned (no
+ * restriction on Hi*Wi).  Both forms add the nine products in the same order (kh-major, kw-minor, bias last): on an x that is exact in
+ * bf16 they give bit-identical y.  Rows of up to 510 pixels; anything else returns EAS_ERR_UNSUPPORTED before a launch
+ * (eas_dwconv_supported: 1 / 0).
+ * stats / nb: NULL / 0, or (bias must be NULL) the BatchNorm partial sums of y exactly as eas_conv_fwd_stats leaves them:
+ * stats[C][nb][2] doubles, (sum, sum of squares) per pixel block, nb = eas_dwconv_fwd_stats_blocks(same geometry); any other nb is
+ * EAS_ERR_INVALID_ARG before a launch.  A lane's own <= 6 values are added in fp32, everything above in double in a fixed order. */
+int eas_dwconv_supported(int NI, int C, int Hi, int Wi, int stride, int x_form);
+int eas_dwconv_fwd_stats_blocks(int NI, int C, int Hi, int Wi, int stride, int x_form);
+int eas_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int NI, int C, int Hi, int Wi, int stride, double* stats,
+                   int nb, eas_stream_t stream);
+int eas_dwconv_fwd_planes(const void* x_planes, const float* w, const float* bias, float* y, int NI, int C, int Hi, int Wi, int stride,
+                          double* stats, int nb, eas_stream_t stream);
+/* grad_x [NI][C][Hi][Wi] from grad_y [NI][C][Ho][Wo] (Hi, Wi: the INPUT size of the forward).  Stride 1: the forward on grad_y with the
+ * taps flipped; stride 2: a gather per 2x2 input quad through the taps whose parity matches.  No scatter, no atomics: deterministic. */
+int eas_dwconv_dgrad(const float* grad_y, const float* w, float* grad_x, int NI, int C, int Hi, int Wi, int stride, eas_stream_t stream);
+/* grad_w [C][1][3][3]: nine sums over NI*Ho*Wo per channel.  Stage 1 leaves fp32 partials workspace[C][nparts][9] (lanes accumulate in
+ * fp32; wave and block are reduced in a fixed order), stage 2 adds the nparts partials in double in a fixed order: two runs give
+ * bit-equal gradients, no float atomics.  workspace: eas_dwconv_wgrad_workspace_floats floats (0 = unsupported geometry).  x as fp32
+ * or as spike planes (the forms of the forward). */
+int64_t eas_dwconv_wgrad_workspace_floats(int NI, int C, int Hi, int Wi, int stride);
+int eas_dwconv_wgrad(const float* x, const float* grad_y, float* workspace, float* grad_w, int NI, int C, int Hi, int Wi, int stride,
+                     eas_stream_t stream);
+int eas_dwconv_wgrad_planes(const void* x_planes, const float* grad_y, float* workspace, float* grad_w, int NI, int C, int Hi, int Wi,
+                            int stride, eas_stream_t stream);
+
 /* SPP pooling block fused: out[N][4C][H][W] = cat[x, maxpool_k0(x), maxpool_k1(x), maxpool_k2(x)] (stride 1, padding k/2,
  * odd k; ATen tie rule: first maximum in row-major order) and its backward (arg-max recomputed from x; deterministic gather).
  * Replaces SPPBottleneck.forward's three MaxPool2d + torch.cat (yolox/models/network_blocks.py:143-147).  H*W <= 1024. */

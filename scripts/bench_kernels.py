@@ -11,7 +11,8 @@ import eas_snn_amd  # noqa
 from eas_snn_amd import ops
 
 
-def timeit(fn, reps=20, warm=3):
+def timeit_spread(fn, reps=20, warm=3):
+    """(median, min, max) ms of ``reps`` runs after ``warm`` warm-up runs (HIP events)"""
     for _ in range(warm):
         fn()
     ts = []
@@ -20,7 +21,11 @@ def timeit(fn, reps=20, warm=3):
         s.record(); fn(); e.record(); torch.cuda.synchronize()
         ts.append(s.elapsed_time(e))
     ts.sort()
-    return ts[len(ts) // 2]
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def timeit(fn, reps=20, warm=3):
+    return timeit_spread(fn, reps, warm)[0]
 
 
 def smallconv(which):
@@ -42,7 +47,72 @@ def smallconv(which):
                   + f'  = {flops / (ms * 1e-3) / 1e12:6.2f} TFLOP/s')
 
 
+# the depthwise layers a depthwise=True SYOLOX-S of config 2 (256x320 canvas, NI = T * B = 192) would have: (C, H, W, stride)
+DWCONV_SHAPES = [(32, 128, 160, 2), (32, 64, 80, 1), (64, 64, 80, 2), (64, 32, 40, 1), (128, 32, 40, 2), (128, 16, 20, 1), (256, 16, 20, 2),
+                 (256, 8, 10, 1)]
+
+
+def dwconv(args):
+    """eas_dwconv forward (with the BatchNorm statistics epilogue) / input gradient / weight gradient against the library route
+    (EAS_DWCONV=0: dense() of the planes where the input is planes, ATen forward + the separate statistics pass, ATen
+    convolution_backward) at the same shapes in the same process.  GB/s = the algorithmic bytes of the NATIVE form over the time:
+    planes 2 B + fp32 4 B per element read, 4 B per element written."""
+    dev = torch.device('cuda:0')
+    NI = int(args[0]) if args else 192
+    L = eas_snn_amd.hip_library()
+    tot = {}
+    print(f'NI={NI}; ms = median (min..max) of 20')
+    for (C_, H, W, s) in DWCONV_SHAPES:
+        Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+        x = (torch.rand(NI, C_, H, W, device=dev) < 0.3).float()
+        sp = ops.to_planes(x)
+        w = torch.randn(C_, 1, 3, 3, device=dev) / 3
+        gy = torch.randn(NI, C_, Ho, Wo, device=dev)
+        nx, ny = x.numel(), gy.numel()
+        ws = torch.empty(L.eas_bn_workspace_doubles(C_), dtype=torch.float64, device=dev)
+
+        def stats_pass(y):
+            return L.eas_bn_stats_partial(ops.ptr(y), 0, NI, C_, Ho * Wo, ops.ptr(ws), ops.stream())
+
+        def native_fwd(xs):
+            with ops.conv_stats_scope(True):
+                ops.dwconv_fwd(x, w, None, s, xs)
+            ops.clear_conv_stats()
+
+        def lib_fwd(from_planes):
+            xd = ops.dense(ops.ghost(x.shape, dev, sp)) if from_planes else x
+            y = torch.ops.aten.convolution(xd, w, None, (s, s), (1, 1), (1, 1), False, (0, 0), C_)
+            assert stats_pass(y) > 0
+
+        def lib_bwd(mask):
+            torch.ops.aten.convolution_backward(gy, x, w, None, (s, s), (1, 1), (1, 1), False, (0, 0), C_, mask)
+
+        rows = [
+            ('fwd planes', lambda: native_fwd(sp), lambda: lib_fwd(True), 2 * nx + 4 * ny),
+            ('fwd fp32', lambda: native_fwd(None), lambda: lib_fwd(False), 4 * nx + 4 * ny),
+            ('dgrad', lambda: ops.dwconv_dgrad(gy, w, x.shape, s), lambda: lib_bwd((True, False, False)), 4 * ny + 4 * nx),
+            ('wgrad planes', lambda: ops.dwconv_wgrad(x, gy, s, sp), lambda: lib_bwd((False, True, False)), 2 * nx + 4 * ny),
+            ('wgrad fp32', lambda: ops.dwconv_wgrad(x, gy, s, None), lambda: lib_bwd((False, True, False)), 4 * nx + 4 * ny),
+        ]
+        with torch.no_grad():
+            for name, native, lib, nbytes in rows:
+                a, b = timeit_spread(native), timeit_spread(lib)
+                t = tot.setdefault(name, [0.0, 0.0, 0.0, 0.0])
+                t[0] += a[0]; t[1] += b[0]; t[2] += a[2] - a[1]; t[3] += b[2] - b[1]
+                print(f'dwconv C={C_:3d} {H:3d}x{W:3d} s{s} {name:12s}: native {a[0]:7.3f} ({a[1]:.3f}..{a[2]:.3f}) ms {nbytes / a[0] / 1e6:7.0f} GB/s'
+                      f' | library {b[0]:7.3f} ({b[1]:.3f}..{b[2]:.3f}) ms | x{b[0] / a[0]:.2f}', flush=True)
+        del x, sp, gy
+    for name, t in tot.items():
+        print(f'sum over the shapes {name:12s}: native {t[0]:8.3f} ms (sum of spreads {t[2]:.3f}) | library {t[1]:8.3f} ms (sum of spreads {t[3]:.3f})')
+    for form in ('planes', 'fp32'):
+        a = tot[f'fwd {form}'][0] + tot['dgrad'][0] + tot[f'wgrad {form}'][0]
+        b = tot[f'fwd {form}'][1] + tot['dgrad'][1] + tot[f'wgrad {form}'][1]
+        print(f'forward + both gradients, {form} input: native {a:.3f} ms | library {b:.3f} ms | x{b / a:.2f}')
+
+
 if __name__ == '__main__':
     what = sys.argv[1] if len(sys.argv) > 1 else 'smallconv'
     if what == 'smallconv':
         smallconv(sys.argv[2:])
+    elif what == 'dwconv':
+        dwconv(sys.argv[2:])
