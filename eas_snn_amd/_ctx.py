@@ -30,6 +30,7 @@ class Context:
         self.defer_wgrad_reduce = _env_flag('EAS_DEFER_WGRAD_REDUCE', '0')
         self.wgrad_side_batch = int(os.environ.get('EAS_WGRAD_SIDE', '16'))   # 0: everything on the main stream; 16: swept on config 2 (12 / 15 / 17 / 20 / 24 lose 0.1-0.3 ms of its 0.37 ms)
         self.dwconv = _env_flag('EAS_DWCONV')                          # 0: depthwise 3x3 convolutions on the library (ATen/MIOpen) as before the eas_dwconv kernels (the tests' comparison route)
+        self.device_ap = _env_flag('EAS_DEVICE_AP')                    # 0: the evaluator computes no AP on the device (pycocotools if importable, else None fields, as before the eas_cocoeval kernels)
         self.verify_small_int = False       # tests switch this on: every tagged tensor is checked (host sync) before it is used
         # ---- scopes
         self.state_writeback = True         # final membrane potentials are written back after a multi-step call (ops.no_state_writeback)

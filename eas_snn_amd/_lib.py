@@ -229,6 +229,12 @@ PROTOTYPES = {
     'eas_adam_advance_steps': (C.c_int, [_P, C.c_int, _P]),
     'eas_adam_step_ex': (C.c_int, [_P, C.c_int, C.c_longlong, C.POINTER(EasAdamHyper), _P]),
     'eas_adam_advance_steps_ex': (C.c_int, [_P, C.c_int, _P, _P]),
+    'eas_cocoeval_supported': (C.c_int, [C.c_int64] * 3 + [C.c_int] * 5 + [C.c_int64]),
+    'eas_cocoeval_workspace_bytes': (C.c_int64, [C.c_int64]),
+    'eas_cocoeval_keys': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
+    'eas_cocoeval_match': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int,
+                                     C.c_int64, _P, _P, _P, _P, _P, _P]),
+    'eas_cocoeval_accumulate': (C.c_int, [_P] * 5 + [C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
 }
 
 

@@ -13,12 +13,18 @@ model moved.  With a live RCCL process group a capture waits until the group's w
 (``yolox.utils.wait_process_group_idle``: a condition read from the flight recorder, not a delay); where that cannot be established
 the evaluator launches eagerly.
 
-mAP itself (COCO API) is outside the hot path: it is computed when ``pycocotools`` is importable, else the AP fields
-are ``None`` and the summary says so -- detections, timings and the loop are what this file provides."""
+mAP itself (``COCOeval(gt, dt, 'bbox')`` evaluate -> accumulate -> summarize, :446-461) is computed on the device by ``ops.coco_eval``
+(the eas_cocoeval kernels: what the reference's own native module yolox/layers/cocoeval computes, bit for bit) when the model lives on the
+GPU: a single process feeds it the device rows of the post-processing directly -- boxes and scores by the torch expressions of
+``convert_to_coco_format``, applied on the device -- and with ``distributed=True`` rank 0 uploads the gathered records.  The ground
+truths are numbered 0.. in ``gt_dict`` order as getcocoGT numbers them (:365-372).  The return triple is ``(AP, AP50, timings + the twelve
+lines of summarize + the per-class AP / AR tables)``.  The Python records, ``return_outputs``, the timers and the statistics are
+unchanged.  A model on the CPU, ``EAS_DEVICE_AP=0`` (``ctx.device_ap``) or an input beyond the kernels' limits (the summary names the
+reason) take the route of before: pycocotools when importable, else ``None`` AP fields and a summary that says so."""
 import itertools
 import os
 import time
-from collections import ChainMap, defaultdict
+from collections import ChainMap, Counter, defaultdict
 
 import torch
 
@@ -87,6 +93,15 @@ class _GraphedBatch:
         return [self.rows[i, :n].clone() if n else None for i, n in enumerate(counts)]
 
 
+def _per_class_table(per_class, headers, columns=6):
+    """name / value pairs laid out ``columns`` cells wide as a pipe table (the layout of per_class_AP_table / per_class_AR_table, :35-80)"""
+    from tabulate import tabulate
+    cells = [x for item in per_class.items() for x in item]
+    width = min(columns, len(cells))
+    rows = itertools.zip_longest(*[cells[i::width] for i in range(width)])
+    return tabulate(rows, tablefmt='pipe', floatfmt='.3f', headers=headers * (width // len(headers)), numalign='left')
+
+
 class _null:
     def __enter__(self):
         return self
@@ -115,6 +130,7 @@ class EventEvaluator:
         self._graphed = {}                  # signature -> _GraphedBatch (full batch, short last batch)
         self.graphs_recorded = 0
         self.last_statistics = None
+        self.last_coco = None               # the ``ops.coco_eval`` result of the last evaluation that computed its AP on the device
 
     # ------------------------------------------------------------------ the loop
     def evaluate(self, model, distributed=False, half=False, trt_file=None, decoder=None, test_size=None, return_outputs=False):
@@ -138,6 +154,9 @@ class EventEvaluator:
 
     def _evaluate_loop(self, model, distributed, decoder, return_outputs, dev, graph_ok):
         data_list, output_data, gt_dict = [], {}, {}
+        from eas_snn_amd._ctx import ctx
+        device_ap = dev.type == 'cuda' and ctx.device_ap
+        feed = [] if device_ap and not distributed else None          # single process: the detections stay on the device for the AP
         inference_time = nms_time = 0.0
         n_batches = len(self.dataloader)
         n_samples = max(n_batches - 1, 1)
@@ -165,6 +184,8 @@ class EventEvaluator:
                 if timed:
                     nms_end = time_synchronized()
                     nms_time += nms_end - infer_end
+            if feed is not None:
+                self._feed_device_rows(feed, outputs, info_imgs, ids, dev)
             elems, image_wise = self.convert_to_coco_format(outputs, info_imgs, ids, return_outputs=True)
             data_list.extend(elems)
             output_data.update(image_wise)
@@ -181,7 +202,7 @@ class EventEvaluator:
             output_data = dict(ChainMap(*gather(output_data, dst=0)))
             torch.distributed.reduce(statistics, dst=0)
         self.last_statistics = statistics
-        eval_results = self.evaluate_prediction(data_list, gt_dict, statistics)
+        eval_results = self.evaluate_prediction(data_list, gt_dict, statistics, device=dev if device_ap else None, feed=feed)
         synchronize()
         if return_outputs:
             return eval_results, output_data
@@ -227,8 +248,79 @@ class EventEvaluator:
             return data_list, image_wise
         return data_list
 
+    def _feed_device_rows(self, feed, outputs, info_imgs, ids, dev):
+        """the batch's detections for ``ops.coco_eval`` without leaving the device: (image id int64 [n], class int32 [n], xywh fp32 [n,4],
+        score fp32 [n]) by the expressions of ``convert_to_coco_format`` (the division is by a tensor holding the float32 scale: a true
+        division like the CPU's, where tensor / python number on the GPU multiplies by the reciprocal)"""
+        kept = [k for k, o in enumerate(outputs) if o is not None]
+        if not kept:
+            return
+        rows = torch.cat([outputs[k].detach() for k in kept])
+        counts = [outputs[k].shape[0] for k in kept]
+        # per-image values go to the device as they are (a few numbers) and are spread over the rows there: a host tensor operation of
+        # this many rows would wake the host's thread pool, which then competes with the record loop below for the processors
+        per_row = torch.repeat_interleave(torch.arange(len(kept), device=dev), torch.tensor(counts, device=dev), output_size=sum(counts))
+        scale = torch.tensor([min(self.img_size[0] / float(info_imgs[0][k]), self.img_size[1] / float(info_imgs[1][k])) for k in kept],
+                             dtype=torch.float32, device=dev)[per_row]
+        img = torch.as_tensor(ids).to(torch.int64)[kept].to(dev)[per_row]
+        bboxes = rows[:, 0:4] / scale[:, None]
+        scores = rows[:, 4] * rows[:, 5]
+        xywh = bboxes.clone()
+        xywh[:, 2:4] -= xywh[:, 0:2]
+        feed.append((img, rows[:, 6].to(torch.int32), xywh, scores))
+
+    def _device_ap(self, data_dict, gt_dict, feed, dev, names):
+        """-> (ap50_95, ap50, text) from ``ops.coco_eval`` + ``ops.coco_summarize``, or the reason (str) why the kernels decline this input"""
+        import numpy as np
+        from eas_snn_amd import ops
+        image_ids = sorted(gt_dict)
+        dense = {i: k for k, i in enumerate(image_ids)}
+        gt_img, gt_cls, gt_box = [], [], []
+        for i, g in gt_dict.items():                    # annotation ids 0.. in this order (getcocoGT, :365-372)
+            for box, c in zip(g['bboxes'], g['category_ids']):
+                gt_img.append(dense[i])
+                gt_cls.append(c)
+                gt_box.append(box)
+        per_pair = Counter(zip(gt_img, gt_cls))
+        max_gt = max(per_pair.values()) if per_pair else 0
+        D = sum(int(f[3].numel()) for f in feed) if feed is not None else len(data_dict)
+        G, I, K = len(gt_img), len(image_ids), len(names)
+        if not ops.coco_eval_supported(D, G, I, K, max_gt=max_gt):      # asked before anything goes to the device
+            return (f'{D} detections, {G} ground truths ({max_gt} in one image and class), {I} images, {K} classes are beyond the limits of '
+                    'the eas_cocoeval kernels')
+        if feed is not None:
+            det_ids = torch.cat([f[0] for f in feed])
+            det_cls, det_box, det_score = (torch.cat([f[j] for f in feed]) for j in (1, 2, 3))
+        else:                                           # gathered records (rank 0 of a distributed evaluation): uploaded
+            det_ids = torch.tensor([d['image_id'] for d in data_dict], dtype=torch.int64, device=dev)
+            det_cls = torch.tensor([d['category_id'] for d in data_dict], dtype=torch.int32, device=dev)
+            det_box = torch.from_numpy(np.array([d['bbox'] for d in data_dict], np.float32).reshape(-1, 4)).to(dev)
+            det_score = torch.from_numpy(np.array([d['score'] for d in data_dict], np.float32)).to(dev)
+        # image id -> dense index = its position among the sorted ids (pycocotools: imgIds sorted); an id without ground-truth entry: dropped
+        table = torch.tensor(image_ids, dtype=torch.int64, device=dev)
+        pos = torch.searchsorted(table, det_ids).clamp_(max=max(I - 1, 0))
+        det_img = torch.where(table[pos] == det_ids, pos, torch.full_like(pos, -1)) if I else torch.full_like(det_ids, -1)
+        res = ops.coco_eval(det_img, det_cls, det_box, det_score,
+                            torch.tensor(gt_img, dtype=torch.int32, device=dev), torch.tensor(gt_cls, dtype=torch.int32, device=dev),
+                            torch.tensor(gt_box, dtype=torch.float32, device=dev).reshape(-1, 4), I, K, max_gt=max_gt)
+        self.last_coco = dict(res, detections=D, ground_truths=G, images=I)
+        stats, lines = ops.coco_summarize(res)
+        text = ''.join(line + '\n' for line in lines)
+        precision, recall = res['precision'].cpu().numpy(), res['recall'].cpu().numpy()
+
+        def mean100(v):
+            v = v[v > -1]
+            return float(np.mean(v) * 100) if v.size else float('nan')
+        if self.per_class_AP:                           # area range 'all', the last max-dets entry (:58-80)
+            text += 'per class AP:\n' + _per_class_table({n: mean100(precision[:, :, k, 0, -1]) for k, n in enumerate(names)}, ['class', 'AP']) + '\n'
+        if self.per_class_AR:
+            text += 'per class AR:\n' + _per_class_table({n: mean100(recall[:, k, 0, -1]) for k, n in enumerate(names)}, ['class', 'AR']) + '\n'
+        return float(stats[0]), float(stats[1]), text
+
     # ------------------------------------------------------------------ summary (:396-462)
-    def evaluate_prediction(self, data_dict, gt_dict, statistics):
+    def evaluate_prediction(self, data_dict, gt_dict, statistics, device=None, feed=None):
+        """``device``: where ``ops.coco_eval`` computes the AP (None: the host route); ``feed``: the detections as device arrays
+        (``_feed_device_rows``), else ``data_dict`` is uploaded"""
         if not is_main_process():
             return 0, 0, None
         inference_time, nms_time, n_samples = (float(v) for v in statistics.tolist())
@@ -238,6 +330,12 @@ class EventEvaluator:
                          zip(['forward', 'NMS', 'inference'], [a_infer, a_nms, a_infer + a_nms])) + '\n'
         if not data_dict:
             return 0, 0, info
+        names = getattr(getattr(self.dataloader, 'dataset', None), 'class_names', None) or [str(i) for i in range(self.num_classes)]
+        if device is not None:
+            res = self._device_ap(data_dict, gt_dict, feed, device, names)
+            if not isinstance(res, str):
+                return res[0], res[1], info + res[2]
+            info += 'AP on the device declined: ' + res + '\n'
         try:
             from pycocotools.coco import COCO
             from pycocotools.cocoeval import COCOeval
@@ -246,7 +344,6 @@ class EventEvaluator:
                 len(data_dict), len(gt_dict))
         import contextlib
         import io
-        names = getattr(getattr(self.dataloader, 'dataset', None), 'class_names', None) or [str(i) for i in range(self.num_classes)]
         gt = COCO()
         gt.dataset = {'images': [{'id': i, 'file_name': str(i), 'width': g['width'], 'height': g['height']} for i, g in gt_dict.items()],
                       'annotations': [], 'categories': [{'id': i, 'name': n, 'supercategory': n} for i, n in enumerate(names)]}

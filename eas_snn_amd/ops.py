@@ -14,7 +14,7 @@ No CPU path: CPU tensors raise.
   ops_conv     dense convolutions on the matrix cores, weight packing and its scopes, weight-gradient side stream, fused eval blocks
   ops_dwconv   depthwise 3x3 convolutions (DWConv.dconv of the depthwise=True models): forward, input gradient, weight gradient
   ops_events   K1 and the other event representations          ops_glue   SPP, upsample + concatenate, Focus
-  ops_det      post-processing, SimOTA, detection loss         ops_group  grouped (multi-problem) launches (imported on its own)
+  ops_det      post-processing, COCO AP, SimOTA, det. loss      ops_group  grouped (multi-problem) launches (imported on its own)
 
 Every switch and scope the operators consult is a field of ONE object, ``eas_snn_amd._ctx.ctx`` (``ops.ctx``).  The module-level names
 of earlier rounds (``ops.WGRAD_SIDE_BATCH``, ``ops.VERIFY_SMALL_INT``, ``ops._PLANES_SCOPE`` ...) still read and ASSIGN: this module
@@ -45,7 +45,8 @@ _ALIASES = {
     'ARSNN_FUSED': 'arsnn_fused', 'DEFER_WGRAD_REDUCE': 'defer_wgrad_reduce', '_PENDING_REDUCE': 'pending_reduce',
     'WGRAD_SIDE_BATCH': 'wgrad_side_batch', '_SIDE': 'side',
     'VERIFY_SMALL_INT': 'verify_small_int', 'SMALL_DGRAD': 'small_dgrad', '_PACK_SCOPE': 'pack_scope', '_PACK_GEN': 'pack_gen', '_FROZEN': 'frozen',
-    '_CONV_SINK': 'conv_sink', 'FUSED_ANN_EVAL': 'fused_ann_eval', '_DEFERRED': 'deferred_counters', 'DWCONV': 'dwconv'}
+    '_CONV_SINK': 'conv_sink', 'FUSED_ANN_EVAL': 'fused_ann_eval', '_DEFERRED': 'deferred_counters', 'DWCONV': 'dwconv',
+    'DEVICE_AP': 'device_ap'}
 
 
 class _OpsModule(types.ModuleType):

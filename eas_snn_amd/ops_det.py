@@ -1,9 +1,11 @@
-"""Detections: batch-wide post-processing (confidence mask + class-aware NMS), SimOTA assignment, decode + loss terms + gradient
-(reference: yolox/utils/boxes.py:33-77; yolox/models/yolo_head.py get_losses / get_assignments).
+"""Detections: batch-wide post-processing (confidence mask + class-aware NMS), COCO-style average precision, SimOTA assignment, decode +
+loss terms + gradient (reference: yolox/utils/boxes.py:33-77; yolox/layers/cocoeval/cocoeval.cpp; yolox/models/yolo_head.py get_losses /
+get_assignments).
 
 Part of the operator layer of ``eas_snn_amd.ops`` (split by kernel family; ``ops`` re-exports everything here, so ``ops.<name>`` keeps working)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -33,6 +35,133 @@ def postprocess(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, class_agn
     out, cnt = postprocess_device(prediction, num_classes, conf_thre, nms_thre, class_agnostic)
     counts = cnt.tolist()                                   # the one host synchronisation: the result is a ragged python list
     return [out[i, :n] if n else None for i, n in enumerate(counts)]
+
+
+# ------------------------------------------------------------------------------------------------ average precision
+COCO_AREA_NAMES = ('all', 'small', 'medium', 'large')
+_COCO_TABLES = {}
+
+
+def coco_default_params():
+    """pycocotools' Params('bbox') -- the same numpy expressions, so the tables are bit-equal to the ones the reference evaluates with"""
+    return dict(iou_thr=np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True),
+                rec_thr=np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True),
+                area_rng=np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64),
+                max_dets=(1, 10, 100))
+
+
+def _coco_tables(device, iou_thr, rec_thr, area_rng, max_dets):
+    """the parameter tables as host numpy arrays and on the device (uploaded once per distinct set and device)"""
+    d = coco_default_params()
+    iou_thr = np.ascontiguousarray(d['iou_thr'] if iou_thr is None else iou_thr, np.float64).reshape(-1)
+    rec_thr = np.ascontiguousarray(d['rec_thr'] if rec_thr is None else rec_thr, np.float64).reshape(-1)
+    area_rng = np.ascontiguousarray(d['area_rng'] if area_rng is None else area_rng, np.float64).reshape(-1, 2)
+    max_dets = np.ascontiguousarray(sorted(int(v) for v in max_dets), np.int32)
+    if rec_thr.size > 1 and not np.all(np.diff(rec_thr) >= 0):
+        raise ValueError('rec_thr must be ascending')
+    key = (str(device), iou_thr.tobytes(), rec_thr.tobytes(), area_rng.tobytes(), max_dets.tobytes())
+    t = _COCO_TABLES.get(key)
+    if t is None:
+        if len(_COCO_TABLES) >= 16:
+            _COCO_TABLES.clear()
+        t = _COCO_TABLES[key] = tuple(torch.from_numpy(a).to(device) for a in (iou_thr, rec_thr, area_rng, max_dets))
+    return (iou_thr, rec_thr, area_rng, max_dets), t
+
+
+def coco_eval_supported(D, G, num_images, num_classes, T=10, R=101, A=4, M=3, max_gt=0):
+    """the limits of the eas_cocoeval_* kernels (include/eas_hip.h): at most 64 ground truths per (image, category), T <= 16, A <= 8,
+    A * T <= 64, R <= 128, M <= 8, images * classes <= 2^24"""
+    return bool(_lib.lib().eas_cocoeval_supported(int(D), int(G), int(num_images), int(num_classes), int(T), int(R), int(A), int(M), int(max_gt)))
+
+
+@torch.no_grad()
+def coco_eval(det_img, det_cls, det_box, det_score, gt_img, gt_cls, gt_box, num_images, num_classes, gt_id=None, iou_thr=None, rec_thr=None,
+              area_rng=None, max_dets=(1, 10, 100), max_gt=None):
+    """COCO bbox evaluation on the device: ``COCOeval(gt, dt, 'bbox')`` ``.evaluate()`` + ``.accumulate()`` as the reference's native module
+    computes them (yolox/layers/cocoeval/cocoeval.cpp), bit for bit.  -> dict(precision float64 [T,R,K,A,M], recall float64 [T,K,A,M],
+    counts int32 [K,A] = ground truths not ignored per (category, area range), params = the host tables), tensors on the device.
+
+    det_img / gt_img: dense image index 0..num_images-1 (the position of the image id in the sorted ids); det_cls / gt_cls: 0..num_classes-1;
+    boxes (x, y, w, h) float32; rows whose image or category is outside the tables are dropped, as pycocotools drops them.  Parameters
+    default to pycocotools' (``coco_default_params``).  ``iscrowd`` is 0 throughout; the ``scores`` array is not produced.
+
+    ``gt_id`` (default 0..G-1, the numbering of the reference's getcocoGT, event_evaluator.py:367) matters in one way, a quirk of the
+    reference that is kept: a detection counts as matched when the id of its ground truth is not 0 (cocoeval.cpp:322-323, pycocotools'
+    ``dtm``), so a detection matched to the annotation with id 0 takes that ground truth and still counts as unmatched.
+
+    ``max_gt``: the largest number of ground truths in one (image, category) if the caller knows it; None computes it (one host
+    synchronisation -- pass it under graph capture).  An input beyond the kernels' limits (``coco_eval_supported``) raises before anything
+    is launched."""
+    _dev(det_img, det_cls, det_box, det_score, gt_img, gt_cls, gt_box, gt_id)
+    dev = det_box.device
+    D, G, I, K = int(det_score.numel()), int(gt_img.numel()), int(num_images), int(num_classes)
+    det_img, det_cls = det_img.to(torch.int32).contiguous(), det_cls.to(torch.int32).contiguous()
+    gt_img, gt_cls = gt_img.to(torch.int32).contiguous(), gt_cls.to(torch.int32).contiguous()
+    det_box, gt_box, det_score = _f32c(det_box).reshape(D, 4), _f32c(gt_box).reshape(G, 4), _f32c(det_score).reshape(D)
+    gt_id = torch.arange(G, dtype=torch.int64, device=dev) if gt_id is None else gt_id.to(torch.int64).contiguous()
+    host, (d_iou, d_rec, d_area, d_maxdets) = _coco_tables(dev, iou_thr, rec_thr, area_rng, max_dets)
+    T, R, A, M = len(host[0]), len(host[1]), len(host[2]), len(host[3])
+    if max_gt is None:
+        max_gt = 0
+        if G:
+            ok = (gt_img >= 0) & (gt_img < I) & (gt_cls >= 0) & (gt_cls < K)
+            counts = torch.unique((gt_img.long() * K + gt_cls)[ok], return_counts=True)[1]
+            max_gt = int(counts.max()) if counts.numel() else 0
+    L = _lib.lib()
+    if not L.eas_cocoeval_supported(D, G, I, K, T, R, A, M, int(max_gt)):
+        raise _lib.EasHipError(f'eas_cocoeval: beyond the kernels\' limits (D={D} G={G} images={I} classes={K} T={T} R={R} A={A} M={M}, '
+                               f'{int(max_gt)} ground truths in one (image, category); include/eas_hip.h lists them)')
+    i64 = dict(dtype=torch.int64, device=dev)
+    det_key, gt_key = torch.empty(D, **i64), torch.empty(G, **i64)
+    _call('eas_cocoeval_keys', 12 * D + 16 * G, L.eas_cocoeval_keys, ptr(det_img), ptr(det_cls), ptr(det_score), D, ptr(gt_img), ptr(gt_cls), G,
+          I, K, ptr(det_key), ptr(gt_key), stream())
+    det_key, det_order = torch.sort(det_key, stable=True)
+    gt_key, gt_order = torch.sort(gt_key, stable=True)
+    rank = torch.empty(D, dtype=torch.int32, device=dev)
+    matched, ignored, key2 = torch.empty(D, **i64), torch.empty(D, **i64), torch.empty(D, **i64)
+    npig = torch.empty((K, A), dtype=torch.int32, device=dev)
+    _call('eas_cocoeval_match', 60 * D + 40 * G, L.eas_cocoeval_match, ptr(det_key), ptr(det_order), ptr(det_box), D, ptr(gt_key), ptr(gt_order),
+          ptr(gt_box), ptr(gt_id), G, I, K, ptr(d_iou), T, ptr(d_area), A, int(host[3].max()) if M else 0, int(max_gt), ptr(rank), ptr(matched),
+          ptr(ignored), ptr(key2), ptr(npig), stream())
+    key2, order2 = torch.sort(key2, stable=True)
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+    ws = torch.empty(L.eas_cocoeval_workspace_bytes(D), dtype=torch.uint8, device=dev)
+    _call('eas_cocoeval_accumulate', 48 * D + 20 * D * A * M + 8 * precision.numel(), L.eas_cocoeval_accumulate, ptr(key2),
+          ptr(order2), ptr(rank), ptr(matched), ptr(ignored), D, ptr(npig), K, T, ptr(d_rec), R, A, ptr(d_maxdets), M, ptr(precision),
+          ptr(recall), ptr(ws), stream())
+    return dict(precision=precision, recall=recall, counts=npig,
+                params=dict(iou_thr=host[0], rec_thr=host[1], area_rng=host[2], max_dets=[int(v) for v in host[3]]))
+
+
+def coco_summarize(result):
+    """``COCOeval.summarize`` for bbox (pycocotools cocoeval.py _summarizeDets): (stats float64 [12], the twelve text lines) from a
+    ``coco_eval`` result.  stats = AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl, each the mean over the entries > -1 of
+    its slice (-1 if there is none), taken on the host in float64 from the copied arrays."""
+    precision, recall = result['precision'], result['recall']
+    precision = precision.cpu().numpy() if torch.is_tensor(precision) else np.asarray(precision)
+    recall = recall.cpu().numpy() if torch.is_tensor(recall) else np.asarray(recall)
+    params = result.get('params') or coco_default_params()
+    iou_thr, max_dets = np.asarray(params['iou_thr'], np.float64), [int(v) for v in params['max_dets']]
+    if precision.shape[3] != len(COCO_AREA_NAMES) or len(max_dets) < 3:
+        raise ValueError('coco_summarize needs the four area ranges (all, small, medium, large) and three max-dets entries')
+
+    def one(ap, thr, area, md):
+        a, m = COCO_AREA_NAMES.index(area), max_dets.index(md)
+        s = precision if ap else recall
+        if thr is not None:
+            s = s[np.where(thr == iou_thr)[0]]
+        s = s[:, :, :, a, m] if ap else s[:, :, a, m]
+        mean = float(np.mean(s[s > -1])) if len(s[s > -1]) else -1.0
+        iou = '{:0.2f}:{:0.2f}'.format(iou_thr[0], iou_thr[-1]) if thr is None else '{:0.2f}'.format(thr)
+        line = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'.format(
+            'Average Precision' if ap else 'Average Recall', '(AP)' if ap else '(AR)', iou, area, md, mean)
+        return mean, line
+    rows = [one(1, None, 'all', max_dets[2]), one(1, .5, 'all', max_dets[2]), one(1, .75, 'all', max_dets[2]),
+            one(1, None, 'small', max_dets[2]), one(1, None, 'medium', max_dets[2]), one(1, None, 'large', max_dets[2]),
+            one(0, None, 'all', max_dets[0]), one(0, None, 'all', max_dets[1]), one(0, None, 'all', max_dets[2]),
+            one(0, None, 'small', max_dets[2]), one(0, None, 'medium', max_dets[2]), one(0, None, 'large', max_dets[2])]
+    return np.array([r[0] for r in rows], np.float64), [r[1] for r in rows]
 
 
 def simota_supported(gt_valid, bbox_preds):

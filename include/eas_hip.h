@@ -794,6 +794,41 @@ typedef struct {
 int eas_adam_step_ex(const void* table, int ntensors, long long total_blocks, const EasAdamHyper* hyper, eas_stream_t stream);
 int eas_adam_advance_steps_ex(const void* table, int ntensors, double* ema_updates, eas_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO-style bounding-box evaluation (additive, ABI 9): the evaluate -> accumulate sequence of COCOeval(gt, dt, 'bbox') as the reference's
+ * native module computes it (yolox/layers/cocoeval/cocoeval.cpp:59-197 EvaluateImages, :221-476 Accumulate; driven as in
+ * yolox/layers/fast_coco_eval_api.py:62-117).  iscrowd is always 0 (yolox/evaluators/event_evaluator.py:365-372).  Boxes (x, y, w, h) and
+ * scores are float32, widened to double; IoU in the order of pycocotools' bbIou; results equal the reference's bit for bit.
+ * Call order: eas_cocoeval_keys -> stable ascending sort of det_key and gt_key by the caller (the permutations are det_order / gt_order) ->
+ * eas_cocoeval_match -> stable ascending sort of key2 (permutation order2) -> eas_cocoeval_accumulate.
+ * pair = image * K + category; masks carry bit a * T + t for (area range a, IoU threshold t).  "Matched" means the matched ground
+ * truth's gt_id is not 0 (cocoeval.cpp:322-323): the reference numbers annotations from 0 (event_evaluator.py:367), a match to id 0
+ * takes that ground truth and counts as unmatched.
+ * Limits: ground truths per (image, category) <= 64; T <= 16, A <= 8, A * T <= 64, R <= 128, M <= 8; I * K <= 2^24; K * A * M <= 2^20;
+ * D, G < 2^31; rec_thr ascending.  Beyond them: EAS_ERR_UNSUPPORTED, nothing is launched.  Zero detections, ground truths or images are
+ * valid (their pointers may be NULL).  The per-threshold `scores` array of pycocotools is not produced. */
+int eas_cocoeval_supported(int64_t D, int64_t G, int64_t I, int K, int T, int R, int A, int M, int64_t max_gt_per_pair);
+int64_t eas_cocoeval_workspace_bytes(int64_t D);
+/* det_key[D] = pair << 32 | bits that order scores descending; gt_key[G] = pair (I * K for an index outside the tables).
+ * Replaces the grouping of COCOeval._prepare and the sort key of SortInstancesByDetectionScore (cocoeval.cpp:16-28). */
+int eas_cocoeval_keys(const int32_t* det_img, const int32_t* det_cls, const float* det_score, int64_t D, const int32_t* gt_img,
+                      const int32_t* gt_cls, int64_t G, int64_t I, int K, int64_t* det_key, int64_t* gt_key, eas_stream_t stream);
+/* Stage 1, replaces EvaluateImages (cocoeval.cpp:140-197 with :16-55 and MatchDetectionsToGroundTruth :59-138) and the IoU of pycocotools'
+ * computeIoU.  det_key / gt_key sorted; det_box / gt_box / gt_id in input order.  Outputs by sorted position: rank inside the pair, matched
+ * and ignored masks (first max_det of a pair, 0 behind), key2 = category << 32 | score bits for the second sort; npig [K][A] = non-ignored
+ * ground truths (integer atomics). */
+int eas_cocoeval_match(const int64_t* det_key, const int64_t* det_order, const float* det_box, int64_t D, const int64_t* gt_key,
+                       const int64_t* gt_order, const float* gt_box, const int64_t* gt_id, int64_t G, int64_t I, int K, const double* iou_thr,
+                       int T, const double* area_rng, int A, int max_det, int64_t max_gt_per_pair, int32_t* rank, uint64_t* matched,
+                       uint64_t* ignored, int64_t* key2, int32_t* npig, eas_stream_t stream);
+/* Stage 2, replaces Accumulate (cocoeval.cpp:370-476 with BuildSortedDetectionList :221-271 and ComputePrecisionRecallCurve :282-369).
+ * key2 sorted, order2 its permutation; rank / matched / ignored / npig as eas_cocoeval_match left them; max_dets: DEVICE int32 [M].
+ * precision [T][R][K][A][M] and recall [T][K][A][M] are written completely (-1 where no ground truth counts; precision = tp / (tp + fp) as
+ * in the reference's C++, not pycocotools' tp / (tp + fp + spacing(1))).  workspace: eas_cocoeval_workspace_bytes(D) bytes. */
+int eas_cocoeval_accumulate(const int64_t* key2, const int64_t* order2, const int32_t* rank, const uint64_t* matched, const uint64_t* ignored,
+                            int64_t D, const int32_t* npig, int K, int T, const double* rec_thr, int R, int A, const int32_t* max_dets, int M,
+                            double* precision, double* recall, void* workspace, eas_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
