@@ -551,6 +551,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_many_kernel(const Reduc
     wgrad_reduce_block(jobs.slabs[lo], jobs.gw[lo], jobs.n[lo], jobs.kslices[lo], (int)blockIdx.x - jobs.first_block[lo]);
 }
 
+// ---- host side: geometry -> kernel instance -> plan.  Every decision is made once: wg_inst names the instance, wg_fit says whether a tile
+// fits it, wg_support whether a problem has a kernel at all, wg_select maps the instance to its template (for the plan and the launch).
+constexpr size_t kWgLdsMax = 160 * 1024;
+
 int pick_rows(int Ho, int Wo, int cap) {
     int best = 0;
     for (int rt = 1; rt * Wo <= cap; ++rt)
@@ -558,85 +562,39 @@ int pick_rows(int Ho, int Wo, int cap) {
     return best;
 }
 
-template <int S, int XT, int PM, int PN, int VEC, bool XPL = false, int NITX = 0>
-int launch_wgrad(const float* x, const float* gy, float* slabs, WgGeom g, hipStream_t st) {
-    auto kern = conv_wgrad_mfma_kernel<S, XT, PM, PN, VEC, XPL, NITX>;
-    constexpr int NT = 192 * PM * PN;
-    const size_t lds = (size_t)(g.single ? 1 : 2) * (3 * PM * A_PLANE + (size_t)XT * PN * g.Q * ROWB);
-    const int nbg = PN == 1 && g.Cin < 32 ? (g.Cin + 7) / 8 : 4 * PN;
-    const int nitems = (TP / VEC) * 4 * PM + g.nseg * g.rows_in * (g.Wst / VEC) * nbg;
-    if (lds > 160 * 1024 || nitems > (NITX ? NITX : (PM * PN == 4 ? 1 : 2)) * NT) {
-        if (eas_dev_env("EAS_CONV_DBG")) fprintf(stderr, "wgrad launch: lds %zu nitems %d NT %d PM %d PN %d VEC %d RT %d Q %d\n", lds, nitems, NT, PM, PN, VEC, g.RT, g.Q);
-        return EAS_ERR_UNSUPPORTED;
-    }
-    if constexpr (XT == 1) {
-        // the spike-input instances address a tile's items as 32-bit byte offsets from the tile base in raw buffer loads whose descriptors say
-        // num_records = 2^31 (offsets from there on mean "outside: zeros"): the images of a tile plus the 8 channel rows of an item must stay
-        // below that (ADVICE r3; far above every EAS-SNN shape: a 64-channel 128x160 image is 5 MB)
-        const size_t img_y = (size_t)g.Cout * g.Ho * g.pitchY * 4, img_x = (size_t)g.Cin * g.Hi * g.pitchX * (XPL ? 2 : 4);
-        const size_t span = (size_t)(g.nseg + 1) * (img_y > img_x ? img_y : img_x) + (size_t)8 * g.Hi * g.pitchX * 4;
-        if (span >= ((size_t)1 << 31)) return EAS_ERR_UNSUPPORTED;
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
-        attr_set = true;
-    }
-    g.ci_blocks = (g.Cin + 32 * PN - 1) / (32 * PN);
-    const int co_blocks = (g.Cout + 32 * PM - 1) / (32 * PM);
-    dim3 grid(g.kslices, co_blocks * g.ci_blocks);
-    EAS_LAUNCH(kern, grid, dim3(NT), lds, st, x, gy, slabs, g);
-    return EAS_OK;
+// The kernel instance of a layer: the template arguments of conv_wgrad_mfma_kernel as data (nit = the body's NIT, not NITX)
+struct WgInst { int s, xt, pm, pn, vec, nit; bool planes; };
+
+// staging items per thread of an instance (conv_wgrad_body NIT): one for the 12-wave blocks, else two, unless the instance names its own
+constexpr int wg_nit(int pm, int pn, int nitx) { return nitx ? nitx : (pm * pn == 4 ? 1 : 2); }
+
+// x_terms 1 or 3 (spike planes: 1 with planes set); pn and nitx are wg_geom's choices
+WgInst wg_inst(const WgGeom& g, int stride, int x_terms, bool planes, int pn, int nitx) {
+    WgInst in;
+    in.s = stride; in.xt = x_terms; in.planes = planes;
+    in.pm = g.Cout >= 64 ? 2 : 1;
+    in.pn = pn;
+    in.vec = (g.parts > 1 || (g.Wi % 4 == 0 && g.Wo % 4 == 0)) ? 4 : 2;      // staging units of 16 bytes, or 8 where a row is no multiple of 4 floats
+    in.nit = wg_nit(in.pm, pn, nitx);
+    return in;
 }
 
-// blocks of this kernel instance a CU holds at once with `lds` bytes of dynamic LDS (registers, waves and LDS all count), cached
-template <int S, int XT, int PM, int PN, int VEC, bool XPL = false, int NITX = 0>
-int resident_wgrad(size_t lds) {
-    static size_t seen[16];
-    static int val[16], n = 0;
-    for (int i = 0; i < n; ++i)
-        if (seen[i] == lds) return val[i];
-    auto kern = conv_wgrad_mfma_kernel<S, XT, PM, PN, VEC, XPL, NITX>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 192 * PM * PN, lds) != hipSuccess || nb < 1) nb = 1;
-    if (n < 16) { seen[n] = lds; val[n] = nb; ++n; }
-    return nb;
-}
-
-struct WgPlan { int pm, pn, kslices; };
-
-// block shape and number of pixel slices for a layer (shared by the workspace query and the launch)
-// pn = 2 (a block owns 64 input channels: grad_y is staged by half as many blocks) for spike inputs with >= 64 channels whenever the two
-// x planes fit LDS next to the grad_y tile (always at stride 1; at stride 2 on the small maps, where the layers with many channels
-// are bound by re-staging the same pixels from L2 in every (co, ci) block)
-WgPlan wg_plan(int Cin, int Cout, int stride, int x_terms, int ntiles, int parts, int pn, int resident = 0) {
-    WgPlan p;
-    p.pm = Cout >= 64 ? 2 : 1;
-    p.pn = pn;
-    const int yz = ((Cout + 32 * p.pm - 1) / (32 * p.pm)) * ((Cin + 32 * p.pn - 1) / (32 * p.pn));
-    // Pixel slices: every block walks ntiles / ks tiles and the launch takes ceil(ks * yz / slots) rounds of the chip's block slots
-    // (slots = 256 CUs x the blocks of THIS kernel instance a CU really holds: registers, waves and LDS -- 108 KB of double-buffered LDS
-    // leave one, where the old rule of thumb "4 / (pm pn)" assumed two and sized the grid for 512 slots: 2.25 rounds).  The slice count
-    // with the fewest tile periods wins; ties go to fewer slabs.  resident = 0: geometry search only (pm / pn are all it reads).
-    static const int slot_pct = eas_dev_env("EAS_WG_SLOT_PCT") ? atoi(eas_dev_env("EAS_WG_SLOT_PCT")) : 100;      // development: share of the chip a launch is sized for
-    const int slots = 256 * (resident > 0 ? resident : 1) * slot_pct / 100;
-    const int step = parts > 1 ? parts : 1;
-    int best = step;
-    static const double pen = eas_dev_env("EAS_WG_SHARE_PEN") ? atof(eas_dev_env("EAS_WG_SHARE_PEN")) : 0.0;      // development
-    const int res1 = resident > 0 ? resident : 1;
-    double best_cost = -1.0;
-    for (int ks = step; ks <= ntiles && (long)ks * yz <= 4L * slots; ks += step) {
-        const long blocks = (long)ks * yz;
-        const long rounds = (blocks + slots - 1) / slots;
-        // blocks that share a CU share its matrix cores: a tile period stretches by `pen` per co-resident block
-        long share = (blocks + 255) / 256;
-        if (share > res1) share = res1;
-        const double cost = (double)rounds * (double)((ntiles + ks - 1) / ks) * (1.0 + pen * (double)(share - 1));
-        if (best_cost < 0 || cost < best_cost - 1e-9) { best_cost = cost; best = ks; }
-    }
-    p.kslices = best;
-    return p;
+// what a tile needs of a block: LDS bytes (one or two buffers) and staging items against the items its threads can hold
+struct WgFit {
+    size_t lds;
+    int nitems, capacity;
+    bool ok() const { return lds <= kWgLdsMax && nitems <= capacity; }
+};
+WgFit wg_fit(const WgGeom& g, const WgInst& in, bool single) {
+    WgFit f;
+    f.lds = (size_t)(single ? 1 : 2) * (3 * in.pm * A_PLANE + (size_t)in.xt * in.pn * g.Q * ROWB);
+    // The kernel counts the 8-channel groups of x per block (its nbg: the last ci block of a layer stages only the groups that exist).  The
+    // host counts them for the whole layer: fewer than four only where the layer has ONE ci block of fewer than 32 channels, four per
+    // plane otherwise -- the block with the most items, which is the one that has to fit.
+    const int nbg = in.pn == 1 && g.Cin < 32 ? (g.Cin + 7) / 8 : 4 * in.pn;
+    f.nitems = (TP / in.vec) * 4 * in.pm + g.nseg * g.rows_in * (g.Wst / in.vec) * nbg;
+    f.capacity = in.nit * 192 * in.pm * in.pn;
+    return f;
 }
 
 // geometry of a layer cut into `parts` column parts per row (1 = whole rows), tile <= cap output pixels
@@ -665,28 +623,29 @@ bool wg_geom_cap(WgGeom& g, int NI, int Cin, int Cout, int Hi, int Wi, int strid
     return true;
 }
 
-// largest tile (<= 80 output pixels) whose double-buffered images and staging items fit the block; whole rows first, then 2, 4
-// and 8 column parts per row
-bool wg_geom(WgGeom& g, int NI, int Cin, int Cout, int Hi, int Wi, int stride, int x_terms) {
+// largest tile (<= 80 output pixels) whose double-buffered images and staging items fit the block, and the instance it runs on; whole
+// rows first, then 2, 4 and 8 column parts per row
+// pn = 2 (a block owns 64 input channels: grad_y is staged by half as many blocks) for spike inputs with >= 64 channels whenever the two
+// x planes fit LDS next to the grad_y tile (always at stride 1; at stride 2 on the small maps, where the layers with many channels
+// are bound by re-staging the same pixels from L2 in every (co, ci) block)
+bool wg_geom(WgGeom& g, WgInst& in, int NI, int Cin, int Cout, int Hi, int Wi, int stride, int x_terms, bool planes) {
     static const int force_parts = eas_dev_env("EAS_WG_PARTS") ? atoi(eas_dev_env("EAS_WG_PARTS")) : 0;      // development switch
     static const int pn2_s2 = eas_dev_env("EAS_WG_PN2_S2") ? atoi(eas_dev_env("EAS_WG_PN2_S2")) : 1;       // development switch
     for (int parts = force_parts > 0 ? force_parts : 1; parts <= 8; parts *= 2) {
         for (int cap = TP; cap >= 8; cap /= 2)
           for (int pn = (Cin >= 64 && x_terms == 1 && (stride == 1 || (pn2_s2 && cap == TP))) ? 2 : 1; pn >= 1; --pn) {
             if (!wg_geom_cap(g, NI, Cin, Cout, Hi, Wi, stride, cap, parts)) continue;
-            g.pn = pn;
-            const WgPlan p = wg_plan(Cin, Cout, stride, x_terms, g.ntiles, parts, pn);
-            const int vec = parts > 1 ? 4 : ((Wi % 4 == 0 && g.Wo % 4 == 0) ? 4 : 2);
-            const size_t lds = (size_t)2 * (3 * p.pm * A_PLANE + (size_t)x_terms * p.pn * g.Q * ROWB);
-            const int nbg = p.pn == 1 && Cin < 32 ? (Cin + 7) / 8 : 4 * p.pn;
-            const int nitems = (TP / vec) * 4 * p.pm + g.nseg * g.rows_in * (g.Wst / vec) * nbg;
-            const int nt = 192 * p.pm * p.pn;
-            g.nit = p.pm * p.pn == 4 ? 1 : 2;
-            if (lds <= 160 * 1024 && nitems <= g.nit * nt) return true;
+            in = wg_inst(g, stride, x_terms, planes, pn, 0);
+            bool ok = wg_fit(g, in, false).ok();
             // stride 2, spike inputs, 64-output-channel blocks: a third item per thread keeps the 80-pixel tile (dark5.0 at 16x20 -> 8x10: 1000
             // items for 384 threads; with two the tile shrank to 40 pixels -- half of every MFMA step on zeros, twice the barriers: 296 -> 199 us)
-            if (stride == 2 && x_terms == 1 && p.pm == 2 && p.pn == 1 && cap == TP && lds <= 160 * 1024 && nitems <= 3 * nt) {
-                g.nit = 3;
+            if (!ok && stride == 2 && x_terms == 1 && in.pm == 2 && pn == 1 && cap == TP) {
+                in = wg_inst(g, stride, x_terms, planes, pn, 3);
+                ok = wg_fit(g, in, false).ok();
+            }
+            if (ok) {
+                g.pn = in.pn;
+                g.nit = in.nit;
                 return true;
             }
         }
@@ -695,84 +654,185 @@ bool wg_geom(WgGeom& g, int NI, int Cin, int Cout, int Hi, int Wi, int stride, i
     return false;
 }
 
-// the plan of a layer whose geometry is fixed: block shape, then the residency of the kernel instance the launch will use, then slices
-WgPlan wg_plan_final(const WgGeom& g, int Cin, int Cout, int stride, int x_terms, bool planes, int& single) {
-    const WgPlan p0 = wg_plan(Cin, Cout, stride, x_terms, g.ntiles, g.parts, g.pn);
-    const size_t lds = (size_t)2 * (3 * p0.pm * A_PLANE + (size_t)x_terms * p0.pn * g.Q * ROWB);
-    const bool v4 = g.parts > 1 || (g.Wi % 4 == 0 && g.Wo % 4 == 0);
-    int res = 1;
-    if (g.nit == 3) {        // (wg_geom: stride 2, one term, pm 2, pn 1; never single-buffered)
-        res = planes ? (v4 ? resident_wgrad<2, 1, 2, 1, 4, true, 3>(lds) : resident_wgrad<2, 1, 2, 1, 2, true, 3>(lds))
-                     : (v4 ? resident_wgrad<2, 1, 2, 1, 4, false, 3>(lds) : resident_wgrad<2, 1, 2, 1, 2, false, 3>(lds));
-        single = 0;
-        return wg_plan(Cin, Cout, stride, x_terms, g.ntiles, g.parts, g.pn, res);
+// Whether a 3x3 problem has a kernel -- asked by the workspace and parts queries and by both launches, so a query says 0 exactly where a
+// launch refuses -- and if so its geometry and instance.  x_terms as in eas_conv_fwd (2: spike planes).
+int wg_support(WgGeom& g, WgInst& in, int NI, int Cin, int Cout, int Hi, int Wi, int stride, int x_terms) {
+    if (NI <= 0 || Cin <= 0 || Cout <= 0 || Hi <= 0 || Wi <= 0) return EAS_ERR_INVALID_ARG;
+    if (x_terms < 1 || x_terms > 3 || (stride != 1 && stride != 2)) return EAS_ERR_UNSUPPORTED;
+    // channels are staged in groups of eight, rows in units of two or four floats
+    if (Cin % 8 != 0 || Cout % 8 != 0 || Wi % 2 != 0) return EAS_ERR_UNSUPPORTED;
+    const bool planes = x_terms == 2;       // the geometry of one-term inputs
+    if (!wg_geom(g, in, NI, Cin, Cout, Hi, Wi, stride, planes ? 1 : x_terms, planes)) return EAS_ERR_UNSUPPORTED;
+    // grad_y is read in the same units: its rows start on 8 bytes, its channel planes on 16
+    if (g.Wo % 2 != 0 || (g.Ho * g.pitchY) % 4 != 0) return EAS_ERR_UNSUPPORTED;
+    if (in.xt == 1) {
+        // (the refusal the address comment of conv_wgrad_body speaks of) the spike-input instances address a tile's items as 32-bit byte offsets from the tile base in raw buffer loads whose descriptors say
+        // num_records = 2^31 (offsets from there on mean "outside: zeros"): the images of a tile plus the 8 channel rows of an item must stay
+        // below that (far above every EAS-SNN shape: a 64-channel 128x160 image is 5 MB)
+        const size_t img_y = (size_t)g.Cout * g.Ho * g.pitchY * 4, img_x = (size_t)g.Cin * g.Hi * g.pitchX * (planes ? 2 : 4);
+        const size_t span = (size_t)(g.nseg + 1) * (img_y > img_x ? img_y : img_x) + (size_t)8 * g.Hi * g.pitchX * 4;
+        if (span >= ((size_t)1 << 31)) return EAS_ERR_UNSUPPORTED;
     }
-#define EAS_RS(S_, XT_, PM_, PN_, PL_) (v4 ? resident_wgrad<S_, XT_, PM_, PN_, 4, PL_>(lds) : resident_wgrad<S_, XT_, PM_, PN_, 2, PL_>(lds))
-#define EAS_RS_SHAPE(S_, XT_, PL_)                                              \
-    do {                                                                        \
-        if (p0.pm == 2 && p0.pn == 2) res = EAS_RS(S_, XT_, 2, 2, PL_);         \
-        else if (p0.pm == 2) res = EAS_RS(S_, XT_, 2, 1, PL_);                  \
-        else if (p0.pn == 2) res = EAS_RS(S_, XT_, 1, 2, PL_);                  \
-        else res = EAS_RS(S_, XT_, 1, 1, PL_);                                  \
-    } while (0)
-    if (planes && stride == 1) EAS_RS_SHAPE(1, 1, true);
-    else if (planes) EAS_RS_SHAPE(2, 1, true);
-    else if (stride == 1 && x_terms == 1) EAS_RS_SHAPE(1, 1, false);
-    else if (stride == 1) EAS_RS_SHAPE(1, 3, false);
-    else if (x_terms == 1) EAS_RS_SHAPE(2, 1, false);
-    else EAS_RS_SHAPE(2, 3, false);
-#undef EAS_RS_SHAPE
-#undef EAS_RS
+    return EAS_OK;
+}
+
+// First use of a kernel: raises its dynamic-LDS limit (false: it could not be raised, the kernel cannot be launched)
+template <auto KERN>
+bool wg_raise_lds() {
+    static bool raised = false;
+    if (!raised) raised = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgLdsMax) == hipSuccess;
+    return raised;
+}
+
+// blocks of a kernel a CU holds at once with `lds` bytes of dynamic LDS (registers, waves and LDS all count; 1 when unknown), cached per
+// LDS size: the tile, and with it the LDS, depends on the layer
+template <auto KERN>
+int wg_resident(int threads, size_t lds) {
+    static size_t seen[16];
+    static int val[16], n = 0;
+    for (int i = 0; i < n; ++i)
+        if (seen[i] == lds) return val[i];
+    (void)wg_raise_lds<KERN>();
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)KERN, threads, lds) != hipSuccess || nb < 1) nb = 1;
+    if (n < 16) { seen[n] = lds; val[n] = nb; ++n; }
+    return nb;
+}
+
+struct WgCall {
+    const float* x;
+    const float* gy;
+    float* slabs;
+    WgGeom g;               // complete: kslices, single and ci_blocks set
+    WgInst in;
+    hipStream_t st;
+};
+
+// one instance of the single-layer kernel: its resident blocks per CU (c == NULL, for the plan) or its launch.  A call whose instance is
+// not this one is a wrong row of the ladder: it fails here, on the host, instead of reading a geometry the kernel was not built for
+template <int S, int XT, int PM, int PN, int VEC, bool XPL, int NITX>
+int wg_instance(const WgCall* c, size_t lds) {
+    constexpr auto kern = conv_wgrad_mfma_kernel<S, XT, PM, PN, VEC, XPL, NITX>;
+    constexpr int NT = 192 * PM * PN;
+    if (!c) return wg_resident<kern>(NT, lds);
+    const WgInst& in = c->in;
+    if (in.s != S || in.xt != XT || in.pm != PM || in.pn != PN || in.vec != VEC || in.planes != XPL || in.nit != wg_nit(PM, PN, NITX))
+        return EAS_ERR_LAUNCH;
+    if (!wg_raise_lds<kern>()) return EAS_ERR_LAUNCH;
+    dim3 grid(c->g.kslices, ((c->g.Cout + 32 * PM - 1) / (32 * PM)) * c->g.ci_blocks);
+    EAS_LAUNCH(kern, grid, dim3(NT), lds, c->st, c->x, c->gy, c->slabs, c->g);
+    return EAS_OK;
+}
+
+// The ladder: every instance the library holds.  pn = 2 exists for one-term inputs only (wg_geom), three items per thread only for the
+// stride-2 one-term 6-wave blocks.
+struct WgRow {
+    WgInst in;
+    int (*fn)(const WgCall*, size_t);
+};
+template <int S, int XT, int PM, int PN, int VEC, bool XPL = false, int NITX = 0>
+constexpr WgRow wg_row() {
+    return {{S, XT, PM, PN, VEC, wg_nit(PM, PN, NITX), XPL}, wg_instance<S, XT, PM, PN, VEC, XPL, NITX>};
+}
+const WgRow kWgLadder[] = {
+    // stride 1: one term, spike planes, three terms
+    wg_row<1, 1, 1, 1, 2>(), wg_row<1, 1, 1, 1, 4>(), wg_row<1, 1, 1, 2, 2>(), wg_row<1, 1, 1, 2, 4>(),
+    wg_row<1, 1, 2, 1, 2>(), wg_row<1, 1, 2, 1, 4>(), wg_row<1, 1, 2, 2, 2>(), wg_row<1, 1, 2, 2, 4>(),
+    wg_row<1, 1, 1, 1, 2, true>(), wg_row<1, 1, 1, 1, 4, true>(), wg_row<1, 1, 1, 2, 2, true>(), wg_row<1, 1, 1, 2, 4, true>(),
+    wg_row<1, 1, 2, 1, 2, true>(), wg_row<1, 1, 2, 1, 4, true>(), wg_row<1, 1, 2, 2, 2, true>(), wg_row<1, 1, 2, 2, 4, true>(),
+    wg_row<1, 3, 1, 1, 2>(), wg_row<1, 3, 1, 1, 4>(), wg_row<1, 3, 2, 1, 2>(), wg_row<1, 3, 2, 1, 4>(),
+    // stride 2
+    wg_row<2, 1, 1, 1, 2>(), wg_row<2, 1, 1, 1, 4>(), wg_row<2, 1, 1, 2, 2>(), wg_row<2, 1, 1, 2, 4>(),
+    wg_row<2, 1, 2, 1, 2>(), wg_row<2, 1, 2, 1, 4>(), wg_row<2, 1, 2, 2, 2>(), wg_row<2, 1, 2, 2, 4>(),
+    wg_row<2, 1, 1, 1, 2, true>(), wg_row<2, 1, 1, 1, 4, true>(), wg_row<2, 1, 1, 2, 2, true>(), wg_row<2, 1, 1, 2, 4, true>(),
+    wg_row<2, 1, 2, 1, 2, true>(), wg_row<2, 1, 2, 1, 4, true>(), wg_row<2, 1, 2, 2, 2, true>(), wg_row<2, 1, 2, 2, 4, true>(),
+    wg_row<2, 3, 1, 1, 2>(), wg_row<2, 3, 1, 1, 4>(), wg_row<2, 3, 2, 1, 2>(), wg_row<2, 3, 2, 1, 4>(),
+    // stride 2, one term, 6-wave blocks with three items per thread.  8-byte units only: in 16-byte units the x patch of an 80-pixel tile
+    // (at most six input pixels per output pixel) never needs a third item -- no shape selects such an instance
+    wg_row<2, 1, 2, 1, 2, false, 3>(), wg_row<2, 1, 2, 1, 2, true, 3>(),
+};
+
+// the instance of a descriptor: its resident blocks per CU (c == NULL) or its launch; a descriptor the ladder does not list has no kernel
+int wg_select(const WgInst& in, const WgCall* c, size_t lds) {
+    for (const WgRow& r : kWgLadder)
+        if (r.in.s == in.s && r.in.xt == in.xt && r.in.pm == in.pm && r.in.pn == in.pn && r.in.vec == in.vec && r.in.nit == in.nit &&
+            r.in.planes == in.planes)
+            return r.fn(c, lds);
+    return EAS_ERR_UNSUPPORTED;
+}
+
+// block slots of the chip a launch is sized for: 256 CUs x the blocks of the kernel instance a CU really holds
+long wg_slots(int resident) {
+    static const int slot_pct = eas_dev_env("EAS_WG_SLOT_PCT") ? atoi(eas_dev_env("EAS_WG_SLOT_PCT")) : 100;      // development: share of the chip a launch is sized for
+    return 256L * resident * slot_pct / 100;
+}
+
+// number of pixel slices for a layer whose instance holds `resident` blocks per CU
+int wg_slices(const WgGeom& g, const WgInst& in, int resident) {
+    const int yz = ((g.Cout + 32 * in.pm - 1) / (32 * in.pm)) * ((g.Cin + 32 * in.pn - 1) / (32 * in.pn));
+    // Pixel slices: every block walks ntiles / ks tiles and the launch takes ceil(ks * yz / slots) rounds of the chip's block slots
+    // (slots = 256 CUs x the blocks of THIS kernel instance a CU really holds: registers, waves and LDS -- 108 KB of double-buffered LDS
+    // leave one, where the old rule of thumb "4 / (pm pn)" assumed two and sized the grid for 512 slots: 2.25 rounds).  The slice count
+    // with the fewest tile periods wins; ties go to fewer slabs.
+    const long slots = wg_slots(resident);
+    const int step = g.parts > 1 ? g.parts : 1;
+    int best = step;
+    static const double pen = eas_dev_env("EAS_WG_SHARE_PEN") ? atof(eas_dev_env("EAS_WG_SHARE_PEN")) : 0.0;      // development
+    double best_cost = -1.0;
+    for (int ks = step; ks <= g.ntiles && (long)ks * yz <= 4L * slots; ks += step) {
+        const long blocks = (long)ks * yz;
+        const long rounds = (blocks + slots - 1) / slots;
+        // blocks that share a CU share its matrix cores: a tile period stretches by `pen` per co-resident block
+        long share = (blocks + 255) / 256;
+        if (share > resident) share = resident;
+        const double cost = (double)rounds * (double)((g.ntiles + ks - 1) / ks) * (1.0 + pen * (double)(share - 1));
+        if (best_cost < 0 || cost < best_cost - 1e-9) { best_cost = cost; best = ks; }
+    }
+    return best;
+}
+
+struct WgPlan { int kslices, single; };      // kslices 0: the ladder has no such instance
+
+// the plan of a supported layer (shared by the workspace query and the launch): the residency of the kernel instance the launch will
+// use, one LDS buffer or two, then slices
+WgPlan wg_plan(const WgGeom& g, const WgInst& in) {
+    const size_t lds = wg_fit(g, in, false).lds;
+    int res = wg_select(in, nullptr, lds);
+    if (res < 1) return {0, 0};
     // single-buffered LDS where the double-buffered tile leaves ONE block per CU and half of it two: the second block overlaps everything
     // the first one waits for, which a second buffer inside one 6- or 12-wave block cannot (a tile's write is exposed instead: +15 %)
     static const int single_env = eas_dev_env("EAS_WG_SINGLE") ? atoi(eas_dev_env("EAS_WG_SINGLE")) : -1;      // development: 0 never, 1 whenever it fits twice
-    single = 0;
+    int single = 0;
     static const int single_cap = eas_dev_env("EAS_WG_SINGLE_CAP") ? atoi(eas_dev_env("EAS_WG_SINGLE_CAP")) : 2;       // development
     // (measured: 3-wave blocks -- layers of fewer than 64 output channels on the big maps -- gain 20-30 %: real-input 48 -> 48 channels at
     // 64x80 699 -> 496 us; 6- and 12-wave blocks lose 5-8 %: they already keep the SIMDs' issue slots busy and the exposed write costs more)
-    if (single_env != 0 && res == 1 && (p0.pm * p0.pn == 1 || single_env == 1)) {
-        const size_t lds1 = lds / 2;
-        int res1 = 1;
-#define EAS_RS(S_, XT_, PM_, PN_, PL_) (v4 ? resident_wgrad<S_, XT_, PM_, PN_, 4, PL_>(lds1) : resident_wgrad<S_, XT_, PM_, PN_, 2, PL_>(lds1))
-#define EAS_RS_SHAPE(S_, XT_, PL_)                                              \
-    do {                                                                        \
-        if (p0.pm == 2 && p0.pn == 2) res1 = EAS_RS(S_, XT_, 2, 2, PL_);        \
-        else if (p0.pm == 2) res1 = EAS_RS(S_, XT_, 2, 1, PL_);                 \
-        else if (p0.pn == 2) res1 = EAS_RS(S_, XT_, 1, 2, PL_);                 \
-        else res1 = EAS_RS(S_, XT_, 1, 1, PL_);                                 \
-    } while (0)
-        if (planes && stride == 1) EAS_RS_SHAPE(1, 1, true);
-        else if (planes) EAS_RS_SHAPE(2, 1, true);
-        else if (stride == 1 && x_terms == 1) EAS_RS_SHAPE(1, 1, false);
-        else if (stride == 1) EAS_RS_SHAPE(1, 3, false);
-        else if (x_terms == 1) EAS_RS_SHAPE(2, 1, false);
-        else EAS_RS_SHAPE(2, 3, false);
-#undef EAS_RS_SHAPE
-#undef EAS_RS
+    // (never the three-item instances)
+    if (single_env != 0 && res == 1 && in.nit != 3 && (in.pm * in.pn == 1 || single_env == 1)) {
+        const int res1 = wg_select(in, nullptr, wg_fit(g, in, true).lds);
         if (res1 >= 2) {
             single = 1;
             res = res1 > single_cap ? single_cap : res1;
         }
     }
-    return wg_plan(Cin, Cout, stride, x_terms, g.ntiles, g.parts, g.pn, res);
+    return {wg_slices(g, in, res), single};
 }
 
 // ---- grouped launch: plan.  Every layer keeps its own (co, ci) blocks; the pixel slices of ALL layers are sized together: a common
-// number of tiles per block tau, slices_p = ceil(ntiles_p / tau), chosen like wg_plan chooses a layer's -- the fewest tile periods
+// number of tiles per block tau, slices_p = ceil(ntiles_p / tau), chosen like wg_slices chooses a layer's -- the fewest tile periods
 // (rounds of the chip's block slots x tau), ties to the larger tau (fewer slabs).  A layer alone needs its slices to fill 256 CUs by
 // itself (512 slabs for a 128 -> 128 layer on 32x40 maps); in a group the other layers' blocks fill them.
-template <int XT, int PM, int PN>
-int resident_wgrad_group(size_t lds) {
-    static size_t seen[8];
-    static int val[8], n = 0;
-    for (int i = 0; i < n; ++i)
-        if (seen[i] == lds) return val[i];
-    auto kern = conv_wgrad_group_kernel<XT, PM, PN>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 192 * PM * PN, lds) != hipSuccess || nb < 1) nb = 1;
-    if (n < 8) { seen[n] = lds; val[n] = nb; ++n; }
-    return nb;
+
+// one instance of the grouped kernel (three-term x, pn = 1): its resident blocks per CU (a == NULL) or its launch
+template <int PM>
+int wg_group_instance(const WgGroupArgs* a, int blocks, size_t lds, hipStream_t st) {
+    constexpr auto kern = conv_wgrad_group_kernel<3, PM, 1>;
+    if (!a) return wg_resident<kern>(192 * PM, lds);
+    if (!wg_raise_lds<kern>()) return EAS_ERR_LAUNCH;
+    EAS_LAUNCH(kern, dim3(blocks), dim3(192 * PM), lds, st, *a);
+    return EAS_OK;
+}
+int wg_group_select(int pm, const WgGroupArgs* a, int blocks, size_t lds, hipStream_t st) {
+    return pm == 2 ? wg_group_instance<2>(a, blocks, lds, st) : wg_group_instance<1>(a, blocks, lds, st);
 }
 
 // tau for block counts yz[p] and tile counts nt[p]
@@ -796,27 +856,27 @@ int wgrad_group3(const EasWgradProblem* pr, int n, int x_terms, hipStream_t st, 
     WgGroupArgs a{};
     int yz[kMaxWgGroup], nt[kMaxWgGroup];
     size_t lds = 0;
-    const int pm = pr[0].Cout >= 64 ? 2 : 1;
+    int pm = 0;
     for (int p = 0; p < n; ++p) {
         const EasWgradProblem& q = pr[p];
-        if (q.NI <= 0 || q.Cin <= 0 || q.Cout <= 0 || q.Hi <= 0 || q.Wi <= 0) return EAS_ERR_INVALID_ARG;
         if (!query && (!q.x || !q.grad_y || !q.workspace)) return EAS_ERR_INVALID_ARG;
-        if (q.Cin % 8 != 0 || q.Cout % 8 != 0 || q.Wi % 2 != 0 || (q.Cout >= 64 ? 2 : 1) != pm) return EAS_ERR_UNSUPPORTED;
         WgGeom& g = a.g[p];
-        if (!wg_geom(g, q.NI, q.Cin, q.Cout, q.Hi, q.Wi, 1, x_terms) || g.parts != 1 || g.pn != 1) return EAS_ERR_UNSUPPORTED;
-        if (g.Wo % 2 != 0 || (g.Ho * g.pitchY) % 4 != 0) return EAS_ERR_UNSUPPORTED;
-        a.vec2[p] = (g.Wi % 4 == 0 && g.Wo % 4 == 0) ? 0 : 1;
-        const size_t l = (size_t)2 * (3 * pm * A_PLANE + (size_t)x_terms * g.Q * ROWB);
+        WgInst in;
+        const int rc = wg_support(g, in, q.NI, q.Cin, q.Cout, q.Hi, q.Wi, 1, x_terms);
+        if (rc != EAS_OK) return rc;
+        // one kernel for the group: whole-row tiles, one block shape
+        if (p == 0) pm = in.pm;
+        if (g.parts != 1 || in.pn != 1 || in.pm != pm) return EAS_ERR_UNSUPPORTED;
+        a.vec2[p] = in.vec == 2;
+        const size_t l = wg_fit(g, in, false).lds;
         lds = l > lds ? l : lds;
         g.ci_blocks = (g.Cin + 31) / 32;
         yz[p] = ((g.Cout + 32 * pm - 1) / (32 * pm)) * g.ci_blocks;
         nt[p] = g.ntiles;
         a.x[p] = (const float*)q.x; a.gy[p] = q.grad_y; a.slabs[p] = q.workspace;
     }
-    if (lds > 160 * 1024) return EAS_ERR_UNSUPPORTED;
-    const int res = pm == 2 ? resident_wgrad_group<3, 2, 1>(lds) : resident_wgrad_group<3, 1, 1>(lds);
-    static const int slot_pct_g = eas_dev_env("EAS_WG_SLOT_PCT") ? atoi(eas_dev_env("EAS_WG_SLOT_PCT")) : 100;      // development (wg_plan)
-    const int tau = group_tau(yz, nt, n, 256L * res * slot_pct_g / 100);
+    const int res = wg_group_select(pm, nullptr, 0, lds, st);
+    const int tau = group_tau(yz, nt, n, wg_slots(res));
     int blocks = 0;
     for (int p = 0; p < n; ++p) {
         a.g[p].kslices = (nt[p] + tau - 1) / tau;
@@ -828,9 +888,7 @@ int wgrad_group3(const EasWgradProblem* pr, int n, int x_terms, hipStream_t st, 
     a.first[n] = blocks;
     a.n = n;
     if (query) return EAS_OK;
-    if (pm == 2) EAS_LAUNCH((conv_wgrad_group_kernel<3, 2, 1>), dim3(blocks), dim3(384), lds, st, a);
-    else EAS_LAUNCH((conv_wgrad_group_kernel<3, 1, 1>), dim3(blocks), dim3(192), lds, st, a);
-    return EAS_OK;
+    return wg_group_select(pm, &a, blocks, lds, st);
 }
 
 }  // namespace
@@ -843,22 +901,23 @@ int eas_conv1x1_wgrad_dispatch(const void* x, const float* gy, float* slabs, int
 extern "C" {
 
 int64_t eas_conv_wgrad_workspace_floats(int NI, int Cin, int Cout, int Hi, int Wi, int ksize, int stride, int x_terms) {
-    const bool planes = x_terms == 2;
-    if (planes) x_terms = 1;                // spike planes: the geometry of one-term inputs
-    if (ksize == 1) return stride == 1 ? (int64_t)eas_conv1x1_wgrad_slices(NI, Cin, Cout, Hi * Wi, x_terms, planes ? 1 : 0) * Cout * Cin : 0;
+    if (ksize == 1) {
+        const bool planes = x_terms == 2;       // spike planes: the geometry of one-term inputs
+        return stride == 1 ? (int64_t)eas_conv1x1_wgrad_slices(NI, Cin, Cout, Hi * Wi, planes ? 1 : x_terms, planes ? 1 : 0) * Cout * Cin : 0;
+    }
     if (ksize != 3) return 0;
     WgGeom g{};
-    if (!wg_geom(g, NI, Cin, Cout, Hi, Wi, stride, x_terms)) return 0;
-    int single = 0;
-    return (int64_t)wg_plan_final(g, Cin, Cout, stride, x_terms, planes, single).kslices * Cout * Cin * 9;
+    WgInst in;
+    if (wg_support(g, in, NI, Cin, Cout, Hi, Wi, stride, x_terms) != EAS_OK) return 0;
+    return (int64_t)wg_plan(g, in).kslices * Cout * Cin * 9;
 }
 
 // number of column parts per row eas_conv_wgrad uses for a 3x3 layer: 1 = whole rows fit one reduction tile, 2..8 = column parts
 // (same kernel, one launch), 0 = unsupported
 int eas_conv_wgrad_parts(int NI, int Cin, int Cout, int Hi, int Wi, int stride, int x_terms) {
-    if (x_terms == 2) x_terms = 1;
     WgGeom g{};
-    return wg_geom(g, NI, Cin, Cout, Hi, Wi, stride, x_terms) ? g.parts : 0;
+    WgInst in;
+    return wg_support(g, in, NI, Cin, Cout, Hi, Wi, stride, x_terms) == EAS_OK ? g.parts : 0;
 }
 
 // grad_w[Cout][Cin][3][3] of a 3x3 convolution (padding 1, stride 1 or 2) from x[NI][Cin][Hi][Wi] and grad_y[NI][Cout][Ho][Wo].
@@ -880,43 +939,26 @@ static int wgrad_partial(const float* x, const float* grad_y, float* workspace, 
         EAS_CHECK_LAUNCH();
         return slices;
     }
-    if (ksize != 3 || (stride != 1 && stride != 2) || Cin % 8 != 0 || Cout % 8 != 0 || Wi % 2 != 0) return EAS_ERR_UNSUPPORTED;
+    if (ksize != 3) return EAS_ERR_UNSUPPORTED;
     EAS_CLEAR_ERR();
-    WgGeom g{};
-    if (!wg_geom(g, NI, Cin, Cout, Hi, Wi, stride, x_terms)) return EAS_ERR_UNSUPPORTED;
-    if (g.Wo % 2 != 0 || (g.Ho * g.pitchY) % 4 != 0) return EAS_ERR_UNSUPPORTED;
-    int single = 0;
-    const WgPlan p = wg_plan_final(g, Cin, Cout, stride, x_terms, planes, single);
-    g.kslices = p.kslices;
-    g.single = single;
-    const int slabs = p.kslices;
-    hipStream_t st = eas_s(stream);
-    const int n = Cout * Cin * 9;
-    int rc = EAS_ERR_UNSUPPORTED;
-    const bool v4 = g.parts > 1 || (g.Wi % 4 == 0 && g.Wo % 4 == 0);
-#define EAS_WG(S_, XT_, PM_, PN_, PL_) (v4 ? launch_wgrad<S_, XT_, PM_, PN_, 4, PL_>(x, grad_y, workspace, g, st) : launch_wgrad<S_, XT_, PM_, PN_, 2, PL_>(x, grad_y, workspace, g, st))
-#define EAS_WG_SHAPE(S_, XT_, PL_)                                             \
-    do {                                                                       \
-        if (p.pm == 2 && p.pn == 2) rc = EAS_WG(S_, XT_, 2, 2, PL_);           \
-        else if (p.pm == 2) rc = EAS_WG(S_, XT_, 2, 1, PL_);                   \
-        else if (p.pn == 2) rc = EAS_WG(S_, XT_, 1, 2, PL_);                   \
-        else rc = EAS_WG(S_, XT_, 1, 1, PL_);                                  \
-    } while (0)
-    if (g.nit == 3)
-        rc = planes ? (v4 ? launch_wgrad<2, 1, 2, 1, 4, true, 3>(x, grad_y, workspace, g, st) : launch_wgrad<2, 1, 2, 1, 2, true, 3>(x, grad_y, workspace, g, st))
-                    : (v4 ? launch_wgrad<2, 1, 2, 1, 4, false, 3>(x, grad_y, workspace, g, st) : launch_wgrad<2, 1, 2, 1, 2, false, 3>(x, grad_y, workspace, g, st));
-    else if (planes && stride == 1) EAS_WG_SHAPE(1, 1, true);
-    else if (planes) EAS_WG_SHAPE(2, 1, true);
-    else if (stride == 1 && x_terms == 1) EAS_WG_SHAPE(1, 1, false);
-    else if (stride == 1) EAS_WG_SHAPE(1, 3, false);
-    else if (x_terms == 1) EAS_WG_SHAPE(2, 1, false);
-    else EAS_WG_SHAPE(2, 3, false);
-#undef EAS_WG_SHAPE
-#undef EAS_WG
+    WgCall c{x, grad_y, workspace, {}, {}, eas_s(stream)};
+    const int rc = wg_support(c.g, c.in, NI, Cin, Cout, Hi, Wi, stride, planes ? 2 : x_terms);
     if (rc != EAS_OK) return rc;
+    const WgPlan p = wg_plan(c.g, c.in);
+    if (p.kslices < 1) return EAS_ERR_UNSUPPORTED;
+    c.g.kslices = p.kslices;
+    c.g.single = p.single;
+    c.g.ci_blocks = (Cin + 32 * c.in.pn - 1) / (32 * c.in.pn);
+    const WgFit f = wg_fit(c.g, c.in, p.single != 0);
+    if (!f.ok()) {
+        if (eas_dev_env("EAS_CONV_DBG"))
+            fprintf(stderr, "wgrad launch: lds %zu nitems %d of %d PM %d PN %d VEC %d RT %d Q %d\n", f.lds, f.nitems, f.capacity, c.in.pm, c.in.pn, c.in.vec, c.g.RT, c.g.Q);
+        return EAS_ERR_UNSUPPORTED;
+    }
+    const int rcl = wg_select(c.in, &c, f.lds);
+    if (rcl != EAS_OK) return rcl;
     EAS_CHECK_LAUNCH();
-    (void)n;
-    return slabs;
+    return p.kslices;
 }
 
 int eas_conv_wgrad(const float* x, const float* grad_y, float* grad_w, float* workspace, int NI, int Cin, int Cout, int Hi, int Wi, int ksize,

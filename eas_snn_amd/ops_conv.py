@@ -550,8 +550,8 @@ def conv_route(x_shape, Cout, k, stride, x_terms):
             dgrad = None
         if dgrad and not L.eas_conv_fwd_supported(NI, Cout, Cin, Ho, Wo + (2 if dgrad == 2 else 0), k, 1, 3):
             dgrad = None
-        wgrad = L.eas_conv_wgrad_workspace_floats(*key) > 0 and (k == 1 or (Cout % 8 == 0 and Wo % 2 == 0 and (Ho * Wo) % 4 == 0))
-        r = _ROUTES[key] = ConvRoute(Ho, Wo, bool(L.eas_conv_fwd_supported(*key)), dgrad, bool(wgrad))
+        wgrad = L.eas_conv_wgrad_workspace_floats(*key) > 0         # 0: eas_conv_wgrad would refuse
+        r = _ROUTES[key] = ConvRoute(Ho, Wo, bool(L.eas_conv_fwd_supported(*key)), dgrad, wgrad)
     return r
 
 

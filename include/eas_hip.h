@@ -515,10 +515,12 @@ int eas_conv_dgrad_small(const float* grad_y, const float* w, float* grad_x, int
  * grad_y[NI][Cout][Ho][Wo] (ATen convolution_backward, weight part).  Reduction over output pixels on the matrix
  * cores (csrc/conv_wgrad_mfma.hip): grad_y as three exact bf16 terms, x as one (x_terms = 1, spikes / small integers)
  * or three; per-block partial sums are reduced in fixed order through `workspace`
- * (eas_conv_wgrad_workspace_floats(...) floats) -- deterministic. */
+ * (eas_conv_wgrad_workspace_floats(...) floats) -- deterministic.
+ * eas_conv_wgrad_workspace_floats: 0 = eas_conv_wgrad (and the *_partial forms) would refuse this problem with EAS_ERR_UNSUPPORTED --
+ * the query and the launch ask the same rule (3x3: Cin, Cout multiples of 8, even Wi and Wo, Ho * Wo a multiple of 4, a tile that fits). */
 int64_t eas_conv_wgrad_workspace_floats(int NI, int Cin, int Cout, int Hi, int Wi, int ksize, int stride, int x_terms);
 /* number of column parts per row eas_conv_wgrad uses for a 3x3 layer: 1 = whole rows fit one reduction tile, 2..8 = column parts
- * (same kernel, one launch), 0 = unsupported. */
+ * (same kernel, one launch), 0 = the launch would refuse (exactly where eas_conv_wgrad_workspace_floats says 0). */
 int eas_conv_wgrad_parts(int NI, int Cin, int Cout, int Hi, int Wi, int stride, int x_terms);
 int eas_conv_wgrad(const float* x, const float* grad_y, float* grad_w, float* workspace, int NI, int Cin, int Cout, int Hi,
                    int Wi, int ksize, int stride, int x_terms, eas_stream_t stream);

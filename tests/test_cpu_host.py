@@ -41,6 +41,29 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert lib.eas_bn_workspace_doubles(32) > 0 and lib.eas_reduce_workspace_floats(1 << 20) > 0
 
 
+def test_weight_gradient_queries_say_zero_where_the_launch_refuses():
+    """eas_conv_wgrad_workspace_floats and eas_conv_wgrad_parts ask the rule eas_conv_wgrad launches by (conv_wgrad_mfma.hip wg_support;
+    the queries need no GPU: an instance then counts as one resident block per CU): 0 for 3x3 problems it refuses -- output channels or input
+    channels that are no multiple of 8, an odd input width, an odd output width (6 columns at stride 2), and the two 3x3 rows of CONV_CASES
+    the GPU test names as the library's (Cout = 5; Ho * Wo = 30, no multiple of 4) -- and a plan for every other 3x3 row of the
+    fp64-compared GPU cases, in each input form the row's shape allows."""
+    from test_gpu_kernels import CONV_CASES, WGRAD_INSTANCE_CASES, WGRAD_LIBRARY_CASES
+    lib = eas_snn_amd.hip_library()
+    refused = [(2, 16, 5, 8, 10, 1), (2, 12, 16, 8, 10, 1), (2, 16, 16, 8, 9, 1), (2, 16, 16, 8, 6, 2)]
+    refused += [(NI, Cin, Cout, H, W, s) for NI, Cin, Cout, H, W, k, s, _ in WGRAD_LIBRARY_CASES]
+    for NI, Cin, Cout, H, W, s in refused:
+        for xt in (1, 2, 3):
+            assert lib.eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, 3, s, xt) == 0, (NI, Cin, Cout, H, W, s, xt)
+            assert lib.eas_conv_wgrad_parts(NI, Cin, Cout, H, W, s, xt) == 0, (NI, Cin, Cout, H, W, s, xt)
+    rows = [c for c in CONV_CASES + WGRAD_INSTANCE_CASES if c[5] == 3 and c not in WGRAD_LIBRARY_CASES]
+    assert len(rows) >= 30 and all(c[5] == 3 for c in WGRAD_LIBRARY_CASES)
+    for NI, Cin, Cout, H, W, k, s, spikes in rows:
+        for xt in ((1, 2) if spikes else (3,)):
+            floats = lib.eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, 3, s, xt)
+            assert floats > 0 and floats % (Cout * Cin * 9) == 0, (NI, Cin, Cout, H, W, s, xt)
+            assert 1 <= lib.eas_conv_wgrad_parts(NI, Cin, Cout, H, W, s, xt) <= 8, (NI, Cin, Cout, H, W, s, xt)
+
+
 def test_gfx950_code_object_only():
     out = subprocess.run(['/opt/rocm/lib/llvm/bin/clang-offload-bundler', '--list', '--type=o',
                           f'--input={eas_snn_amd._lib.LIB_PATH}'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout

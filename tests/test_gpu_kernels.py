@@ -1249,10 +1249,20 @@ CONV_CASES = [  # NI, Cin, Cout, H, W, k, stride, spikes
     (2, 64, 64, 8, 320, 3, 2, True),
     # single-buffered LDS forms: 3-wave weight-gradient blocks whose double-buffered tile fills the LDS; real-input forward with 2 / 3 chunks
     (2, 48, 48, 64, 80, 3, 1, False), (2, 48, 96, 32, 160, 3, 2, False), (2, 32, 64, 64, 160, 3, 2, False)]
+# 3x3 rows of CONV_CASES whose weight gradient has no kernel of its own (eas_conv_wgrad_workspace_floats says 0, the library convolution
+# computes it): Cout is no multiple of 8; Ho * Wo = 5 * 6 is no multiple of 4
+WGRAD_LIBRARY_CASES = [(1, 8, 5, 7, 10, 3, 1, False), (3, 40, 72, 10, 12, 3, 2, False)]
+# The smallest shapes that select the instances of the 3x3 weight-gradient ladder (conv_wgrad_mfma.hip kWgLadder) no row above reaches, as
+# (stride, x terms, co tiles, ci tiles, staging unit in floats): (1,1,1,2,2) (1,1,2,1,2) (1,3,2,1,2) (2,1,1,1,2) (2,3,1,1,2) (2,1,1,1,4)
+# (2,1,1,2,4) (2,1,2,1,2); at stride 2 two ci tiles fit an 8-byte-unit block only on tiles of very few rows: (2,1,1,2,2) (2,1,2,2,2)
+WGRAD_INSTANCE_CASES = [
+    (2, 64, 32, 8, 10, 3, 1, True), (2, 32, 64, 8, 10, 3, 1, True), (2, 32, 64, 8, 10, 3, 1, False), (2, 16, 32, 8, 12, 3, 2, True),
+    (2, 16, 32, 8, 12, 3, 2, False), (2, 16, 32, 8, 16, 3, 2, True), (2, 64, 32, 8, 16, 3, 2, True), (2, 16, 64, 8, 12, 3, 2, True),
+    (1, 64, 16, 28, 28, 3, 2, True), (1, 64, 64, 68, 12, 3, 2, True)]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('NI,Cin,Cout,H,W,k,s,spikes', CONV_CASES)
+@pytest.mark.parametrize('NI,Cin,Cout,H,W,k,s,spikes', CONV_CASES + WGRAD_INSTANCE_CASES)
 def test_conv_mfma_forward_dgrad_wgrad_vs_fp64(dev, NI, Cin, Cout, H, W, k, s, spikes):
     """The bf16-term MFMA convolutions against an fp64 convolution: forward, input gradient and weight gradient through
     the autograd wrapper (the same entry the model uses).  Tolerance: 1e-5 of the largest magnitude -- fp32-class accuracy
@@ -1265,9 +1275,11 @@ def test_conv_mfma_forward_dgrad_wgrad_vs_fp64(dev, NI, Cin, Cout, H, W, k, s, s
         conv.weight.copy_(w)
     xd = x.to(dev).requires_grad_(True)
     assert ops.conv_eligible(xd, conv)
-    if k == 3 and Cout % 8 == 0:          # the weight gradient of these runs on the own kernel too (no library fallback)
+    if k == 3:          # the weight gradient runs on the own kernel too (no library fallback) except where the query says it has none
         from eas_snn_amd import _lib
-        assert _lib.lib().eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, k, s, 1 if spikes else 3) > 0
+        own = _lib.lib().eas_conv_wgrad_workspace_floats(NI, Cin, Cout, H, W, k, s, 1 if spikes else 3) > 0
+        assert own == ((NI, Cin, Cout, H, W, k, s, spikes) not in WGRAD_LIBRARY_CASES)
+        assert ops.conv_route(xd.shape, Cout, k, s, 1 if spikes else 3).wgrad == own
     y = ops.conv2d(xd, conv, small_int=spikes)
     gy = torch.randn(y.shape, generator=torch.Generator().manual_seed(7))
     y.backward(gy.to(dev))
@@ -1889,7 +1901,16 @@ def test_prediction_conv_input_gradient_on_own_kernel(dev, Cout, H, W):
                                                            (5, 1, 128, 256, 4, 8, 1, 1, False), (3, 2, 256, 512, 8, 10, 1, 1, True),
                                                            (3, 2, 32, 64, 16, 20, 3, 1, True), (3, 4, 64, 64, 8, 12, 3, 1, False),
                                                            (3, 2, 64, 128, 16, 24, 3, 2, True), (2, 3, 72, 40, 12, 16, 3, 1, False),
-                                                           (3, 2, 200, 96, 8, 12, 1, 1, False)])
+                                                           (3, 2, 200, 96, 8, 12, 1, 1, False),
+                                                           # the spike-plane instances of the 3x3 weight-gradient ladder the rows above do not reach
+                                                           # (the shapes of WGRAD_INSTANCE_CASES and their 16-byte-unit neighbours)
+                                                           (2, 1, 16, 32, 8, 10, 3, 1, False), (2, 1, 16, 32, 8, 12, 3, 1, True),
+                                                           (2, 1, 64, 32, 8, 10, 3, 1, False), (2, 1, 32, 64, 8, 10, 3, 1, True),
+                                                           (2, 1, 64, 64, 8, 10, 3, 1, False), (2, 1, 16, 32, 8, 12, 3, 2, True),
+                                                           (2, 1, 16, 32, 8, 16, 3, 2, False), (2, 1, 64, 16, 28, 28, 3, 2, True),
+                                                           (2, 1, 64, 32, 8, 16, 3, 2, False), (2, 1, 16, 64, 8, 12, 3, 2, True),
+                                                           (2, 1, 32, 64, 8, 16, 3, 2, False), (2, 1, 64, 64, 68, 12, 3, 2, True),
+                                                           (2, 1, 32, 64, 8, 12, 3, 2, False)])
 def test_spike_planes_feed_the_convolutions_bit_identically(dev, T, N, Cin, Cout, H, W, k, stride, sew):
     """A convolution that reads its input as bf16 spike planes (eas_conv_fwd_planes) and its weight gradient
     (eas_conv_wgrad_planes_partial) give exactly the results of the fp32 route on the same spikes: y, the batch statistics the forward
@@ -2225,7 +2246,7 @@ def test_grouped_prediction_convolutions_bias_ragged_channels_and_accumulation(d
 
 
 @pytest.mark.parametrize('batch', [2, 64])
-@pytest.mark.parametrize('k,cin,cout', [(3, 128, 256), (3, 128, 128), (1, 128, 128), (1, 128, 4)])
+@pytest.mark.parametrize('k,cin,cout', [(3, 128, 256), (3, 128, 128), (1, 128, 128), (1, 128, 4), (3, 32, 32)])      # (3, 32, 32): the 3-wave grouped kernel
 def test_grouped_weight_gradient_slabs_vs_fp64(dev, batch, k, cin, cout):
     """eas_conv_wgrad_group_partial: the slab kernels of several layers as one grid, pixel slices sized for the group; reduced in fixed
     order like every weight gradient.  Against fp64 (1e-5 of the largest magnitude) and repeatable bit for bit."""
