@@ -12,6 +12,9 @@
 // for backward: h_t is recomputed in registers from y (T <= 8).
 #include <stdlib.h>
 
+#include <string.h>
+
+#include "bn_lif_policy.h"
 #include "eas_common.h"
 
 namespace {
@@ -290,7 +293,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_fwd_sp_kernel(const float* _
 
 // ------------------------------------------------------------------------------------------------ backward
 // Recompute h_t from y, then walk the LIF backward: dz[t] = dL/dz_t (z = BN output), dk += dL/dk.
-template <int T_, bool HARD, bool DI, bool STRICT>
+// POL (bn_lif_policy.h): a fast policy fixes the surrogate and the reset form at compile time (detach / sg_id are then not read); the
+// generic policy takes them from the arguments at every step.
+template <int T_, bool HARD, bool DI, bool STRICT, class POL>
 __device__ __forceinline__ void recompute_dz(const float (&yv)[T_], const float (&gs)[T_], float v0, float scale,
                                              float shift, float k, float omk, const EasLifParams& p, bool detach,
                                              int sg_id, float alpha, float (&dz)[T_], float& dk, float& da) {
@@ -307,14 +312,21 @@ __device__ __forceinline__ void recompute_dz(const float (&yv)[T_], const float 
 #pragma unroll
     for (int t = T_ - 1; t >= 0; --t) {
         float dkt, gx;
-        eas_lif_step_bwd<HARD, DI, STRICT>(gs[t], gv, h[t], vprev[t], z[t], k, omk, p.v_th, p.v_reset, detach, sg_id,
-                                           alpha, dkt, gx, da);
+        if constexpr (POL::fast)
+            eas_lif_step_bwd_ct<HARD, DI, STRICT, POL::sg, POL::detach>(gs[t], gv, h[t], vprev[t], z[t], k, omk, p.v_th, p.v_reset, alpha, dkt,
+                                                                        gx, da);
+        else
+            eas_lif_step_bwd<HARD, DI, STRICT>(gs[t], gv, h[t], vprev[t], z[t], k, omk, p.v_th, p.v_reset, detach, sg_id, alpha, dkt, gx, da);
         dz[t] = gx;
         dk += dkt;
     }
 }
 
-template <int T_, bool HARD, bool DI, bool STRICT, bool APPLY>
+// A fast instance (POL::fast) is launched for plain operands only (bwd_select): grad_s present, no grad_mean, no v_init, no broadcast input
+// frame.  Its loop has no launch-uniform branch: the optional operands are compiled out and a channel slice (gs_ctot / y_ctot) is addressed
+// through the channel count like a dense tensor.  Per element the expressions of the generic body (0 + grad_s included: it turns -0 into
+// +0), so both forms give the same bits.
+template <int T_, bool HARD, bool DI, bool STRICT, bool APPLY, class POL>
 __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
     const float* __restrict__ grad_s, const float* __restrict__ grad_mean, const float* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -324,6 +336,8 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
     const float* __restrict__ alpha_dev, float* __restrict__ grad_alpha, int c_begin, int c_end, int finalize) {
     __shared__ double red[NW];
     __shared__ float bc[2];
+    constexpr bool FAST = POL::fast;
+    if (FAST) { bcast = 0; sg_id = POL::sg; }
     if (alpha_dev) alpha = fabsf(*alpha_dev);    // learnable slope (EAS_SG_PATAN)
     // channels [c_begin, c_end) of the layer: a launch pair (sums, apply) may cover a channel group only, so that the apply pass finds the
     // group's y / grad_s still in the Infinity Cache (launch_bwd_t)
@@ -344,6 +358,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
     const int64_t My = (int64_t)N * Cy * HW;
     const int64_t yts = bcast ? 0 : My;
     const int64_t Mg = gs_ctot ? (int64_t)N * gs_ctot * HW : M;      // grad_s may be a channel slice of a wider tensor
+    const int Cg = gs_ctot ? gs_ctot : C;
     float m1 = 0.f, m2 = 0.f;
     if (APPLY) {
         // fixed-order reduction of this channel's chunk partials (every block computes the same value)
@@ -379,22 +394,23 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
 #pragma unroll
         for (int t = 0; t < T_; ++t) ys[t] = *reinterpret_cast<const float4*>(y + (int64_t)t * yts + ybase);
         float4 gm = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (grad_mean) {
+        if (!FAST && grad_mean) {
             gm = *reinterpret_cast<const float4*>(grad_mean + base);
             gm.x *= invT; gm.y *= invT; gm.z *= invT; gm.w *= invT;
         }
 #pragma unroll
         for (int t = 0; t < T_; ++t) {
             gsv[t] = gm;
-            if (grad_s) {
-                const int64_t gbase = gs_ctot ? (n * gs_ctot + c) * (int64_t)HW + (int64_t)q * VEC : base;
+            if (FAST || grad_s) {
+                const int64_t gbase = FAST ? (n * Cg + c) * (int64_t)HW + (int64_t)q * VEC
+                                           : (gs_ctot ? (n * gs_ctot + c) * (int64_t)HW + (int64_t)q * VEC : base);
                 const float4 g4 = *reinterpret_cast<const float4*>(grad_s + (int64_t)t * Mg + gbase);
                 gsv[t].x += g4.x; gsv[t].y += g4.y; gsv[t].z += g4.z; gsv[t].w += g4.w;
             }
         }
         const float vr0 = HARD ? p.v_reset : 0.0f;
         float4 v0 = make_float4(vr0, vr0, vr0, vr0);
-        if (v_init) v0 = *reinterpret_cast<const float4*>(v_init + base);
+        if (!FAST && v_init) v0 = *reinterpret_cast<const float4*>(v_init + base);
         float4 outv[T_];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
@@ -406,7 +422,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
             }
             const float v0e = reinterpret_cast<const float*>(&v0)[e];
             float dke = 0.f;
-            recompute_dz<T_, HARD, DI, STRICT>(yv, gs, v0e, scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, da);
+            recompute_dz<T_, HARD, DI, STRICT, POL>(yv, gs, v0e, scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, da);
 #pragma unroll
             for (int t = 0; t < T_; ++t) {
                 const float xhat = (yv[t] - mu) * istd;
@@ -473,7 +489,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
 // each (these layers are bound by the launches, not by their 30 MB).  Per element the arithmetic of the two-pass kernels; the per-channel
 // dL/dk / dL/dalpha partials go to the same workspace slots (chunk 0) and a one-block kernel adds them over the channels in fixed order.
 // (first half.)
-template <int T_, bool HARD, bool DI, bool STRICT, int NT_, int GPT>
+template <int T_, bool HARD, bool DI, bool STRICT, int NT_, int GPT, class POL>
 __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
     const float* __restrict__ grad_s, const float* __restrict__ grad_mean, const float* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -483,6 +499,9 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
     constexpr int NWV = NT_ / EAS_WAVE;
     __shared__ double red[4][NWV];
     __shared__ float bc[2];
+    // (a fast instance of this kernel takes every operand form: the optional operands are read once per thread in front of the two
+    // passes, not inside them)
+    if (POL::fast) sg_id = POL::sg;
     if (alpha_dev) alpha = fabsf(*alpha_dev);
     const int c = blockIdx.x;
     const float mu = mean[c], istd = invstd[c];
@@ -541,7 +560,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
                 gs[t] = reinterpret_cast<const float*>(&gsv[i][t])[e];
             }
             float dke = 0.f, dae = 0.f;
-            recompute_dz<T_, HARD, DI, STRICT>(yv, gs, reinterpret_cast<const float*>(&v0[i])[e], scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, dae);
+            recompute_dz<T_, HARD, DI, STRICT, POL>(yv, gs, reinterpret_cast<const float*>(&v0[i])[e], scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, dae);
             if (live) {
 #pragma unroll
                 for (int t = 0; t < T_; ++t) {
@@ -586,7 +605,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
                 gs[t] = reinterpret_cast<const float*>(&gsv[i][t])[e];
             }
             float dke = 0.f, dae = 0.f;
-            recompute_dz<T_, HARD, DI, STRICT>(yv, gs, reinterpret_cast<const float*>(&v0[i])[e], scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, dae);
+            recompute_dz<T_, HARD, DI, STRICT, POL>(yv, gs, reinterpret_cast<const float*>(&v0[i])[e], scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, dae);
 #pragma unroll
             for (int t = 0; t < T_; ++t) reinterpret_cast<float*>(&outv[t])[e] = scale * (dz[t] - m1 - ((yv[t] - mu) * istd) * m2);
         }
@@ -662,32 +681,54 @@ int launch_fwd(int T, const float* y, const float* mean, const float* invstd, co
 #undef EAS_CASE
 }
 
-template <int T_, bool HARD, bool DI, bool STRICT>
-int launch_bwd_t(const float* grad_s, const float* grad_mean, const float* y, const float* mean, const float* invstd,
-                 const float* gamma, const float* beta, const float* v_init, EasLifParams p, int sg, float alpha,
-                 int batch_stats, float* grad_y, float* grad_gamma, float* grad_beta, float* grad_w, double* ws, int N,
-                 int C, int HW, int bcast, int gs_ctot, int y_ctot, const float* alpha_dev, float* grad_alpha, hipStream_t st) {
+// One backward call: the operands of eas_bn_lif_bwd_ex / _patan after validation.
+struct BwdCall {
+    const float *grad_s, *grad_mean, *y, *mean, *invstd, *gamma, *beta, *v_init;
+    EasLifParams p;
+    int sg;
+    float alpha;
+    int batch_stats;
+    float *grad_y, *grad_gamma, *grad_beta, *grad_w;
+    double* ws;
+    int T, N, C, HW, bcast, gs_ctot, y_ctot;
+    const float* alpha_dev;
+    float* grad_alpha;
+    hipStream_t st;
+};
+
+// development switch, read per call (a test compares the forms in one process): EAS_BNLIF_BWD holds "two" (keep the two-pass launches where
+// one block per channel would do) and / or "generic" (the generic instance where the table has a fast one), e.g. "two,generic"
+static inline bool bwd_form(const char* word) {
+    const char* form = getenv("EAS_BNLIF_BWD");
+    return form && strstr(form, word);
+}
+
+// one block per channel where a channel fits the registers of a block (bn_lif_bwd_small_kernel): groups per thread, 0 = two passes
+static inline int bwd_one_pass_gpt(const BwdCall& c) {
+    const int gpt = c.T <= 3 ? 3 : (c.T <= 5 ? 2 : 1);                // 8 * T floats per group in registers
+    const int64_t groups = (int64_t)c.N * (c.HW / VEC);
+    return (!bwd_form("two") && !c.bcast && c.C >= 64 && groups <= 512 * gpt) ? gpt : 0;       // (1024-thread blocks are capped at 128 registers: they spill)
+}
+
+template <int T_, bool HARD, bool DI, bool STRICT, class POL>
+int launch_bwd_t(const BwdCall& c) {
+    const int N = c.N, C = c.C, HW = c.HW;
     const int chunks = pick_chunks((int64_t)N * (HW / VEC), C);
-    {
-        // one block per channel where a channel fits the registers of a block (bn_lif_bwd_small_kernel); EAS_BNLIF_BWD=two keeps the
-        // two-pass launches (development)
-        const char* form = getenv("EAS_BNLIF_BWD");      // (read per call: a test compares the two forms in one process)
-        const bool small_ok = !(form && form[0] == 't');
-        constexpr int GPT = T_ <= 3 ? 3 : (T_ <= 5 ? 2 : 1);         // 8 * T floats per group in registers
+    if (bwd_one_pass_gpt(c)) {
+        constexpr int GPT = T_ <= 3 ? 3 : (T_ <= 5 ? 2 : 1);
         const int64_t groups = (int64_t)N * (HW / VEC);
-        if (small_ok && !bcast && C >= 64 && groups <= 512 * GPT) {       // (1024-thread blocks are capped at 128 registers: they spill)
-#define EAS_SMALL(NT_) EAS_LAUNCH((bn_lif_bwd_small_kernel<T_, HARD, DI, STRICT, NT_, GPT>), dim3(C), dim3(NT_), 0, st, grad_s, grad_mean, y, mean, \
-                                   invstd, gamma, beta, v_init, p, sg, alpha, batch_stats, ws, grad_y, grad_gamma, grad_beta, N, C, HW, gs_ctot, y_ctot, alpha_dev)
-            if (groups <= 256 * GPT) EAS_SMALL(256);
-            else EAS_SMALL(512);
+#define EAS_SMALL(NT_) EAS_LAUNCH((bn_lif_bwd_small_kernel<T_, HARD, DI, STRICT, NT_, GPT, POL>), dim3(C), dim3(NT_), 0, c.st, c.grad_s, c.grad_mean, c.y, \
+                                   c.mean, c.invstd, c.gamma, c.beta, c.v_init, c.p, c.sg, c.alpha, c.batch_stats, c.ws, c.grad_y, c.grad_gamma,       \
+                                   c.grad_beta, N, C, HW, c.gs_ctot, c.y_ctot, c.alpha_dev)
+        if (groups <= 256 * GPT) EAS_SMALL(256);
+        else EAS_SMALL(512);
 #undef EAS_SMALL
+        EAS_CHECK_LAUNCH();
+        if (c.grad_w || c.grad_alpha) {
+            EAS_LAUNCH(bn_lif_bwd_scalars_kernel, dim3(1), dim3(EAS_BLOCK), 0, c.st, c.ws, C, c.p, c.grad_w, c.alpha_dev, c.grad_alpha);
             EAS_CHECK_LAUNCH();
-            if (grad_w || grad_alpha) {
-                EAS_LAUNCH(bn_lif_bwd_scalars_kernel, dim3(1), dim3(EAS_BLOCK), 0, st, ws, C, p, grad_w, alpha_dev, grad_alpha);
-                EAS_CHECK_LAUNCH();
-            }
-            return EAS_OK;
         }
+        return EAS_OK;
     }
     // two passes: the BatchNorm backward needs the channel's sums of dz and dz * xhat before any grad_y; pass 2 recomputes the neuron
     // (cheaper than parking dz: measured).
@@ -697,7 +738,7 @@ int launch_bwd_t(const float* grad_s, const float* grad_mean, const float* y, co
     static const int group_mb = eas_dev_env("EAS_BNLIF_BWD_GROUP_MB") ? atoi(eas_dev_env("EAS_BNLIF_BWD_GROUP_MB")) : 0;
     int gc = C;
     if (group_mb > 0) {
-        const double per_channel = (double)N * HW * 4.0 * ((bcast ? 1 : T_) + T_);
+        const double per_channel = (double)N * HW * 4.0 * ((c.bcast ? 1 : T_) + T_);
         gc = (int)(group_mb * 1048576.0 / per_channel) / 8 * 8;
         if (gc < 8) gc = 8;
         if (gc > C) gc = C;
@@ -705,34 +746,54 @@ int launch_bwd_t(const float* grad_s, const float* grad_mean, const float* y, co
     for (int c0 = 0; c0 < C; c0 += gc) {
         const int c1 = c0 + gc < C ? c0 + gc : C;
         const int last = c1 == C;
-        EAS_LAUNCH((bn_lif_bwd_kernel<T_, HARD, DI, STRICT, false>), EAS_CHAN_GRID(chunks, c1 - c0), dim3(EAS_BLOCK), 0, st, grad_s,
-                   grad_mean, y, mean, invstd, gamma, beta, v_init, p, sg, alpha, batch_stats, ws, chunks, grad_y,
-                   grad_gamma, grad_beta, (float*)nullptr, N, C, HW, bcast, gs_ctot, y_ctot, alpha_dev, (float*)nullptr, c0, c1, 0);
+        EAS_LAUNCH((bn_lif_bwd_kernel<T_, HARD, DI, STRICT, false, POL>), EAS_CHAN_GRID(chunks, c1 - c0), dim3(EAS_BLOCK), 0, c.st, c.grad_s,
+                   c.grad_mean, c.y, c.mean, c.invstd, c.gamma, c.beta, c.v_init, c.p, c.sg, c.alpha, c.batch_stats, c.ws, chunks, c.grad_y,
+                   c.grad_gamma, c.grad_beta, (float*)nullptr, N, C, HW, c.bcast, c.gs_ctot, c.y_ctot, c.alpha_dev, (float*)nullptr, c0, c1, 0);
         EAS_CHECK_LAUNCH();
-        EAS_LAUNCH((bn_lif_bwd_kernel<T_, HARD, DI, STRICT, true>), EAS_CHAN_GRID(chunks, c1 - c0), dim3(EAS_BLOCK), 0, st, grad_s,
-                   grad_mean, y, mean, invstd, gamma, beta, v_init, p, sg, alpha, batch_stats, ws, chunks, grad_y,
-                   grad_gamma, grad_beta, grad_w, N, C, HW, bcast, gs_ctot, y_ctot, alpha_dev, grad_alpha, c0, c1, last);
+        EAS_LAUNCH((bn_lif_bwd_kernel<T_, HARD, DI, STRICT, true, POL>), EAS_CHAN_GRID(chunks, c1 - c0), dim3(EAS_BLOCK), 0, c.st, c.grad_s,
+                   c.grad_mean, c.y, c.mean, c.invstd, c.gamma, c.beta, c.v_init, c.p, c.sg, c.alpha, c.batch_stats, c.ws, chunks, c.grad_y,
+                   c.grad_gamma, c.grad_beta, c.grad_w, N, C, HW, c.bcast, c.gs_ctot, c.y_ctot, c.alpha_dev, c.grad_alpha, c0, c1, last);
         EAS_CHECK_LAUNCH();
     }
     return EAS_OK;
 }
 
-template <bool HARD, bool DI, bool STRICT>
-int launch_bwd(int T, const float* grad_s, const float* grad_mean, const float* y, const float* mean,
-               const float* invstd, const float* gamma, const float* beta, const float* v_init, EasLifParams p, int sg,
-               float alpha, int batch_stats, float* grad_y, float* grad_gamma, float* grad_beta, float* grad_w,
-               double* ws, int N, int C, int HW, int bcast, int gs_ctot, int y_ctot, const float* alpha_dev, float* grad_alpha,
-               hipStream_t st) {
-#define EAS_CASE(TT)                                                                                               \
-    case TT:                                                                                                       \
-        return launch_bwd_t<TT, HARD, DI, STRICT>(grad_s, grad_mean, y, mean, invstd, gamma, beta, v_init, p, sg, alpha, \
-                                                  batch_stats, grad_y, grad_gamma, grad_beta, grad_w, ws, N, C, HW, bcast, gs_ctot, y_ctot,         \
-                                                  alpha_dev, grad_alpha, st);
-    switch (T) {
-        EAS_CASE(1) EAS_CASE(2) EAS_CASE(3) EAS_CASE(4) EAS_CASE(5) EAS_CASE(6) EAS_CASE(7) EAS_CASE(8)
-        default: return EAS_ERR_UNSUPPORTED;
+// The instances of the backward: every row is one set of kernels (sums, apply, one-pass at 256 and 512 threads).  A fast row serves the
+// launches with exactly its surrogate and reset form and -- in the two-pass form -- plain operands; a generic row (sg = EAS_SG_RUNTIME) serves every launch of its
+// (T, reset, decay) form.  Fast rows exist for what the bench workloads and the published recipes train with (eas_snn_amd/workloads.py:
+// soft reset, decay_input = False, attached reset, spike_fn atan, T = 3 / 5 / 7); everything else runs the generic row of its form.
+struct BwdRow {
+    int T;
+    bool hard, di;
+    int sg;
+    bool detach;
+    int (*fn)(const BwdCall&);
+};
+template <int T_, bool HARD, bool DI, int SG = EAS_SG_RUNTIME, bool DETACH = false>
+constexpr BwdRow bwd_row() {
+    return {T_, HARD, DI, SG, DETACH, launch_bwd_t<T_, HARD, DI, false, BnLifBwdPolicy<SG, DETACH>>};
+}
+#define EAS_BWD_GENERIC_ROWS(H, D) \
+    bwd_row<1, H, D>(), bwd_row<2, H, D>(), bwd_row<3, H, D>(), bwd_row<4, H, D>(), bwd_row<5, H, D>(), bwd_row<6, H, D>(), bwd_row<7, H, D>(), bwd_row<8, H, D>()
+const BwdRow kBwdInstances[] = {
+    // fast (first: the first matching row is taken)
+    bwd_row<3, false, false, EAS_SG_ATAN>(), bwd_row<5, false, false, EAS_SG_ATAN>(), bwd_row<7, false, false, EAS_SG_ATAN>(),
+    // generic
+    EAS_BWD_GENERIC_ROWS(false, false), EAS_BWD_GENERIC_ROWS(true, false), EAS_BWD_GENERIC_ROWS(false, true), EAS_BWD_GENERIC_ROWS(true, true),
+};
+#undef EAS_BWD_GENERIC_ROWS
+
+// the table decides: the first row that serves the call
+int bwd_select(const BwdCall& c) {
+    const bool hard = c.p.flags & EAS_LIF_HARD_RESET, di = c.p.flags & EAS_LIF_DECAY_INPUT, detach = c.p.flags & EAS_LIF_DETACH_RESET;
+    if (c.p.flags & EAS_LIF_FIRE_STRICT) return EAS_ERR_UNSUPPORTED;      // strict '>' firing only exists in the sampler / in-repo LIFCell
+    const bool plain = bwd_one_pass_gpt(c) || (c.grad_s && !c.grad_mean && !c.v_init && !c.bcast);      // the one-pass kernel takes every operand form
+    const bool fast_ok = plain && !bwd_form("generic");
+    for (const BwdRow& r : kBwdInstances) {
+        if (r.T != c.T || r.hard != hard || r.di != di) continue;
+        if (r.sg == EAS_SG_RUNTIME || (fast_ok && r.sg == c.sg && r.detach == detach)) return r.fn(c);
     }
-#undef EAS_CASE
+    return EAS_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -854,20 +915,11 @@ static int bn_lif_bwd_impl(const float* grad_s, int grad_s_ctot, const float* gr
     if ((grad_s_ctot != 0 && grad_s_ctot < C) || (y_ctot != 0 && (y_ctot < C || y_bcast))) return EAS_ERR_INVALID_ARG;
     const int gs_ctot = grad_s_ctot == C ? 0 : grad_s_ctot;
     const int yc = y_ctot == C ? 0 : y_ctot;
-    EasLifParams p{w_logit, k_const, v_th, v_reset, flags};
-    const bool hard = flags & EAS_LIF_HARD_RESET, di = flags & EAS_LIF_DECAY_INPUT, strict = flags & EAS_LIF_FIRE_STRICT;
-    hipStream_t st = eas_s(stream);
+    const BwdCall call{grad_s, grad_mean, y, mean, invstd, gamma, beta, v_init, EasLifParams{w_logit, k_const, v_th, v_reset, flags}, surrogate, alpha,
+                       batch_stats, grad_y, grad_gamma, grad_beta, grad_w, workspace, T, N, C, HW, y_bcast, gs_ctot, yc, alpha_dev, grad_alpha,
+                       eas_s(stream)};
     EAS_CLEAR_ERR();
-#define EAS_DISPATCH(H, D, S)                                                                                       \
-    return launch_bwd<H, D, S>(T, grad_s, grad_mean, y, mean, invstd, gamma, beta, v_init, p, surrogate, alpha,     \
-                               batch_stats, grad_y, grad_gamma, grad_beta, grad_w, workspace, N, C, HW, y_bcast, gs_ctot, yc,    \
-                               alpha_dev, grad_alpha, st)
-    if (!hard && !di && !strict) EAS_DISPATCH(false, false, false);
-    if (hard && !di && !strict) EAS_DISPATCH(true, false, false);
-    if (!hard && di && !strict) EAS_DISPATCH(false, true, false);
-    if (hard && di && !strict) EAS_DISPATCH(true, true, false);
-    return EAS_ERR_UNSUPPORTED;
-#undef EAS_DISPATCH
+    return bwd_select(call);
 }
 
 int eas_bn_lif_bwd_ex(const float* grad_s, int grad_s_ctot, const float* grad_mean, const float* y, int y_ctot, const float* mean,
