@@ -196,6 +196,7 @@ PROTOTYPES = {
     'eas_conv_fwd_stats': (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P, _P, C.c_int, _P]),
     'eas_conv_fwd_stats_blocks': (C.c_int, [C.c_int] * 8),
     'eas_conv_dgrad_s2': (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P]),
+    'eas_conv_dgrad_s2_supported': (C.c_int, [C.c_int] * 5),
     'eas_conv_dgrad_small_supported': (C.c_int, [C.c_int] * 5),
     'eas_conv_dgrad_small': (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P]),
     'eas_conv_wgrad_workspace_floats': (C.c_int64, [C.c_int] * 8),

@@ -46,13 +46,11 @@ __global__ __launch_bounds__(64 * WVM * WVN, 2) void conv3x3_group_kernel(const 
 }
 
 template <int XT, int WN, int WVM, int WVN, int NIT, int LM, typename G>
-int launch_group3(const ConvGroupArgsT<G>& a, int grid_y, size_t lds, hipStream_t st) {
+int launch_group3(ConvGroupArgsT<G>& a, int grid_y, size_t lds, hipStream_t st) {
     auto kern = conv3x3_group_kernel<XT, WN, WVM, WVN, NIT, LM, G>;
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
-        attr_set = true;
-    }
+    for (int p = 0; p < a.n; ++p)
+        if (const int rc = conv_launch_prep((const void*)kern, attr_set, a.g[p], a.vec2[p] ? 2 : 4, 16)) return rc;
     EAS_LAUNCH(kern, dim3(a.first[a.n], grid_y), dim3(64 * WVM * WVN), lds, st, a);
     return EAS_OK;
 }
@@ -61,7 +59,7 @@ struct GCand { int wvm, wvn, wn, nit; };
 static const GCand kCands[4] = {{4, 1, 5, 2}, {2, 2, 5, 2}, {4, 1, 3, 2}, {2, 2, 3, 2}};
 
 template <int XT, int LM, typename G>
-int launch_cand3(int i, const ConvGroupArgsT<G>& a, int grid_y, size_t lds, hipStream_t st) {
+int launch_cand3(int i, ConvGroupArgsT<G>& a, int grid_y, size_t lds, hipStream_t st) {
     switch (i) {
         case 0: return launch_group3<XT, 5, 4, 1, 2, LM, G>(a, grid_y, lds, st);
         case 1: return launch_group3<XT, 5, 2, 2, 2, LM, G>(a, grid_y, lds, st);
@@ -70,42 +68,9 @@ int launch_cand3(int i, const ConvGroupArgsT<G>& a, int grid_y, size_t lds, hipS
     }
 }
 
-// geometry of one 3x3 stride-1 problem (padding 1), before a tile is chosen: conv_fwd_impl's set-up
-void base_geom(ConvGeomCore& g, const EasConvProblem& q) {
-    g.NI = q.NI; g.Cin = q.Cin; g.Cout = q.Cout; g.Hi = q.Hi; g.Wi = q.Wi;
-    g.Ho = q.Hi; g.Wo = q.Wi;
-    g.RS = q.Wi + 2;
-    g.pad_t = g.pad_l = 1;
-    g.ext_h = 3;
-    for (int t = 0; t < 9; ++t) g.tap_off[t] = (t / 3) * g.RS + (t % 3);
-    g.oH = g.Ho; g.oW = g.Wo; g.os = 1; g.oph = g.opw = 0;
-    g.MT = (q.Cout + 31) / 32;
-    g.KSTEPS = (q.Cin + 15) / 16;
-    g.total_rows = q.NI * g.Ho;
-    g.Wst = q.Wi; g.gx0 = 0; g.qshift = 0; g.parts = 1;
-}
-
-// the tile of candidate c for problem geometry g: the largest whole-row tile <= c's pixel count whose patch and staging items fit
-template <int XT>
-bool fit_tile(ConvGeomCore& t, const GCand& c, int vec) {
-    constexpr int CCH = 16;
-    const int nchunks = (t.KSTEPS * 16 + CCH - 1) / CCH;
-    const int nbuf = nchunks == 1 ? 1 : 2;
-    const int threads = 64 * c.wvm * c.wvn;
-    for (int cap = 32 * c.wn * c.wvn; cap >= t.Wo; cap -= 32) {
-        t.RT = pick_rows(t.Ho, t.Wo, cap);
-        if (t.RT == 0) return false;
-        t.rows_seg = t.RT < t.Ho ? t.RT : t.Ho;
-        t.nseg = t.RT / t.rows_seg;
-        t.rows_in = (t.rows_seg - 1) + t.ext_h;
-        t.Q = t.nseg * t.rows_in * t.RS;
-        if ((size_t)nbuf * t.Q * CCH * 2 * XT <= 160 * 1024 && t.nseg * t.rows_in * (t.Wst / vec) * (CCH / 8) <= c.nit * threads) return true;
-        cap = t.RT * t.Wo;
-    }
-    return false;
-}
-
-// One tile shape for all problems of the group: the cost model of dispatch_tile (conv_mfma_body.h) over the SUM of the problems' blocks.
+// One tile shape for all problems of the group: every problem gets the candidate's largest fitting whole-row tile (conv_mfma_body.h), and
+// the round cost of dispatch_tile is paid for the SUM of the problems' blocks in fractional rounds (the small levels fill the last round
+// of the large one).
 template <int XT, typename G>
 int plan_group3(const EasConvProblem* pr, int n, ConvGroupArgsT<G>& a, int& best, int& grid_y, size_t& lds, int* nb_out) {
     const GCand* cands = kCands;
@@ -116,6 +81,7 @@ int plan_group3(const EasConvProblem* pr, int n, ConvGroupArgsT<G>& a, int& best
     for (int i = 0; i < 4; ++i) {
         if (force >= 0 && i != force) continue;
         const GCand& c = cands[i];
+        const int threads = 64 * c.wvm * c.wvn;
         int cout_min = 1 << 30;
         for (int p = 0; p < n; ++p) cout_min = pr[p].Cout < cout_min ? pr[p].Cout : cout_min;
         if ((c.wvm - 1) * 32 >= cout_min) continue;          // every wave row has channels to compute in every problem
@@ -126,27 +92,23 @@ int plan_group3(const EasConvProblem* pr, int n, ConvGroupArgsT<G>& a, int& best
         int gy = 1, blocks_x = 0;
         for (int p = 0; p < n && ok; ++p) {
             G& g = t.g[p];
-            base_geom(g, pr[p]);
+            conv3_base_geom(g, pr[p].NI, pr[p].Cin, pr[p].Cout, pr[p].Hi, pr[p].Wi, 1);
             const int vec = pr[p].Wi % 4 == 0 ? 4 : 2;
             t.vec2[p] = vec == 2;
-            ok = fit_tile<XT>(g, c, vec);
+            const size_t l = conv_tile_shrink(g, 32 * c.wn * c.wvn, 1, g.KSTEPS == 1 ? 1 : 2, 16, XT, vec, c.nit * threads);
+            ok = l != 0;
             if (!ok) break;
-            const int nchunks = g.KSTEPS;
-            const size_t l = (size_t)(nchunks == 1 ? 1 : 2) * g.Q * 16 * 2 * XT;
             lds_max = l > lds_max ? l : lds_max;
-            const int bxp = (g.total_rows + g.RT - 1) / g.RT;
-            const int byp = (g.MT + c.wvm - 1) / c.wvm;
+            const dim3 gp = conv_tile_grid(g, c.wvm);
             t.first[p] = blocks_x;
-            blocks_x += bxp;
-            gy = byp > gy ? byp : gy;
-            load += (double)bxp * byp;
+            blocks_x += gp.x;
+            gy = (int)gp.y > gy ? (int)gp.y : gy;
+            load += (double)gp.x * gp.y;
         }
         if (!ok) continue;
         t.first[n] = blocks_x;
-        const int bpc = 2 * lds_max <= 160 * 1024 ? 2 : 1;
-        const double per_tile = XT == 1 ? 96.0 : 192.0;
-        const double mfma_part = (c.wn * per_tile > 450.0 ? c.wn * per_tile : 450.0) / (5.0 * per_tile);
-        const double round_cost = (bpc == 2 && load > 256.0 ? 1.2 : 1.0) * (0.3 + 0.7 * mfma_part);
+        const int bpc = conv_blocks_per_cu(threads, lds_max);
+        const double round_cost = conv_round_factor(threads, bpc, load) * conv_block_time(c.wn, 5.0, XT == 1 ? 96.0 : 192.0, conv_step_lat());
         double rounds = load / (256.0 * bpc);
         if (rounds < 1.0) rounds = 1.0;
         const double cost = rounds * round_cost;
@@ -162,12 +124,11 @@ int plan_group3(const EasConvProblem* pr, int n, ConvGroupArgsT<G>& a, int& best
     for (int p = 0; p < n; ++p) {
         G& g = a.g[p];
         const int gxp = a.first[p + 1] - a.first[p];
+        conv_plan_note("group", best, a.vec2[p] ? 2 : 4, g, dim3(gxp, grid_y, a.first[n]), lds);
         if (nb_out) nb_out[p] = gxp;
         g.stats = pr[p].stats;
         g.stats_nb = gxp;
         any_stats = any_stats || pr[p].stats;
-        if (g.total_rows >= (1 << 20) || g.nseg * g.rows_in * (g.Wst / (a.vec2[p] ? 2 : 4)) >= (1 << 20)) return EAS_ERR_UNSUPPORTED;     // fdiv range
-        conv_geom_magics(g, a.vec2[p] ? 2 : 4, 16);
         a.x[p] = (const float*)pr[p].x; a.wp[p] = (const bf16x8*)pr[p].packed_w; a.bias[p] = pr[p].bias; a.y[p] = pr[p].y;
     }
     if (any_stats && lds < stats_lds) lds = stats_lds;

@@ -7,7 +7,7 @@
 namespace {
 
 // Tile choice of the fused eval step (LM = 1: time-major, the wave tile is lif.T time steps of 32 pixels; LM = 2: one result for all steps).
-// Same cost model as dispatch_tile; the block covers 32 * WVN spatial pixels (time-major) whose T time slices are staged side by side.
+// The fit and cost rules are conv_mfma_body.h's; the block covers 32 * WVN spatial pixels (time-major) whose T time slices are staged side by side.
 template <int TAPS, int S, int XT, int CCH, int VEC, bool PL, int LM>
 int dispatch_tile_lif(const float* x, const bf16x8* wp, ConvGeom g, hipStream_t st, bool query) {
     struct Cand { int wvm, wvn, threads, nit, wn; launch_fn fn; };
@@ -31,6 +31,7 @@ int dispatch_tile_lif(const float* x, const bf16x8* wp, ConvGeom g, hipStream_t 
     int best = -1;
     double best_cost = 0.0;
     int best_rank = 0;
+    size_t best_lds = 0;
     ConvGeom best_g = g;
     static const int force = eas_dev_env("EAS_LIF_TILE") ? atoi(eas_dev_env("EAS_LIF_TILE")) : -1;      // development: force a candidate
     for (int i = 0; i < ncand; ++i) {
@@ -39,54 +40,28 @@ int dispatch_tile_lif(const float* x, const bf16x8* wp, ConvGeom g, hipStream_t 
         if (LM == 1 && c.wn % T != 0) continue;          // the wave tile holds the T steps of one or two spatial tiles
         const int m2 = LM == 1 ? c.wn / T : 1;
         if ((c.wvm - 1) * 32 >= g.Cout && c.wvm != 1) continue;
-        const int nbuf = nchunks == 1 ? 1 : 2;
         ConvGeom t = g;
         t.single = 0;
         const int bn = LM == 1 ? 32 * m2 * c.wvn : 32 * c.wn * c.wvn;  // spatial pixels of the block tile
-        bool fits = false;
-        for (int cap = bn; cap >= g.Wo && !fits; cap -= 32) {
-            // whole images per tile where they fit, else RT rows of one image with a short last tile per image (ragged: any RT)
-            const int maxrt = cap / g.Wo;
-            t.bpi = 0;
-            if (maxrt >= g.Ho) t.RT = pick_rows(g.Ho, g.Wo, cap);
-            else {
-                t.RT = maxrt;
-                t.bpi = (g.Ho + t.RT - 1) / t.RT;
-                t.RT = (g.Ho + t.bpi - 1) / t.bpi;       // the same tile count with evener tiles
-            }
-            if (t.RT == 0) break;
-            t.rows_seg = t.RT < g.Ho ? t.RT : g.Ho;
-            t.nseg_s = t.RT / t.rows_seg;
-            t.nseg = (LM == 1 ? T : 1) * t.nseg_s;
-            t.rows_in = (t.rows_seg - 1) * S + g.ext_h;
-            t.Q = t.nseg * t.rows_in * t.RS;
-            fits = (size_t)nbuf * t.Q * CCH * 2 * XT <= 160 * 1024 && t.nseg * t.rows_in * (g.Wst / VEC) * (CCH / 8) <= c.nit * c.threads;
-            cap = t.RT * g.Wo;
-        }
-        if (!fits) continue;
-        const long blocks = (long)(t.bpi ? g.NI * t.bpi : (g.total_rows + t.RT - 1) / t.RT) * ((g.MT + c.wvm - 1) / c.wvm);
-        const size_t lds_bytes = (size_t)nbuf * t.Q * CCH * 2 * XT;
-        const int bpc = c.threads == 512 ? 1 : (2 * lds_bytes <= 160 * 1024 ? 2 : 1);
-        const double per_tile = XT == 1 ? 96.0 : 192.0, lat = 450.0;
-        const double mfma_part = (c.wn * per_tile > lat ? c.wn * per_tile : lat) / (5.0 * per_tile);
-        const double round_cost = (c.threads == 512 ? 1.27 : (bpc == 2 && blocks > 256 ? 1.2 : 1.0)) * (0.3 + 0.7 * mfma_part);
-        // the valid share of the pixel tile matters here (a 32 * WVN pixel block of whole rows): rounds x cost / valid pixels per block
+        // ragged tiles (any RT: a 32 * 2^k pixel tile holds 3 or 6 rows of 40 pixels); time-major: the T time slices in one patch
+        const size_t lds = conv_tile_shrink(t, bn, S, nchunks == 1 ? 1 : 2, CCH, XT, VEC, c.nit * c.threads, true, LM == 1 ? T : 1);
+        if (!lds) continue;
+        const dim3 grid = conv_tile_grid(t, c.wvm);
+        const long blocks = (long)grid.x * grid.y;
+        const int bpc = conv_blocks_per_cu(c.threads, lds);
+        // dispatch_tile's round cost and tie rank (without its single-buffer mode; the rank prefers waves along the channels in every grid)
+        const double round_cost = conv_round_factor(c.threads, bpc, (double)blocks) * conv_block_time(c.wn, 5.0, XT == 1 ? 96.0 : 192.0, conv_step_lat());
         const int valid = t.RT * g.Wo;
         const double cost = (double)((blocks + 256 * bpc - 1) / (256 * bpc)) * round_cost;
         const int rank = c.wvm * 4096 + (valid < 4096 ? valid : 4095);
         if (best < 0 || cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && rank > best_rank)) {
-            best = i; best_cost = cost; best_rank = rank; best_g = t;
+            best = i; best_cost = cost; best_rank = rank; best_g = t; best_lds = lds;
         }
     }
     if (best < 0) return EAS_ERR_UNSUPPORTED;
+    conv_plan_note(LM == 1 ? "lif time-major" : "lif shared", best, VEC, best_g, conv_tile_grid(best_g, cands[best].wvm), best_lds);
     if (query) return EAS_OK;
-    static const bool dbg = eas_dev_env("EAS_LIF_DBG") != nullptr;
-    if (dbg)
-        fprintf(stderr, "lif tile: LM %d T %d N %d %dx%d Cin %d Cout %d S %d -> cand %d (wvm %d wvn %d wn %d) RT %d nseg %d Q %d lds %zu blocks %ld\n", LM, T, g.NI,
-                g.Ho, g.Wo, g.Cin, g.Cout, S, best, cands[best].wvm, cands[best].wvn, cands[best].wn, best_g.RT, best_g.nseg, best_g.Q,
-                (size_t)(nchunks == 1 ? 1 : 2) * best_g.Q * CCH * 2 * XT,
-                (long)(best_g.bpi ? g.NI * best_g.bpi : (g.total_rows + best_g.RT - 1) / best_g.RT) * ((g.MT + cands[best].wvm - 1) / cands[best].wvm));
-    return cands[best].fn(x, wp, nullptr, nullptr, nullptr, best_g, st);
+    return cands[best].fn(x, wp, nullptr, nullptr, nullptr, best_g, best_lds, st);
 }
 
 }  // namespace
@@ -140,19 +115,8 @@ static int conv_lif_impl(const EasConvBnLifEval* d, eas_stream_t stream, bool qu
         rc = eas_conv1x1_lif_dispatch(d->x, d->packed_w, lif, Cin, d->x_terms, d->x_shared, st, query);
     } else {
         ConvGeom g{};
-        g.NI = N; g.Cin = Cin; g.Cout = Cout; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo;
-        g.RS = Wi + 2 * pad;
-        g.pad_t = g.pad_l = pad;
-        g.ext_h = ksize;
-        for (int t = 0; t < 9; ++t) g.tap_off[t] = (t / 3) * g.RS + (t % 3);
-        g.oH = Ho; g.oW = Wo; g.os = 1; g.oph = g.opw = 0;
-        g.MT = (Cout + 31) / 32;
-        g.KSTEPS = (Cin + 15) / 16;
-        g.total_rows = N * Ho;
-        g.Wst = Wi; g.gx0 = 0; g.qshift = 0; g.parts = 1;
+        conv3_base_geom(g, N, Cin, Cout, Hi, Wi, stride);
         g.lif = lif;
-        static const int dbg = eas_dev_env("EAS_CONV_DBG") ? atoi(eas_dev_env("EAS_CONV_DBG")) : 0;
-        g.dbg = dbg;
         const bf16x8* wp = (const bf16x8*)d->packed_w;
         const float* x = (const float*)d->x;
         const bool v4 = Wi % 4 == 0;

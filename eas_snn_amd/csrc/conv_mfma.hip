@@ -22,7 +22,8 @@
 //     of these kernels' wave cycles, so neither is what they wait for.
 //   input gradient of a stride-1 conv is the same kernel on grad_y with the weights packed transposed + flipped.
 //
-//   input gradient of a stride-2 3x3 conv: per parity class of the input pixel a stride-1 tap-list convolution (eas_conv_dgrad_s2).
+//   input gradient of a stride-2 3x3 conv: one launch whose tiles hold the four parity classes of the input pixel (eas_conv_dgrad_s2,
+//   conv_s2d.hip); the weights are packed by class here (mode 2).
 //
 // Wave tile = one 32-channel M-tile x five 32-pixel N-tiles (80 accumulator registers); block = 4 or 8 waves arranged
 // (waves along M) x (waves along N), block tile = RT whole output rows (possibly several whole images); two 4-wave blocks or
@@ -111,7 +112,8 @@ __device__ __forceinline__ void pack_fragment_s2dgrad(const float* __restrict__ 
     wp[base + 2 * term + pos] = t2;
 }
 
-__device__ __forceinline__ int pack_total(int Cout, int Cin, int ksize, int mode) {
+// bf16x8 fragments per term of a packed weight tensor: the one size rule of the packers and of eas_conv_packed_weight_bytes
+__host__ __device__ __forceinline__ int pack_total(int Cout, int Cin, int ksize, int mode) {
     const int M = mode ? Cin : Cout, K = mode ? Cout : Cin;
     return ((M + 31) / 32) * ((K + 15) / 16) * ksize * ksize * 64;
 }
@@ -179,78 +181,24 @@ __global__ __launch_bounds__(256) void conv_pack_weights_flat_kernel(const long 
     }
 }
 
-// Input gradient of a stride-2 3x3 convolution in ONE launch: blockIdx.z = parity class of the input pixel, every class a stride-1
-// tap-list convolution over grad_y with its own tap count (1, 2, 2, 4), channel chunk (64, 32, 32, 16: four MFMA steps per chunk
-// each), weights and tile geometry -- the four class kernels used to be four launches, each leaving most CUs idle on the small
-// maps and each staging grad_y by itself.
-struct S2Geoms {
-    ConvGeom g[4];
-    const bf16x8* wp[4];
-};
-
-template <int WM, int WN, int WVM, int WVN, int VEC, int NIT>
-__global__ __launch_bounds__(64 * WVM * WVN, 2) void conv_dgrad_s2_kernel(const float* __restrict__ gy, float* __restrict__ gx, const S2Geoms sg) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int cls = blockIdx.z;
-    if ((int)blockIdx.x * sg.g[cls].RT >= sg.g[cls].total_rows) return;
-    switch (cls) {
-        case 0: conv_tile_body<1, 1, 3, WM, WN, WVM, WVN, 64, VEC, NIT>(gy, sg.wp[0], nullptr, gx, nullptr, sg.g[0], 0, smem, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x); break;
-        case 1: conv_tile_body<2, 1, 3, WM, WN, WVM, WVN, 32, VEC, NIT>(gy, sg.wp[1], nullptr, gx, nullptr, sg.g[1], 0, smem, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x); break;
-        case 2: conv_tile_body<2, 1, 3, WM, WN, WVM, WVN, 32, VEC, NIT>(gy, sg.wp[2], nullptr, gx, nullptr, sg.g[2], 0, smem, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x); break;
-        default: conv_tile_body<4, 1, 3, WM, WN, WVM, WVN, 16, VEC, NIT>(gy, sg.wp[3], nullptr, gx, nullptr, sg.g[3], 0, smem, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x); break;
-    }
-}
-
-template <int WM, int WN, int WVM, int WVN, int VEC, int NIT>
-int launch_s2(const float* gy, float* gx, S2Geoms sg, hipStream_t st) {
-    auto kern = conv_dgrad_s2_kernel<WM, WN, WVM, WVN, VEC, NIT>;
-    static const int cch[4] = {64, 32, 32, 16};
-    size_t lds = 0;
-    int gx_blocks = 0;
-    for (int c = 0; c < 4; ++c) {
-        ConvGeom& g = sg.g[c];
-        const int nbuf = g.KSTEPS * 16 <= cch[c] ? 1 : 2;
-        const size_t l = (size_t)nbuf * g.Q * cch[c] * 2 * 3;
-        lds = l > lds ? l : lds;
-        const int units = g.nseg * g.rows_in * (g.Wst / VEC);
-        if (g.total_rows >= (1 << 20) || units >= (1 << 20)) return EAS_ERR_UNSUPPORTED;
-        conv_geom_magics(g, VEC, cch[c]);
-        const int b = (g.total_rows + g.RT - 1) / g.RT;
-        gx_blocks = b > gx_blocks ? b : gx_blocks;
-    }
-    if (lds > 160 * 1024) return EAS_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
-        attr_set = true;
-    }
-    dim3 grid(gx_blocks, (sg.g[0].MT + WVM * WM - 1) / (WVM * WM), 4);
-    EAS_LAUNCH(kern, grid, dim3(64 * WVM * WVN), lds, st, gy, gx, sg);
-    return EAS_OK;
-}
-
 }  // namespace
 
 int eas_conv1x1_dispatch(const float* x, const void* packed_w, const float* bias, float* y, int NI, int Cin, int Cout, int HW, int x_terms,
                          hipStream_t st, double* stats, int stats_nb, int* nb_out, int planes, int* inexact, int act, const void* bna);
-// conv_s2d.hip: the stride-2 input gradient with the four parity classes in one tile
-int eas_conv_dgrad_s2c_dispatch(const float* gy, const void* packed_w, float* gx, int NI, int Cin, int Cout, int Hi, int Wi, hipStream_t st, bool query);
 // conv_lif_mfma.hip: the 3x3 tiles with the BatchNorm + activation epilogue (kernel template LM = 3), fp32 three-term input
 int eas_conv3x3_bna_dispatch(int stride, int v4, const float* x, const void* wp, float* y, const void* geom, hipStream_t st);
 
 extern "C" {
 
 int64_t eas_conv_packed_weight_bytes(int Cout, int Cin, int ksize, int mode) {
-    const int M = mode ? Cin : Cout, K = mode ? Cout : Cin;
-    return (int64_t)3 * ((M + 31) / 32) * ((K + 15) / 16) * ksize * ksize * 64 * 16;
+    return (int64_t)3 * pack_total(Cout, Cin, ksize, mode) * 16;
 }
 
 int eas_conv_pack_weights(const float* w, void* packed, int Cout, int Cin, int ksize, int mode, eas_stream_t stream) {
     if (!w || !packed || Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3) || mode < 0 || mode > 2 || (mode == 2 && ksize != 3))
         return EAS_ERR_INVALID_ARG;
     EAS_CLEAR_ERR();
-    const int M = mode ? Cin : Cout, K = mode ? Cout : Cin;
-    const int total = ((M + 31) / 32) * ((K + 15) / 16) * ksize * ksize * 64;
+    const int total = pack_total(Cout, Cin, ksize, mode);
     EAS_LAUNCH(conv_pack_weights_kernel, dim3(eas_grid_1d(total)), dim3(EAS_BLOCK), 0, eas_s(stream), w, (bf16x8*)packed, Cout, Cin, ksize,
                        mode);
     EAS_CHECK_LAUNCH();
@@ -292,31 +240,6 @@ static int conv_fwd_impl(const float* x, const void* packed_w, const float* bias
     if (planes && !query && ((uintptr_t)x & 15)) return EAS_ERR_INVALID_ARG;
     EAS_CLEAR_ERR();
     ConvGeom g{};
-    const int pad = ksize / 2;
-    g.NI = NI; g.Cin = Cin; g.Cout = Cout; g.Hi = Hi; g.Wi = Wi;
-    g.Ho = (Hi + 2 * pad - ksize) / stride + 1;
-    g.Wo = (Wi + 2 * pad - ksize) / stride + 1;
-    g.RS = Wi + 2 * pad;
-    {
-        // Rows narrower than / not a multiple of the 32-pixel fragment: a fragment's lanes then cross a staged-row boundary, where the pixel
-        // index jumps by RS - Wo + 1.  With (RS - Wo) a multiple of 16 the lanes' 16-byte slots stay distinct modulo 16 across the jump, i.e.
-        // the ds_read_b128 stays conflict-free (scripts/lds_conflict_model.py: 32x40 maps 3.2 -> 2.0 LDS cycles per half wave, 16x20 maps
-        // 4.0 -> 2.0); costs 14 more staged (zero) columns per row.  Measured (same box): config 2 unchanged (21.23 / 21.24 ms without,
-        // 21.24 / 21.20 ms with), config 3 SLOWER (45.19 -> 46.7 ms: the wider patches of the 96 / 192-channel layers cost a resident block) --
-        // the LDS pipe is not what these kernels wait for.  Off by default; EAS_CONV_RS_PAD=1: the padded rows.
-        static const int rs_pad = eas_dev_env("EAS_CONV_RS_PAD") ? atoi(eas_dev_env("EAS_CONV_RS_PAD")) : 0;
-        if (rs_pad && ksize == 3 && stride == 1 && g.Wo % 32 != 0) g.RS += (16 - ((g.RS - g.Wo) % 16)) % 16;
-    }
-    g.pad_t = g.pad_l = pad;
-    g.ext_h = ksize;
-    for (int t = 0; t < ksize * ksize; ++t) g.tap_off[t] = (t / ksize) * g.RS + (t % ksize);
-    g.oH = g.Ho; g.oW = g.Wo; g.os = 1; g.oph = g.opw = 0;
-    g.MT = (Cout + 31) / 32;
-    g.KSTEPS = (Cin + 15) / 16;
-    g.total_rows = NI * g.Ho;
-    g.Wst = Wi; g.gx0 = 0; g.qshift = 0; g.parts = 1;
-    static const int dbg = eas_dev_env("EAS_CONV_DBG") ? atoi(eas_dev_env("EAS_CONV_DBG")) : 0;
-    g.dbg = dbg;
     g.stats = stats; g.stats_nb = stats_nb;
     g.act = act;
     if (bna) g.bna = *bna;
@@ -332,24 +255,11 @@ static int conv_fwd_impl(const float* x, const void* packed_w, const float* bias
                             : dispatch_tile<TAPS_, S_, 1, CCH_, 2>(x, wp, bias, y, inexact_flag, g, st))                          \
                       : (v4 ? dispatch_tile<TAPS_, S_, 3, CCH_, 4>(x, wp, bias, y, inexact_flag, g, st)                           \
                             : dispatch_tile<TAPS_, S_, 3, CCH_, 2>(x, wp, bias, y, inexact_flag, g, st))
-    const ConvGeom g_full = g;
     static const int force_parts = eas_dev_env("EAS_CONV_PARTS") ? atoi(eas_dev_env("EAS_CONV_PARTS")) : 0;   // development: force column parts
+    static const int rs_pad = eas_dev_env("EAS_CONV_RS_PAD") ? atoi(eas_dev_env("EAS_CONV_RS_PAD")) : 0;      // development (conv3_base_geom)
     for (int parts = force_parts > 0 ? force_parts : 1; parts <= 8 && rc == EAS_ERR_UNSUPPORTED && ksize == 3; parts *= 2) {
-        g = g_full;
-        if (parts > 1) {
-            // column parts: the tile is Wo/parts output columns wide; the staged row holds their input columns plus one staging
-            // unit (VEC columns, aligned) of halo on either side, all fetched like interior units (zero page outside the image)
-            const int hv = v4 ? 4 : 2;
-            if (g_full.Wo % parts != 0 || ((g_full.Wo / parts) * stride) % hv != 0) continue;
-            g.parts = parts;
-            g.Wo = g_full.Wo / parts;
-            g.Wst = g.Wo * stride + 2 * hv;
-            g.RS = g.Wst;
-            g.pad_l = 0;
-            g.gx0 = -hv;
-            g.qshift = hv - pad;
-            for (int t = 0; t < ksize * ksize; ++t) g.tap_off[t] = (t / ksize) * g.RS + (t % ksize);
-        }
+        // whole rows first; rows whose patch does not fit LDS in one piece in 2, 4 or 8 column parts
+        if (!conv3_base_geom(g, NI, Cin, Cout, Hi, Wi, stride, parts, v4 ? 4 : 2, rs_pad != 0)) continue;
         if (bna) rc = eas_conv3x3_bna_dispatch(stride, v4 ? 1 : 0, x, wp, query ? nullptr : y, &g, st);
         else if (stride == 1) { EAS_CONV_DISPATCH(9, 1, 16); }
         else { EAS_CONV_DISPATCH(9, 2, 16); }
@@ -433,131 +343,6 @@ int eas_conv_fwd_planes(const void* x_planes, const void* packed_w, const float*
 // real-valued inputs wider than ~280 pixels: stem / dark2.0 of the 384x640 canvas) run in 2, 4 or 8 column parts.
 int eas_conv_fwd_supported(int NI, int Cin, int Cout, int Hi, int Wi, int ksize, int stride, int x_terms) {
     return conv_fwd_impl(nullptr, nullptr, nullptr, nullptr, NI, Cin, Cout, Hi, Wi, ksize, stride, x_terms, nullptr, nullptr, true) == EAS_OK ? 1 : 0;
-}
-
-// grad_x[NI,Cin,Hi,Wi] of a stride-2 3x3 convolution (padding 1) from grad_y[NI,Cout,Ho,Wo] and the weights packed with
-// mode 2: four launches, one per parity class of the input pixel (1, 2, 2 and 4 taps), each a stride-1 tap-list
-// convolution over grad_y (general fp32, three bf16 terms) that writes every second row/column of grad_x.
-int eas_conv_dgrad_s2(const float* grad_y, const void* packed_w, float* grad_x, int NI, int Cin, int Cout, int Hi, int Wi, eas_stream_t stream) {
-    if (!grad_y || !packed_w || !grad_x || NI <= 0 || Cin <= 0 || Cout <= 0 || Hi <= 0 || Wi <= 0) return EAS_ERR_INVALID_ARG;
-    const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-    if (Cout % 8 != 0 || Wo % 2 != 0) return EAS_ERR_UNSUPPORTED;
-    EAS_CLEAR_ERR();
-    hipStream_t st = eas_s(stream);
-    static const int dbg = eas_dev_env("EAS_CONV_DBG") ? atoi(eas_dev_env("EAS_CONV_DBG")) : 0;
-    const int MT = (Cin + 31) / 32, KSTEPS = (Cout + 15) / 16;
-    const int cum[4] = {0, 1, 3, 5};
-    const bool v4 = Wo % 4 == 0;
-    S2Geoms sg{};
-    for (int cls = 0; cls < 4; ++cls) {
-        const int ph = cls >> 1, pw = cls & 1;
-        ConvGeom& g = sg.g[cls];
-        g.NI = NI; g.Cin = Cout; g.Cout = Cin; g.Hi = Ho; g.Wi = Wo; g.Ho = Ho; g.Wo = Wo;
-        g.RS = Wo + pw;
-        g.pad_t = g.pad_l = 0;
-        g.ext_h = ph + 1;
-        for (int ih = 0; ih <= ph; ++ih)
-            for (int iw = 0; iw <= pw; ++iw) g.tap_off[ih * (pw + 1) + iw] = ih * g.RS + iw;
-        g.oH = Hi; g.oW = Wi; g.os = 2; g.oph = ph; g.opw = pw;
-        g.MT = MT; g.KSTEPS = KSTEPS;
-        g.total_rows = NI * Ho;
-        g.Wst = Wo; g.gx0 = 0; g.qshift = 0; g.parts = 1;
-        g.dbg = dbg;
-        sg.wp[cls] = (const bf16x8*)packed_w + (size_t)3 * MT * KSTEPS * 64 * cum[cls];
-    }
-    // development: EAS_S2_FORM=1 the class kernels in one launch (round 4), 0 = in four launches; default: the four classes in one tile
-    static const char form = eas_dev_env("EAS_S2_FORM") ? eas_dev_env("EAS_S2_FORM")[0] : 'c';
-    if (form == 'c') {
-        const int rc = eas_conv_dgrad_s2c_dispatch(grad_y, packed_w, grad_x, NI, Cin, Cout, Hi, Wi, st, false);
-        if (rc == EAS_OK) {
-            EAS_CHECK_LAUNCH();
-            return EAS_OK;
-        }
-        if (rc != EAS_ERR_UNSUPPORTED) return rc;
-    }
-    const int one_launch = form != '0';
-    if (one_launch) {
-        // one block shape for the four classes, a tile geometry per class (their staged patches differ: taps, channel chunk)
-        typedef int (*s2_fn)(const float*, float*, S2Geoms, hipStream_t);
-        struct Shape { int wvm, bn, threads, nit, wn; s2_fn f4, f2; };
-        const Shape shapes[14] = {
-            {2, 640, 512, 1, 5, launch_s2<1, 5, 2, 4, 4, 1>, launch_s2<1, 5, 2, 4, 2, 1>}, {4, 320, 512, 1, 5, launch_s2<1, 5, 4, 2, 4, 1>, launch_s2<1, 5, 4, 2, 2, 1>},
-            {8, 160, 512, 1, 5, launch_s2<1, 5, 8, 1, 4, 1>, launch_s2<1, 5, 8, 1, 2, 1>}, {1, 1280, 512, 1, 5, launch_s2<1, 5, 1, 8, 4, 1>, launch_s2<1, 5, 1, 8, 2, 1>},
-            {1, 640, 256, 2, 5, launch_s2<1, 5, 1, 4, 4, 2>, launch_s2<1, 5, 1, 4, 2, 2>}, {2, 320, 256, 2, 5, launch_s2<1, 5, 2, 2, 4, 2>, launch_s2<1, 5, 2, 2, 2, 2>},
-            {4, 160, 256, 2, 5, launch_s2<1, 5, 4, 1, 4, 2>, launch_s2<1, 5, 4, 1, 2, 2>},
-            {2, 384, 512, 1, 3, launch_s2<1, 3, 2, 4, 4, 1>, launch_s2<1, 3, 2, 4, 2, 1>}, {4, 192, 512, 1, 3, launch_s2<1, 3, 4, 2, 4, 1>, launch_s2<1, 3, 4, 2, 2, 1>},
-            {8, 96, 512, 1, 3, launch_s2<1, 3, 8, 1, 4, 1>, launch_s2<1, 3, 8, 1, 2, 1>}, {1, 768, 512, 1, 3, launch_s2<1, 3, 1, 8, 4, 1>, launch_s2<1, 3, 1, 8, 2, 1>},
-            {1, 384, 256, 2, 3, launch_s2<1, 3, 1, 4, 4, 2>, launch_s2<1, 3, 1, 4, 2, 2>}, {2, 192, 256, 2, 3, launch_s2<1, 3, 2, 2, 4, 2>, launch_s2<1, 3, 2, 2, 2, 2>},
-            {4, 96, 256, 2, 3, launch_s2<1, 3, 4, 1, 4, 2>, launch_s2<1, 3, 4, 1, 2, 2>}};
-        static const int cch[4] = {64, 32, 32, 16};
-        static const double work[4] = {0.45, 0.65, 0.65, 1.0};      // relative block time of the classes (1, 2, 2, 4 taps)
-        const int vec = v4 ? 4 : 2;
-        int best = -1;
-        double best_cost = 0.0;
-        S2Geoms best_sg = sg;
-        double four[4] = {1e30, 1e30, 1e30, 1e30};      // the same model's cost of each class as a launch of its own (its best shape)
-        for (int i = 0; i < 14; ++i) {
-            const Shape& c = shapes[i];
-            if ((c.wvm - 1) * 32 >= Cin && c.wvm != 1) continue;
-            S2Geoms t = sg;
-            bool ok = true;
-            double load = 0.0;
-            size_t lds_max = 0;
-            for (int cls = 0; cls < 4 && ok; ++cls) {
-                ConvGeom& g = t.g[cls];
-                const int nbuf = g.KSTEPS * 16 <= cch[cls] ? 1 : 2;
-                bool fits = false;
-                for (int cap = c.bn; cap >= g.Wo && !fits; cap -= 32) {
-                    g.RT = pick_rows(g.Ho, g.Wo, cap);
-                    if (g.RT == 0) break;
-                    g.rows_seg = g.RT < g.Ho ? g.RT : g.Ho;
-                    g.nseg = g.RT / g.rows_seg;
-                    g.rows_in = (g.rows_seg - 1) + g.ext_h;
-                    g.Q = g.nseg * g.rows_in * g.RS;
-                    fits = (size_t)nbuf * g.Q * cch[cls] * 2 * 3 <= 160 * 1024 && g.nseg * g.rows_in * (g.Wst / vec) * (cch[cls] / 8) <= c.nit * c.threads;
-                    cap = g.RT * g.Wo;
-                }
-                ok = fits;
-                if (!ok) break;
-                const size_t l = (size_t)nbuf * g.Q * cch[cls] * 2 * 3;
-                lds_max = l > lds_max ? l : lds_max;
-                const long blocks = (long)((g.total_rows + g.RT - 1) / g.RT) * ((MT + c.wvm - 1) / c.wvm);
-                load += work[cls] * (double)blocks;
-                const int bpc1 = c.threads == 512 ? 1 : (2 * l <= 160 * 1024 ? 2 : 1);
-                const double alone = (double)((blocks + 256 * bpc1 - 1) / (256 * bpc1)) * (c.threads == 512 ? 1.27 : (bpc1 == 2 ? 1.2 : 1.0)) *
-                                     (0.3 + 0.7 * c.wn / 5.0) * work[cls];
-                if (alone < four[cls]) four[cls] = alone;
-            }
-            if (!ok) continue;
-            const int bpc = c.threads == 512 ? 1 : (2 * lds_max <= 160 * 1024 ? 2 : 1);
-            const double round_cost = (c.threads == 512 ? 1.27 : (bpc == 2 ? 1.2 : 1.0)) * (0.3 + 0.7 * c.wn / 5.0);
-            double rounds = load / (256.0 * bpc);
-            if (rounds < 1.0) rounds = 1.0;
-            const double cost = rounds * round_cost;
-            if (best < 0 || cost < best_cost) {
-                best = i; best_cost = cost; best_sg = t;
-            }
-        }
-        // large maps: every class fills the chip by itself and does better with a tile of its own -> four launches
-        if (best >= 0 && four[0] + four[1] + four[2] + four[3] < 0.97 * best_cost) best = -1;
-        if (best >= 0) {
-            const int rc = v4 ? shapes[best].f4(grad_y, grad_x, best_sg, st) : shapes[best].f2(grad_y, grad_x, best_sg, st);
-            if (rc != EAS_OK) return rc;
-            EAS_CHECK_LAUNCH();
-            return EAS_OK;
-        }
-    }
-    for (int cls = 0; cls < 4; ++cls) {
-        const ConvGeom& g = sg.g[cls];
-        const bf16x8* wp = sg.wp[cls];
-        int rc;
-        if (cls == 0) rc = v4 ? dispatch_tile<1, 1, 3, 64, 4>(grad_y, wp, nullptr, grad_x, nullptr, g, st) : dispatch_tile<1, 1, 3, 64, 2>(grad_y, wp, nullptr, grad_x, nullptr, g, st);
-        else if (cls == 3) rc = v4 ? dispatch_tile<4, 1, 3, 16, 4>(grad_y, wp, nullptr, grad_x, nullptr, g, st) : dispatch_tile<4, 1, 3, 16, 2>(grad_y, wp, nullptr, grad_x, nullptr, g, st);
-        else rc = v4 ? dispatch_tile<2, 1, 3, 32, 4>(grad_y, wp, nullptr, grad_x, nullptr, g, st) : dispatch_tile<2, 1, 3, 32, 2>(grad_y, wp, nullptr, grad_x, nullptr, g, st);
-        if (rc != EAS_OK) return rc;
-        EAS_CHECK_LAUNCH();
-    }
-    return EAS_OK;
 }
 
 }  // extern "C"

@@ -561,6 +561,133 @@ __global__ __launch_bounds__(64 * WVM * WVN, 2) void conv_fwd_mfma_kernel(const 
                                                                          (int)blockIdx.y, (int)gridDim.x);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Host side of the tiles: every rule the planners of conv_mfma.hip, conv_s2d.hip, conv_group.hip and conv_lif_mfma.hip share is stated
+// here once -- base geometry, rows of a tile, the fit test, the shrink loop, the cost of a round of blocks, launch preparation.
+
+constexpr size_t kConvLdsMax = 160 * 1024;      // LDS of a CU = the dynamic shared memory the kernels ask for
+constexpr int kFdivRange = 1 << 20;             // fdiv: numerators and divisors below this
+
+static inline int conv_dev_dbg() {              // development ablation switches (ConvGeomCore::dbg)
+    static const int dbg = eas_dev_env("EAS_CONV_DBG") ? atoi(eas_dev_env("EAS_CONV_DBG")) : 0;
+    return dbg;
+}
+
+// Base geometry of a 3x3 / stride S / padding 1 problem, before a tile is chosen.  parts > 1: the column-part variant -- the tile is
+// Wo / parts output columns wide; the staged row holds their input columns plus one staging unit (hv columns, aligned) of halo on either
+// side, all fetched like interior units (zero page outside the image); false = the row does not cut into such parts.
+// rs_pad (development, EAS_CONV_RS_PAD): staged rows padded to (RS - Wo) % 16 == 0 where a fragment's lanes cross a staged-row boundary --
+// conflict-free ds_read_b128 for 14 more staged columns per row; measured without effect on config 2 and SLOWER on config 3 (45.19 ->
+// 46.7 ms: the wider patches cost a resident block), the LDS pipe is not what these kernels wait for.
+// The one-tile stride-2 input gradient (conv_s2d.hip) has class-major taps on rows of Wo + 1 and keeps a set-up of its own.
+static bool conv3_base_geom(ConvGeomCore& g, int NI, int Cin, int Cout, int Hi, int Wi, int S, int parts = 1, int hv = 0, bool rs_pad = false) {
+    g.NI = NI; g.Cin = Cin; g.Cout = Cout; g.Hi = Hi; g.Wi = Wi;
+    g.Ho = (Hi - 1) / S + 1;
+    g.Wo = (Wi - 1) / S + 1;
+    g.RS = Wi + 2;
+    if (rs_pad && S == 1 && g.Wo % 32 != 0) g.RS += (16 - ((g.RS - g.Wo) % 16)) % 16;
+    g.pad_t = g.pad_l = 1;
+    g.ext_h = 3;
+    g.oH = g.Ho; g.oW = g.Wo; g.os = 1; g.oph = g.opw = 0;
+    g.MT = (Cout + 31) / 32;
+    g.KSTEPS = (Cin + 15) / 16;
+    g.total_rows = NI * g.Ho;
+    g.Wst = Wi; g.gx0 = 0; g.qshift = 0; g.parts = 1;
+    if (parts > 1) {
+        if (g.Wo % parts != 0 || ((g.Wo / parts) * S) % hv != 0) return false;
+        g.parts = parts;
+        g.Wo /= parts;
+        g.Wst = g.Wo * S + 2 * hv;
+        g.RS = g.Wst;
+        g.pad_l = 0;
+        g.gx0 = -hv;
+        g.qshift = hv - 1;
+    }
+    for (int t = 0; t < 9; ++t) g.tap_off[t] = (t / 3) * g.RS + (t % 3);
+    g.dbg = conv_dev_dbg();
+    return true;
+}
+
+// rows per tile: the largest RT with RT*Wo <= BN such that tiles never straddle an image boundary mid-image
+static int pick_rows(int Ho, int Wo, int BN) {
+    int best = 0;
+    const int maxrt = BN / Wo;
+    for (int rt = 1; rt <= maxrt; ++rt)
+        if (Ho % rt == 0 || rt % Ho == 0) best = rt;
+    return best;
+}
+
+// The rows of a tile of at most `cap` pixels: RT, bpi, rows_seg, nseg_s, nseg, rows_in, Q of t (base geometry filled in).  Whole rows that
+// never straddle an image mid-image (pick_rows); ragged: where whole images do not fit, every image by itself in bpi tiles of RT rows, the
+// last one short.  T: time slices staged side by side (the time-major fused eval step), else 1.  false = no row fits.
+static bool conv_tile_rows(ConvGeomCore& t, int cap, int S, bool ragged = false, int T = 1) {
+    const int maxrt = cap / t.Wo;
+    t.bpi = 0;
+    if (!ragged || maxrt >= t.Ho) t.RT = pick_rows(t.Ho, t.Wo, cap);
+    else {
+        t.RT = maxrt;
+        t.bpi = (t.Ho + t.RT - 1) / t.RT;
+        t.RT = (t.Ho + t.bpi - 1) / t.bpi;       // the same tile count with evener tiles
+    }
+    if (t.RT == 0) return false;
+    t.rows_seg = t.RT < t.Ho ? t.RT : t.Ho;
+    t.nseg_s = t.RT / t.rows_seg;
+    t.nseg = T * t.nseg_s;
+    t.rows_in = (t.rows_seg - 1) * S + t.ext_h;
+    t.Q = t.nseg * t.rows_in * t.RS;
+    return true;
+}
+
+// The fit test: LDS bytes of the staged patch (nbuf buffers, CCH channels per chunk, XT terms) when it fits the CU, the chunk's staging
+// items in units of `vec` pixels fit `slots` (items per thread x threads) and the geometry stays in fdiv's range; 0 = the tile does not fit.
+// What passes here launches: eas_*_supported and the launch ask the same rule.
+static size_t conv_tile_fit(const ConvGeomCore& t, int nbuf, int CCH, int XT, int vec, int slots) {
+    const size_t lds = (size_t)nbuf * t.Q * CCH * 2 * XT;
+    const int units = t.nseg * t.rows_in * (t.Wst / vec);
+    if (lds > kConvLdsMax || units * (CCH / 8) > slots) return 0;
+    if (t.total_rows >= kFdivRange || units >= kFdivRange) return 0;
+    return lds;
+}
+
+// The shrink loop: the largest tile of at most bn pixels that fits, the cap going down by one 32-pixel fragment below the last tile tried;
+// returns its LDS bytes, 0 = none
+static size_t conv_tile_shrink(ConvGeomCore& t, int bn, int S, int nbuf, int CCH, int XT, int vec, int slots, bool ragged = false, int T = 1) {
+    for (int cap = bn; cap >= t.Wo; cap -= 32) {
+        if (!conv_tile_rows(t, cap, S, ragged, T)) return 0;
+        if (const size_t lds = conv_tile_fit(t, nbuf, CCH, XT, vec, slots)) return lds;
+        cap = t.RT * t.Wo;
+    }
+    return 0;
+}
+
+// grid of a planned tile: pixel tiles x blocks of m_tiles M-tiles x column parts
+static dim3 conv_tile_grid(const ConvGeomCore& g, int m_tiles) {
+    return dim3(g.bpi ? g.NI * g.bpi : (g.total_rows + g.RT - 1) / g.RT, (g.MT + m_tiles - 1) / m_tiles, g.parts);
+}
+
+// Cost of a round of blocks (measured on MI355X, scripts/dev_conv.py, scripts/dev_conv_calls.py).
+// Resident blocks per CU: one 8-wave block, or two 4-wave blocks when their LDS fits twice (independent barriers overlap one block's
+// prologue / epilogue with the other's MFMA phase: cheaper per round than one 8-wave block).
+static int conv_blocks_per_cu(int threads, size_t lds) { return threads == 512 ? 1 : (2 * lds <= kConvLdsMax ? 2 : 1); }
+// two co-resident blocks cost 1.2 rounds of one -- but only when there are more blocks than CUs: a grid of <= 256 blocks puts one block
+// on a CU whatever its LDS size
+static double conv_pair_factor(double blocks) { return blocks > 256 ? 1.2 : 1.0; }
+// a round of 8-wave blocks costs ~1.27x a round of lone 4-wave blocks
+static double conv_round_factor(int threads, int bpc, double blocks) { return threads == 512 ? 1.27 : (bpc == 2 ? conv_pair_factor(blocks) : 1.0); }
+// A block's time is a fixed part (prologue, first patch, epilogue) plus its MFMA work, which goes with the wn pixel tiles of a wave whatever
+// part of them is valid (full_wn: the widest wave tile of the family).  lat: a step's MFMAs (cycles_per_tile each: 96 with one-term
+// inputs, 192 with three) hide the ~450-cycle latency of the next step's weight fragments only when they last that long -- with spike
+// inputs a 3-tile wave (288 MFMA cycles per step) waits on every step and costs nearly as much as a 5-tile wave (dark5.m.conv2: 71 us
+// against 62 us for the 160-pixel shape); 0 = no floor.
+static double conv_step_lat() {
+    static const double lat = eas_dev_env("EAS_CONV_STEP_LAT") ? atof(eas_dev_env("EAS_CONV_STEP_LAT")) : 450.0;   // development
+    return lat;
+}
+static double conv_block_time(int wn, double full_wn, double cycles_per_tile, double lat) {
+    const double cycles = wn * cycles_per_tile;
+    return 0.3 + 0.7 * ((cycles > lat ? cycles : lat) / (full_wn * cycles_per_tile));
+}
+
 static void conv_geom_magics(ConvGeomCore& g, int VEC, int CCH) {
     const int units_row = g.Wst / VEC, units_seg = g.rows_in * units_row, units = g.nseg * units_seg;
     const int rows = g.nseg * g.rows_in, per_row = (g.RS - g.Wst) * (CCH * 2 / 16);
@@ -569,37 +696,42 @@ static void conv_geom_magics(ConvGeomCore& g, int VEC, int CCH) {
     g.m_hrow = fdiv_magic(per_row); g.m_rows = fdiv_magic(rows);
 }
 
-template <int TAPS, int S, int XT, int WM, int WN, int WVM, int WVN, int CCH, int VEC, int NIT, bool PL = false, int LM = 0>
-int launch_fwd(const float* x, const bf16x8* wp, const float* bias, float* y, int* inexact, ConvGeom g, hipStream_t st) {
-    auto kern = conv_fwd_mfma_kernel<TAPS, S, XT, WM, WN, WVM, WVN, CCH, VEC, NIT, PL, LM>;
-    const int nbuf = (g.KSTEPS * 16 <= CCH || g.single) ? 1 : 2;      // one channel chunk: the second (prefetch) buffer is never used
-    size_t lds = (size_t)nbuf * g.Q * CCH * 2 * XT;
-    if (lds > 160 * 1024) return EAS_ERR_UNSUPPORTED;
-    if (g.stats && lds < (size_t)WVM * WVN * (EAS_STATS_SCRATCH * sizeof(float) + WM * 64 * sizeof(double)))
-        lds = (size_t)WVM * WVN * (EAS_STATS_SCRATCH * sizeof(float) + WM * 64 * sizeof(double));
-    static bool attr_set = false;
+// Launch preparation of a planned tile: the kernel's dynamic LDS limit (once per kernel: attr_set is the launcher's flag for it) and the
+// division magics of the geometry.  The plan passed conv_tile_fit, so nothing is refused here.
+static int conv_launch_prep(const void* kern, bool& attr_set, ConvGeomCore& g, int VEC, int CCH) {
     if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EAS_ERR_LAUNCH;
+        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLdsMax) != hipSuccess) return EAS_ERR_LAUNCH;
         attr_set = true;
     }
-    if (g.total_rows >= (1 << 20) || g.nseg * g.rows_in * (g.Wst / VEC) >= (1 << 20)) return EAS_ERR_UNSUPPORTED;     // fdiv range
     conv_geom_magics(g, VEC, CCH);
-    dim3 grid(g.bpi ? g.NI * g.bpi : (g.total_rows + g.RT - 1) / g.RT, (g.MT + WVM * WM - 1) / (WVM * WM), g.parts);
+    return EAS_OK;
+}
+
+// development (EAS_CONV_PLAN): one line per planned tile, from the planners' common exit -- before a query returns, so without a GPU
+static void conv_plan_note(const char* who, int cand, int vec, const ConvGeomCore& g, const dim3& grid, size_t lds) {
+    static const bool on = eas_dev_env("EAS_CONV_PLAN") != nullptr;
+    if (on)
+        fprintf(stderr, "conv plan %s: cand %d vec %d RT %d bpi %d nseg %d Q %d single %d parts %d grid %u %u %u lds %zu | rows %d/%d RS %d Wst %d gx0 %d "
+                "qshift %d pad %d/%d taps %d..%d out %dx%d/%d rows %d MT %d KSTEPS %d\n", who, cand, vec, g.RT, g.bpi, g.nseg, g.Q, g.single, g.parts, grid.x,
+                grid.y, grid.z, lds, g.rows_seg, g.rows_in, g.RS, g.Wst, g.gx0, g.qshift, g.pad_t, g.pad_l, g.tap_off[1], g.tap_off[8], g.oH, g.oW, g.os,
+                g.total_rows, g.MT, g.KSTEPS);
+}
+
+template <int TAPS, int S, int XT, int WM, int WN, int WVM, int WVN, int CCH, int VEC, int NIT, bool PL = false, int LM = 0>
+int launch_fwd(const float* x, const bf16x8* wp, const float* bias, float* y, int* inexact, ConvGeom g, size_t lds, hipStream_t st) {
+    auto kern = conv_fwd_mfma_kernel<TAPS, S, XT, WM, WN, WVM, WVN, CCH, VEC, NIT, PL, LM>;
+    static bool attr_set = false;
+    if (const int rc = conv_launch_prep((const void*)kern, attr_set, g, VEC, CCH)) return rc;
+    if (g.stats && lds < (size_t)WVM * WVN * (EAS_STATS_SCRATCH * sizeof(float) + WM * 64 * sizeof(double)))
+        lds = (size_t)WVM * WVN * (EAS_STATS_SCRATCH * sizeof(float) + WM * 64 * sizeof(double));
+    const dim3 grid = conv_tile_grid(g, WVM * WM);
     if (g.stats && (int)(grid.x * g.parts) != g.stats_nb) return EAS_ERR_INVALID_ARG;
     EAS_LAUNCH(kern, grid, dim3(64 * WVM * WVN), lds, st, x, wp, bias, y, inexact, g);
     return EAS_OK;
 }
 
-// rows per tile: the largest RT with RT*Wo <= BN such that tiles never straddle an image boundary mid-image
-int pick_rows(int Ho, int Wo, int BN) {
-    int best = 0;
-    const int maxrt = BN / Wo;
-    for (int rt = 1; rt <= maxrt; ++rt)
-        if (Ho % rt == 0 || rt % Ho == 0) best = rt;
-    return best;
-}
-
-typedef int (*launch_fn)(const float*, const bf16x8*, const float*, float*, int*, ConvGeom, hipStream_t);
+// (x, packed weights, bias, y, inexact flag, planned geometry, the plan's LDS bytes, stream)
+typedef int (*launch_fn)(const float*, const bf16x8*, const float*, float*, int*, ConvGeom, size_t, hipStream_t);
 
 
 // pixel blocks per channel (grid.x * parts) of the tile the last dispatch_tile call of this thread chose: the number of statistics
@@ -624,12 +756,10 @@ int dispatch_tile(const float* x, const bf16x8* wp, const float* bias, float* y,
         {1, 8, 96, 512, N8, 3, launch_fwd<TAPS, S, XT, 1, 3, 8, 1, CCH, VEC, N8, PL, LM>}, {1, 1, 768, 512, N8, 3, launch_fwd<TAPS, S, XT, 1, 3, 1, 8, CCH, VEC, N8, PL, LM>},
         {1, 1, 384, 256, N4, 3, launch_fwd<TAPS, S, XT, 1, 3, 1, 4, CCH, VEC, N4, PL, LM>}, {1, 2, 192, 256, N4, 3, launch_fwd<TAPS, S, XT, 1, 3, 2, 2, CCH, VEC, N4, PL, LM>},
         {1, 4, 96, 256, N4, 3, launch_fwd<TAPS, S, XT, 1, 3, 4, 1, CCH, VEC, N4, PL, LM>}};
-    // cost model (measured on MI355X, scripts/dev_conv.py, scripts/dev_conv_calls.py): one block per CU; a round of 8-wave blocks costs
-    // ~1.27x a round of 4-wave blocks; a block's time is a fixed part (prologue, first patch, epilogue) plus its MFMA work, which
-    // goes with WN whatever part of the pixel tile is valid
     int best = -1;
     double best_cost = 0.0;
     int best_valid = 0;
+    size_t best_lds = 0;
     ConvGeom best_g = g;
     static const int force = eas_dev_env("EAS_CONV_TILE") ? atoi(eas_dev_env("EAS_CONV_TILE")) : -1;   // development: force a candidate
     static const int ncand = eas_dev_env("EAS_CONV_NCAND") ? atoi(eas_dev_env("EAS_CONV_NCAND")) : 14;  // development: 7 = the 160-pixel wave tiles only
@@ -645,42 +775,23 @@ int dispatch_tile(const float* x, const bf16x8* wp, const float* bias, float* y,
         const Cand& c = cands[i];
         if (force >= 0 && i != force) continue;
         if (mode == 1 && (XT != 3 || nchunks < 2 || nchunks > single_nch)) continue;      // spike-input layers: 76 -> 84 us (the patch is a third)
-        const int nbuf = (nchunks == 1 || mode == 1) ? 1 : 2;
+        const int nbuf = (nchunks == 1 || mode == 1) ? 1 : 2;      // one channel chunk: the second (prefetch) buffer is never used
         if ((c.wvm * c.wm - 1) * 32 >= g.Cout && !(c.wvm == 1 && c.wm == 1)) continue;   // every wave row (and M-tile) has channels to compute
         ConvGeom t = g;
         t.single = mode;
-        bool fits = false;
-        for (int cap = c.bn; cap >= g.Wo && !fits; cap -= 32) {   // shrink the pixel tile until patch + staging slots fit
-            t.RT = pick_rows(g.Ho, g.Wo, cap);
-            if (t.RT == 0) break;
-            t.rows_seg = t.RT < g.Ho ? t.RT : g.Ho;
-            t.nseg = t.RT / t.rows_seg;
-            t.rows_in = (t.rows_seg - 1) * S + g.ext_h;
-            t.Q = t.nseg * t.rows_in * t.RS;
-            fits = (size_t)nbuf * t.Q * CCH * 2 * XT <= 160 * 1024 && t.nseg * t.rows_in * (g.Wst / VEC) * (CCH / 8) <= c.nit * c.threads;
-            cap = t.RT * g.Wo;
-        }
-        if (!fits) continue;
-        const long blocks = (long)((g.total_rows + t.RT - 1) / t.RT) * ((g.MT + c.wvm * c.wm - 1) / (c.wvm * c.wm)) * g.parts;
-        // resident blocks per CU: one 8-wave block, or two 4-wave blocks when their LDS fits twice (independent barriers
-        // overlap one block's prologue/epilogue with the other's MFMA phase: cheaper per round than one 8-wave block)
-        const size_t lds_bytes = (size_t)nbuf * t.Q * CCH * 2 * XT;
-        int bpc = c.threads == 512 ? 1 : (2 * lds_bytes <= 160 * 1024 ? 2 : 1);
+        const size_t lds = conv_tile_shrink(t, c.bn, S, nbuf, CCH, XT, VEC, c.nit * c.threads);
+        if (!lds) continue;
+        const dim3 grid = conv_tile_grid(t, c.wvm * c.wm);
+        const long blocks = (long)grid.x * grid.y * grid.z;
+        int bpc = conv_blocks_per_cu(c.threads, lds);
         if (mode == 1) {
             // worth it only where it buys the second resident block (launch bounds keep the registers of two blocks per CU available)
-            if (2 * lds_bytes > 160 * 1024 || 2 * (2 * lds_bytes) <= 160 * 1024) continue;
+            if (2 * lds > kConvLdsMax || 2 * (2 * lds) <= kConvLdsMax) continue;
             bpc = 2;
         }
-        // (two co-resident 4-wave blocks cost 1.2 rounds of one -- but only when there are more blocks than CUs: a grid of <= 256 blocks
-        // puts one block on a CU whatever its LDS size)
-        // a step's MFMAs (3 * WN with one-term inputs, 6 * WN with three) hide the ~450-cycle latency of the next step's weight
-        // fragments only when they last that long: with spike inputs a 3-tile wave (288 MFMA cycles per step) waits on every step and
-        // costs nearly as much as a 5-tile wave (dark5.m.conv2: 71 us against 62 us for the 160-pixel shape the old model ranked behind)
-        static const double lat = eas_dev_env("EAS_CONV_STEP_LAT") ? atof(eas_dev_env("EAS_CONV_STEP_LAT")) : 450.0;   // development
-        const double per_tile = XT == 1 ? 96.0 : 192.0;
-        const double mfma_part = (c.wn * per_tile > lat ? c.wn * per_tile : lat) / (5.0 * per_tile);
-        const double round_cost = (c.threads == 512 ? 1.27 : (bpc == 2 && blocks > 256 ? 1.2 : 1.0)) * (0.3 + 0.7 * mfma_part) *
-                                  (mode == 1 ? single_pen * (c.threads == 512 && blocks > 256 ? 1.2 : 1.0) : 1.0);
+        // the single-buffer mode pays its exposed patch writes, and two co-resident 8-wave blocks the pair's share on top of their own
+        const double round_cost = conv_round_factor(c.threads, bpc, (double)blocks) * conv_block_time(c.wn, 5.0, XT == 1 ? 96.0 : 192.0, conv_step_lat()) *
+                                  (mode == 1 ? single_pen * (c.threads == 512 ? conv_pair_factor((double)blocks) : 1.0) : 1.0);
         const double cost = (double)((blocks + 256 * bpc - 1) / (256 * bpc)) * round_cost;
         // ties: the larger valid pixel count; among grids of lone blocks (<= 256) first the shape with more waves along the channels
         // (they share one staged pixel patch: the smaller patch per block is the shorter prologue; 8x10 head layers: 35-38 us against
@@ -689,13 +800,15 @@ int dispatch_tile(const float* x, const bf16x8* wp, const float* bias, float* y,
         static const int tie_wvm = eas_dev_env("EAS_CONV_TIE_WVM") ? atoi(eas_dev_env("EAS_CONV_TIE_WVM")) : 1;        // development: 0 = lone blocks only
         const int rank = ((blocks <= 256 || tie_wvm) ? c.wvm * 4096 : 0) + (valid < 4096 ? valid : 4095);
         if (best < 0 || cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && rank > best_valid)) {
-            best = i; best_cost = cost; best_valid = rank; best_g = t;
+            best = i; best_cost = cost; best_valid = rank; best_g = t; best_lds = lds;
         }
     }
     if (best < 0) return EAS_ERR_UNSUPPORTED;
-    tl_pixel_blocks = ((best_g.total_rows + best_g.RT - 1) / best_g.RT) * best_g.parts;
+    const dim3 grid = conv_tile_grid(best_g, cands[best].wvm * cands[best].wm);
+    tl_pixel_blocks = grid.x * best_g.parts;
+    conv_plan_note("fwd", best, VEC, best_g, grid, best_lds);
     if (!y) return EAS_OK;                       // geometry query (eas_conv_fwd_supported): a tile exists, nothing is launched
-    return cands[best].fn(x, wp, bias, y, inexact, best_g, st);
+    return cands[best].fn(x, wp, bias, y, inexact, best_g, best_lds, st);
 }
 
 }  // namespace

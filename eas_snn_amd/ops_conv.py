@@ -536,19 +536,20 @@ def conv_route(x_shape, Cout, k, stride, x_terms):
       Ho, Wo   the output size
       fwd      eas_conv_fwd has a tile (False: the layer keeps the library convolution)
       dgrad    1 / 2: the input gradient runs on the kernel that reads this packing mode (``dgrad_mode``) and has a tile there; None: library
+               (stride 2: rows wider than 512 pixels among others -- eas_conv_dgrad_s2_supported is the launch's own rule)
       wgrad    the weight gradient runs on the matrix cores
-    The stem's small input gradient, ``needs_input_grad`` and the run-time fallback of eas_conv_dgrad_s2 stay with ``_ConvFn.backward``."""
+    The stem's small input gradient and ``needs_input_grad`` stay with ``_ConvFn.backward``."""
     NI, Cin, H, W = x_shape
     key = (NI, Cin, Cout, H, W, k, stride, x_terms)
     r = _ROUTES.get(key)
     if r is None:
         L = _lib.lib()
         Ho, Wo = conv_out_size(H, W, k, stride)
-        # both input-gradient kernels walk grad_y [NI,Cout,Ho,Wo] with the stride-1 tiles of eas_conv_fwd (stride 2: even Wo, two columns wider)
+        # stride 1: eas_conv_fwd's stride-1 tiles over grad_y [NI,Cout,Ho,Wo]; stride 2: the one-tile kernel's own plan
         dgrad = dgrad_mode(k, stride, Cout)
-        if dgrad == 2 and Wo % 2:
+        if dgrad == 1 and not L.eas_conv_fwd_supported(NI, Cout, Cin, Ho, Wo, k, 1, 3):
             dgrad = None
-        if dgrad and not L.eas_conv_fwd_supported(NI, Cout, Cin, Ho, Wo + (2 if dgrad == 2 else 0), k, 1, 3):
+        if dgrad == 2 and not L.eas_conv_dgrad_s2_supported(NI, Cin, Cout, H, W):
             dgrad = None
         wgrad = L.eas_conv_wgrad_workspace_floats(*key) > 0         # 0: eas_conv_wgrad would refuse
         r = _ROUTES[key] = ConvRoute(Ho, Wo, bool(L.eas_conv_fwd_supported(*key)), dgrad, wgrad)
@@ -629,12 +630,10 @@ class _ConvFn(torch.autograd.Function):
             gx = torch.empty_like(x)
             fl = 2.0 * gy.numel() * Cin * 9
             pk = pack_mode(packs, 2, w)
-            try:
-                _call('eas_conv_fwd', 4 * (x.numel() + gy.numel()), _lib.lib().eas_conv_dgrad_s2, ptr(gy), ptr(pk), ptr(gx),
-                      x.shape[0], Cin, w.shape[0], x.shape[2], x.shape[3], stream(), flops=fl, issue_flops=6 * fl)
-                own_d = True
-            except _lib.EasHipError:        # no tile for this width (checked before anything is launched): library input gradient
-                gx = None
+            # (the route asked eas_conv_dgrad_s2_supported: a refusal here is an error, not a reason to fall back)
+            _call('eas_conv_fwd', 4 * (x.numel() + gy.numel()), _lib.lib().eas_conv_dgrad_s2, ptr(gy), ptr(pk), ptr(gx),
+                  x.shape[0], Cin, w.shape[0], x.shape[2], x.shape[3], stream(), flops=fl, issue_flops=6 * fl)
+            own_d = True
         if own_w:
             gw = conv_wgrad(x, gy, k, stride, x_terms, x_sp, defer=_can_defer(w), w=w)
         need_d = ctx.needs_input_grad[0] and not own_d

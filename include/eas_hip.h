@@ -497,10 +497,14 @@ typedef struct {
 } EasConvBnActEval;
 int eas_conv_bn_act_eval(const EasConvBnActEval* d, int* inexact_flag, eas_stream_t stream);
 
-/* Input gradient of a stride-2 3x3 convolution: grad_x[NI][Cin][Hi][Wi] from grad_y[NI][Cout][Ho][Wo] and the weights
- * packed with mode 2 (eas_conv_pack_weights), by parity class of the input pixel (1/2/2/4 taps per class). */
+/* Input gradient of a stride-2 3x3 convolution (padding 1): grad_x[NI][Cin][Hi][Wi] from grad_y[NI][Cout][Ho][Wo] and the weights
+ * packed with mode 2 (eas_conv_pack_weights).  ONE launch: a tile holds the four parity classes of the input pixel (1/2/2/4 taps per
+ * class) and writes whole lines of grad_x (csrc/conv_s2d.hip).  Needs Cout % 8 == 0, an even Wo of at most 256 (rows of up to 512
+ * pixels) and NI * Ho < 2^20; anything else returns EAS_ERR_UNSUPPORTED before a launch and leaves grad_x untouched.
+ * eas_conv_dgrad_s2_supported: 1 / 0 by the launch's own plan; needs no GPU. */
 int eas_conv_dgrad_s2(const float* grad_y, const void* packed_w, float* grad_x, int NI, int Cin, int Cout, int Hi, int Wi,
                       eas_stream_t stream);
+int eas_conv_dgrad_s2_supported(int NI, int Cin, int Cout, int Hi, int Wi);
 
 /* ABI 8.  Input gradient of a 3x3 stride-1 convolution (padding 1) with at most 8 input channels -- the stem of CSPDarknet
  * (yolox/models/darknet.py: BaseConv(in_channels = 8 sampler channels, 32) ahead of dark2), whose gradient flows on into the event sampler:

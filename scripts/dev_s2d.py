@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """development: eas_conv_dgrad_s2 on the stride-2 layers of config 2 (and a few odd geometries): error against an fp64 reference, a
-checksum of the result bits (the forms of the kernel must agree bit for bit: run once per EAS_S2_FORM with a DEV=1 library and compare
-the lines) and the HIP-event time per call.
+checksum of the result bits (to compare two builds of the library line by line) and the HIP-event time per call.
 
   python scripts/dev_s2d.py [--reps 20] [--small]"""
 import argparse

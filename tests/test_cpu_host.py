@@ -64,6 +64,25 @@ def test_weight_gradient_queries_say_zero_where_the_launch_refuses():
             assert 1 <= lib.eas_conv_wgrad_parts(NI, Cin, Cout, H, W, s, xt) <= 8, (NI, Cin, Cout, H, W, s, xt)
 
 
+def test_stride2_input_gradient_query_is_the_launch_rule_and_the_route_follows_it():
+    """eas_conv_dgrad_s2_supported is the plan eas_conv_dgrad_s2 launches by (conv_s2d.hip; no GPU needed): 1 for every row of the
+    fp64-compared GPU cases, 0 for an odd output width (Wo = 5), output channels that are no multiple of 8 (Cout = 12), rows wider than the
+    widest tile (Wo = 260 > 256) and NI * Ho beyond the range of the kernels' multiply-shift division (2^20; arguments only, nothing is
+    allocated).  ops.conv_route names the stride-2 kernel exactly where the query says 1."""
+    from test_gpu_kernels import S2_DGRAD_CASES
+    from eas_snn_amd import ops
+    lib = eas_snn_amd.hip_library()
+    refused = [(1, 8, 8, 4, 10), (1, 8, 12, 4, 8), (1, 8, 8, 2, 520), (1 << 19, 8, 8, 4, 8)]
+    assert len(S2_DGRAD_CASES) >= 13
+    for NI, Cin, Cout, H, W in S2_DGRAD_CASES:
+        assert lib.eas_conv_dgrad_s2_supported(NI, Cin, Cout, H, W) == 1, (NI, Cin, Cout, H, W)
+    for NI, Cin, Cout, H, W in refused:
+        assert lib.eas_conv_dgrad_s2_supported(NI, Cin, Cout, H, W) == 0, (NI, Cin, Cout, H, W)
+    for NI, Cin, Cout, H, W in S2_DGRAD_CASES + refused:
+        want = 2 if lib.eas_conv_dgrad_s2_supported(NI, Cin, Cout, H, W) else None
+        assert ops.conv_route((NI, Cin, H, W), Cout, 3, 2, 3).dgrad == want, (NI, Cin, Cout, H, W)
+
+
 def test_gfx950_code_object_only():
     out = subprocess.run(['/opt/rocm/lib/llvm/bin/clang-offload-bundler', '--list', '--type=o',
                           f'--input={eas_snn_amd._lib.LIB_PATH}'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout

@@ -1602,6 +1602,44 @@ def test_stride2_input_gradient_all_parity_classes_in_one_tile(dev, NI, Cin, Cou
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('NI,Cin,Cout,H,W', [(1, 8, 8, 4, 10), (1, 8, 12, 4, 8), (1, 8, 8, 2, 520)])
+def test_stride2_input_gradient_refuses_before_anything_is_launched(dev, NI, Cin, Cout, H, W):
+    """eas_conv_dgrad_s2 on an odd output width, on output channels that are no multiple of 8 and on rows wider than its widest tile
+    (Wo = 260): the unsupported status, and a grad_x filled with NaN beforehand is still all NaN"""
+    from eas_snn_amd import _lib, ops
+    L = _lib.lib()
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    gy = torch.randn(NI, Cout, Ho, Wo, device=dev)
+    pk = ops.conv_pack_weights(torch.randn(Cout, Cin, 3, 3, device=dev), 2)
+    gx = torch.full((NI, Cin, H, W), float('nan'), device=dev)
+    assert L.eas_conv_dgrad_s2_supported(NI, Cin, Cout, H, W) == 0
+    assert L.eas_conv_dgrad_s2(ops.ptr(gy), ops.ptr(pk), ops.ptr(gx), NI, Cin, Cout, H, W, ops.stream()) == -2      # EAS_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(gx).all()), 'a refused call wrote to grad_x'
+
+
+@pytest.mark.gpu
+def test_stride2_convolution_on_rows_wider_than_the_tile_takes_the_library_input_gradient(dev):
+    """ops.conv2d at stride 2 on 520-pixel rows (Wo = 260, wider than the 256 positions of the widest eas_conv_dgrad_s2 tile): the route
+    names the library's input gradient, no conv_dgrad_s2 kernel runs (kernel trace), and x.grad matches fp64 under the bound of the
+    stride-2 kernel's own test"""
+    import torch.nn as nn
+    from eas_snn_amd import ops
+    g = torch.Generator().manual_seed(5)
+    conv = nn.Conv2d(8, 8, 3, 2, 1).to(dev)
+    x = torch.randn(1, 8, 4, 520, generator=g).to(dev).requires_grad_(True)
+    gy = torch.randn(1, 8, 2, 260, generator=g).to(dev)
+    assert ops.conv_route(x.shape, 8, 3, 2, 3).dgrad is None
+    with ops.kernel_trace() as tr:
+        y = ops.conv2d(x, conv)
+        y.backward(gy)
+    assert y.shape == gy.shape and not any('conv_dgrad_s2' in k for k in tr.kernels), tr.kernels
+    ref = torch.nn.grad.conv2d_input(x.shape, conv.weight.detach().double(), gy.double(), stride=2, padding=1)
+    err = float((x.grad.double() - ref).abs().max() / ref.abs().max())
+    assert err < 1e-5, f'{err:.2e}'
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('NI,Cin,Ca,Cb,H,W,k,s,spikes', [(3, 64, 32, 0, 8, 10, 1, 1, False), (2, 128, 64, 64, 16, 20, 1, 1, False), (2, 32, 40, 0, 16, 20, 3, 1, False),
                                                        (2, 64, 64, 0, 32, 40, 3, 2, False), (64, 256, 128, 128, 8, 10, 3, 1, False), (4, 512, 256, 0, 8, 10, 1, 1, True),
                                                        (2, 96, 48, 48, 32, 40, 1, 1, False), (2, 24, 48, 0, 16, 160, 3, 1, False), (3, 128, 72, 56, 16, 20, 3, 1, True),
