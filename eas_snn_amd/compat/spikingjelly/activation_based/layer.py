@@ -85,15 +85,11 @@ class BatchNorm2d(nn.BatchNorm2d, base.StepModule):
             if residual is not None:
                 out = out + ops.dense(residual)
             return (out, ops.time_mean(out)) if want_mean else out
-        batch = self._use_batch_stats()
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            ops.bump_counter(self.num_batches_tracked)
+        st = ops.bn_state(self)
         a = node.lif_args()
-        update = batch and self.training and self.track_running_stats
         base = getattr(y_seq, '_eas_base', None)       # conv output shared by all T steps (identical input frames)
         spikes, v_out, mean = ops.bn_lif_multistep(
-            y_seq if base is None else base, self.weight, self.bias, self.running_mean if (update or not batch) else None,
-            self.running_var if (update or not batch) else None, batch, self.momentum if update else None, self.eps,
+            y_seq if base is None else base, self.weight, self.bias, st.running_mean, st.running_var, st.batch_stats, st.momentum, st.eps,
             node._v_in(y_seq[0]), a['w'], a['k_const'], a['v_th'], a['v_reset'], a['flags'], a['surrogate'], a['alpha'],
             want_mean=want_mean, t_bcast=0 if base is None else y_seq.shape[0], residual=residual, cat=cat,
             planes=planes)
@@ -121,17 +117,12 @@ def fused_pair(bn_a, node_a, bn_b, node_b, y12, cat_a=None, cat_b=None, planes_a
     as in ``fused_with``."""
     packs = []
     for bn, node, cat, planes in ((bn_a, node_a, cat_a, planes_a), (bn_b, node_b, cat_b, planes_b)):
-        batch = bn._use_batch_stats()
-        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
-            ops.bump_counter(bn.num_batches_tracked)
-        update = batch and bn.training and bn.track_running_stats
+        state = ops.bn_state(bn, replicas=1)
         a = node.lif_args()
-        state = (bn.running_mean if (update or not batch) else None, bn.running_var if (update or not batch) else None, bool(batch),
-                 None if not update or bn.momentum is None else float(bn.momentum), float(bn.eps))
-        cfg = (state, node._v_in(y12[0, :, :bn.num_features]), float(a['k_const']), float(a['v_th']), float(a['v_reset']), int(a['flags']),
-               ops.SURROGATE_IDS[a['surrogate']] if isinstance(a['surrogate'], str) else int(a['surrogate']), float(a['alpha']),
-               bool(ops.state_writeback()), cat, int(bn.num_features), bool(planes) and bn.num_features % 8 == 0)
-        packs.append((bn.weight, bn.bias, a['w'], cfg))
+        lay = ops.LifLayer(state, node._v_in(y12[0, :, :bn.num_features]), float(a['k_const']), float(a['v_th']), float(a['v_reset']),
+                           int(a['flags']), ops.SURROGATE_IDS[a['surrogate']] if isinstance(a['surrogate'], str) else int(a['surrogate']),
+                           float(a['alpha']), bool(ops.state_writeback()), cat, bool(planes) and bn.num_features % 8 == 0)
+        packs.append((bn.weight, bn.bias, a['w'], lay))
     sa, va, sb, vb = ops.bn_lif_pair(y12, packs[0], packs[1])
     if va is not None:
         node_a.v = va

@@ -258,32 +258,20 @@ class _BNSiLUGroupFn(torch.autograd.Function):
         ny, items = cfg['ny'], cfg['items']
         m = len(items)
         ys = [ops._f32c(t) for t in tensors[:ny]]
-        stats = tensors[ny:2 * ny]
+        stats_in = tensors[ny:2 * ny]
         gammas, betas = tensors[2 * ny:2 * ny + m], tensors[2 * ny + m:2 * ny + 2 * m]
+        L = _lib.lib()
         arr = (_lib.EasBnSiluFwdProblem * m)()
         outs, saved = [], []
         nbytes = 0
-        for j, (q, (yi, c0, state)) in enumerate(zip(arr, items)):
-            running_mean, running_var, use_batch_stats, momentum, eps, replicas = state
-            y = ys[yi]
-            N, Ct, H, W = y.shape
-            Cc, HW = gammas[j].shape[0], H * W
-            dev = y.device
-            assert use_batch_stats, 'grouped BatchNorm + SiLU: training-mode statistics (the eval path keeps the fused per-layer kernels)'
-            mean = torch.empty(Cc, dtype=torch.float32, device=dev)
-            invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
-            nb = stats[yi].numel() // (2 * Ct)
-            out = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
-            q.y = y.data_ptr() + 4 * c0 * HW
-            q.mean, q.invstd, q.gamma, q.beta, q.out = ptr(mean), ptr(invstd), ptr(gammas[j]), ptr(betas[j]), ptr(out)
-            q.N, q.C, q.HW, q.out_ctot, q.y_ctot = N, Cc, HW, 0, Ct
-            q.pending = _lib.EasBnPending(stats[yi].data_ptr() + 16 * c0 * nb, nb, int(replicas), float(N) * HW, float(eps),
-                                          float(momentum if momentum is not None else 0.0), ptr(running_mean) if momentum is not None else None,
-                                          ptr(running_var) if momentum is not None else None, nb)
+        for j, (yi, c0, state) in enumerate(items):
+            assert state.batch_stats, 'grouped BatchNorm + SiLU: training-mode statistics (the eval path keeps the fused per-layer kernels)'
+            p, out, stats, _ = ops._silu_fwd_problem(L, ys[yi], ys[yi].shape[1], c0, gammas[j], betas[j], state, handed=stats_in[yi])
+            arr[j] = _lib.EasBnSiluFwdProblem(*p)
             outs.append(out)
-            saved += [mean, invstd]
-            nbytes += 8 * N * Cc * HW
-        ops._call('eas_bn_silu_fwd', nbytes, _lib.lib().eas_bn_silu_fwd_group, arr, m, stream())
+            saved += stats
+            nbytes += 8 * p.N * p.C * p.HW
+        ops._call('eas_bn_silu_fwd', nbytes, L.eas_bn_silu_fwd_group, arr, m, stream())
         ctx.save_for_backward(*ys, *gammas, *betas, *saved)
         ctx.cfg = cfg
         return tuple(outs)
@@ -300,26 +288,16 @@ class _BNSiLUGroupFn(torch.autograd.Function):
         arr = (_lib.EasBnSiluBwdProblem * m)()
         keep, res_g, res_b = [], [], []
         nbytes = 0
-        for j, (q, (yi, c0, state)) in enumerate(zip(arr, items)):
-            y = ys[yi]
-            N, Ct, H, W = y.shape
-            Cc, HW = gammas[j].shape[0], H * W
-            g = gs[j]
+        for j, (yi, c0, _) in enumerate(items):
+            y, g = ys[yi], gs[j]
             if g is None:
-                g = torch.zeros((N, Cc, H, W), dtype=torch.float32, device=y.device)
-            ctot = ops._channel_slice_of4(g, Cc) if (g.dim() == 4 and g.dtype == torch.float32) else 0
-            if ctot == 0:
-                g = ops._f32c(g)
-            ggamma, gbeta = torch.empty_like(gammas[j]), torch.empty_like(betas[j])
-            ws = torch.empty(L.eas_bn_workspace_doubles(Cc), dtype=torch.float64, device=y.device)
-            keep += [g, ws]
-            off = 4 * c0 * HW
-            q.grad_out, q.y, q.mean, q.invstd, q.gamma, q.beta = ptr(g), y.data_ptr() + off, ptr(ms[2 * j]), ptr(ms[2 * j + 1]), ptr(gammas[j]), ptr(betas[j])
-            q.grad_y, q.grad_gamma, q.grad_beta, q.workspace = gys[yi].data_ptr() + off, ptr(ggamma), ptr(gbeta), ptr(ws)
-            q.batch_stats, q.N, q.C, q.HW, q.grad_out_ctot, q.y_ctot = 1, N, Cc, HW, ctot, Ct
+                g = torch.zeros((y.shape[0], gammas[j].shape[0]) + tuple(y.shape[2:]), dtype=torch.float32, device=y.device)
+            p, ggamma, gbeta, kp = ops._silu_bwd_problem(L, g, y, y.shape[1], c0, ms[2 * j], ms[2 * j + 1], gammas[j], betas[j], 1, gys[yi])
+            arr[j] = _lib.EasBnSiluBwdProblem(*p)
+            keep.append(kp)
             res_g.append(ggamma)
             res_b.append(gbeta)
-            nbytes += 12 * N * Cc * HW
+            nbytes += 12 * p.N * p.C * p.HW
         ops._call('eas_bn_silu_bwd', nbytes, L.eas_bn_silu_bwd_group, arr, m, stream())
         del keep
         return (None,) + tuple(gys) + (None,) * ny + tuple(res_g) + tuple(res_b)
@@ -332,7 +310,7 @@ def bn_silu_group_ok(ys, bns):
 
 def bn_silu_group(ys, stats, layers):
     """[silu(bn_j(ys[yi_j][:, c0_j : c0_j + C_j]))] in one launch.  layers[j] = (yi, c0, bn); stats = ``conv_group``'s partial sums of ys."""
-    items = tuple((int(yi), int(c0), ops._bn_state(bn)) for yi, c0, bn in layers)
+    items = tuple((int(yi), int(c0), ops.bn_state(bn)) for yi, c0, bn in layers)
     cfg = dict(ny=len(ys), items=items)
     tensors = list(ys) + list(stats) + [bn.weight for _, _, bn in layers] + [bn.bias for _, _, bn in layers]
     return list(_BNSiLUGroupFn.apply(cfg, *tensors))
