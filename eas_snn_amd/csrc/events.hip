@@ -26,13 +26,17 @@ struct SampleWin {
     uint32_t win;  // 0 -> nothing is binned
 };
 
+// the one micro-slice window rule (gen1.py:313-328): t0 = first timestamp of the range, win = (last - first) / Tm, integer floor
+__device__ __forceinline__ SampleWin make_window(uint32_t t_first, uint32_t t_last, int Tm) {
+    SampleWin w;
+    w.t0 = t_first;
+    w.win = (t_last - t_first) / (uint32_t)Tm;
+    return w;
+}
+
 __device__ __forceinline__ SampleWin sample_window(const uint32_t* __restrict__ t, const int64_t* __restrict__ offsets,
                                                    int b, int Tm) {
-    const int64_t a = offsets[b], e = offsets[b + 1];
-    SampleWin w;
-    w.t0 = t[a];
-    w.win = (t[e - 1] - w.t0) / (uint32_t)Tm;
-    return w;
+    return make_window(t[offsets[b]], t[offsets[b + 1] - 1], Tm);
 }
 
 __device__ __forceinline__ void bin_one(uint32_t tt, uint32_t xx, uint32_t yy, uint32_t pp, const SampleWin& w, int b,
@@ -101,11 +105,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void event_hist_kernel(const uint32_t* _
 // p = bit 28; yolox/utils/psee_loader/io/dat_events_tools.py:24-54): decode + window + histogram in one pass, so the raw
 // file bytes are the only thing that crosses PCIe.  Two records per thread (one 16-byte load) when the buffer is aligned.
 __device__ __forceinline__ SampleWin sample_window_dat(const uint2* __restrict__ rec, const int64_t* __restrict__ offsets, int b, int Tm) {
-    const int64_t a = offsets[b], e = offsets[b + 1];
-    SampleWin w;
-    w.t0 = rec[a].x;
-    w.win = (rec[e - 1].x - w.t0) / (uint32_t)Tm;
-    return w;
+    return make_window(rec[offsets[b]].x, rec[offsets[b + 1] - 1].x, Tm);
 }
 
 __device__ __forceinline__ void bin_dat(uint32_t tt, uint32_t packed, const SampleWin& w, int b, int Tm, int H, int W,
@@ -210,9 +210,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void event_hist_dat_ranges_kernel(const 
     const int b = blockIdx.y;
     const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
     if (e <= a) return;
-    SampleWin w;
-    w.t0 = rec[a].x;
-    w.win = (rec[e - 1].x - w.t0) / (uint32_t)Tm;
+    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, Tm);
     for (int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
         const uint2 v = rec[i];
         bin_dat(v.x, v.y, w, b, Tm, H, W, out, oob);
@@ -229,15 +227,7 @@ constexpr int kBandThreads = 1024;
 constexpr int kBandLdsBytes = 150 * 1024;
 constexpr int kMaxBands = 8;
 
-__device__ __forceinline__ int64_t lower_bound_t(const uint32_t* __restrict__ t, int64_t lo, int64_t hi, uint32_t key) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (t[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// The same bound found by the 64 lanes of one wave: a round probes the last elements of 64 equal sub-ranges with ONE load per lane and
+// A lower bound found by the 64 lanes of one wave: a round probes the last elements of 64 equal sub-ranges with ONE load per lane and
 // keeps the sub-range that holds the answer -- 3 dependent rounds for a 200 k-event sample instead of the 18 dependent loads of the binary
 // search (each a full HBM round trip issued by a single thread: the two searches of a block were ~25 us of its ~45 us).  All lanes of
 // the wave call it with the same arguments and get the same result.
@@ -258,47 +248,136 @@ __device__ __forceinline__ int64_t lower_bound_wave(const uint32_t* __restrict__
     return lo + __popcll(__ballot(below));
 }
 
+// ---- the band form: two kernels over shared pieces (block mapping, range search, zero-fill, per-event count, write-out of a pass) -----
+__device__ __forceinline__ void band_zero(int* cnt, int words, bool vec4) {
+    if (vec4) {
+        for (int i = threadIdx.x; i < words / 4; i += kBandThreads) reinterpret_cast<int4*>(cnt)[i] = make_int4(0, 0, 0, 0);
+    } else {
+        for (int i = threadIdx.x; i < words; i += kBandThreads) cnt[i] = 0;
+    }
+}
+
+// counter idx of a pass: wide = one 32-bit word each, packed = two 16-bit counters per word;  packed4: four consecutive ones, one 8-byte read
+__device__ __forceinline__ int band_counter(const int* cnt, int idx, bool packed) {
+    return packed ? (int)(((unsigned)cnt[idx >> 1] >> (16 * (idx & 1))) & 0xffffu) : cnt[idx];
+}
+__device__ __forceinline__ int4 band_packed4(const int* cnt, int idx) {
+    const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(cnt) + idx);
+    return make_int4((int)(w.x & 0xffffu), (int)(w.x >> 16), (int)(w.y & 0xffffu), (int)(w.y >> 16));
+}
+
+// one event into the counters [2][plane] of rows [ya, yb); events outside the sensor are tallied in the first pass only
+__device__ __forceinline__ void band_count_one(unsigned xv, unsigned yv, unsigned pv, int H, int W, int ya, int yb, int plane, bool packed,
+                                               bool first, int* cnt, unsigned& bad) {
+    if (xv >= (unsigned)W || yv >= (unsigned)H) {
+        if (first) ++bad;
+        return;
+    }
+    if (yv < (unsigned)ya || yv >= (unsigned)yb) return;
+    const int idx = (pv != 0 ? plane : 0) + (int)(yv - ya) * W + (int)xv;
+    if (packed) atomicAdd(&cnt[idx >> 1], (idx & 1) ? 65536 : 1);
+    else atomicAdd(&cnt[idx], 1);
+}
+
+// The counters of a pass (rows [ya, yb) of polarity frames ``frame``, ``frame + 1``) to the int32 counts, or as fp32 into the zero-padded
+// model canvas [B][Tm][2][Hc][Wc] (gen1.py:447-455 + trainer.py:99 cast): the rows with their right padding down to row yend (Hc in the
+// last pass of the last band: the bottom padding).  16-byte stores where the layout allows (the wide counters: WIDE_VEC, counts only).
+template <bool WIDE_VEC>
+__device__ __forceinline__ void band_write_pass(const int* cnt, bool packed, int plane, int W, int ya, int yb, int yend, int64_t frame, int H,
+                                                int32_t* __restrict__ out, float* __restrict__ canvas, int Hc, int Wc) {
+    const int tid = threadIdx.x;
+    if (canvas) {
+        const bool quads = packed && (W & 3) == 0 && (Wc & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)canvas & 15) == 0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            float* dst = canvas + ((frame + c) * Hc + ya) * Wc;
+            if (quads) {                                      // four columns per thread
+                const int q4 = Wc / 4, total4 = (yend - ya) * q4;
+                for (int i = tid; i < total4; i += kBandThreads) {
+                    const int r = i / q4, col = (i - r * q4) * 4;
+                    int4 v = make_int4(0, 0, 0, 0);
+                    if (r < yb - ya && col < W) v = band_packed4(cnt, c * plane + r * W + col);
+                    *reinterpret_cast<float4*>(dst + (int64_t)r * Wc + col) = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+                }
+                continue;
+            }
+            const int total = (yend - ya) * Wc;
+            for (int i = tid; i < total; i += kBandThreads) {
+                const int r = i / Wc, col = i - r * Wc;
+                dst[i] = (r < yb - ya && col < W) ? (float)band_counter(cnt, c * plane + r * W + col, packed) : 0.0f;
+            }
+        }
+        return;
+    }
+    const int n = (yb - ya) * W;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        int32_t* dst = out + ((frame + c) * H + ya) * W;         // the band's rows are contiguous in the output as in LDS
+        if ((packed || WIDE_VEC) && (n & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
+            if (packed) for (int i = tid; i < n / 4; i += kBandThreads) reinterpret_cast<int4*>(dst)[i] = band_packed4(cnt, c * plane + 4 * i);
+            else for (int i = tid; i < n / 4; i += kBandThreads) reinterpret_cast<int4*>(dst)[i] = reinterpret_cast<const int4*>(cnt + c * plane)[i];
+        } else {
+            for (int i = tid; i < n; i += kBandThreads) dst[i] = band_counter(cnt, c * plane + i, packed);
+        }
+    }
+}
+
+// One block = one (sample, micro-slice, band of rows).  XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs, so the
+// bands of one (sample, slice) get ids 8 apart -- same XCD, one L2: the slice's events come from HBM once and from that L2 for the other
+// bands.  false: a block past the last slice
+struct BandBlock { int b, k, band, y0, y1; };
+
+__device__ __forceinline__ bool band_of_block(int nbands, int B, int Tm, int rows, int H, BandBlock& bb) {
+    const int L = blockIdx.x;
+    const int sl = (L & 7) + 8 * (L / (8 * nbands));
+    if (sl >= B * Tm) return false;
+    bb.band = (L >> 3) % nbands;
+    bb.b = sl / Tm;
+    bb.k = sl - bb.b * Tm;
+    bb.y0 = bb.band * rows;
+    bb.y1 = bb.y0 + rows < H ? bb.y0 + rows : H;
+    return true;
+}
+
+// the event range [range[0], range[1]) of micro-slice k of sample b into LDS: searched by the first wave (lower_bound_wave)
+__device__ __forceinline__ void band_slice_range(const uint32_t* __restrict__ t, const int64_t* __restrict__ offsets, int b, int k, int Tm,
+                                                 int64_t* range) {
+    if (threadIdx.x < EAS_WAVE) {
+        const int64_t a = offsets[b], e = offsets[b + 1];
+        int64_t lo = 0, hi = 0;
+        if (e > a) {
+            const SampleWin w = make_window(t[a], t[e - 1], Tm);
+            if (w.win != 0) {
+                lo = lower_bound_wave(t, a, e, w.t0 + (uint32_t)k * w.win);
+                hi = lower_bound_wave(t, lo, e, w.t0 + (uint32_t)(k + 1) * w.win);
+            }
+        }
+        if (threadIdx.x == 0) {
+            range[0] = lo;
+            range[1] = hi;
+        }
+    }
+}
+
+// 32-bit counters [2][rows][W]: one pass, one event per load with UN loads per array issued before the first LDS atomic, int4 zero-fill
+// (issued before the range search) and copy-out
 __global__ __launch_bounds__(kBandThreads) void event_hist_banded_kernel(const uint32_t* __restrict__ t, const uint16_t* __restrict__ x,
                                                                          const uint16_t* __restrict__ y, const uint8_t* __restrict__ p,
                                                                          const int64_t* __restrict__ offsets, int B, int Tm, int H, int W,
                                                                          int rows, int nbands, int32_t* __restrict__ out,
                                                                          uint32_t* __restrict__ oob, float* __restrict__ canvas, int Hc,
                                                                          int Wc) {
-    extern __shared__ int cnt[];            // [2][rows][W]
+    extern __shared__ int cnt[];
     __shared__ int64_t range[2];
-    // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs, so the bands of one (sample, slice) get ids
-    // 8 apart -- same XCD, one L2: the slice's events come from HBM once and from that L2 for the other bands
-    const int L = blockIdx.x, tid = threadIdx.x;
-    const int sl = (L & 7) + 8 * (L / (8 * nbands)), band = (L >> 3) % nbands;
-    if (sl >= B * Tm) return;
-    const int b = sl / Tm, k = sl - b * Tm;
-    const int y0 = band * rows, y1 = y0 + rows < H ? y0 + rows : H;
-    const int plane = rows * W;
-    if ((plane & 3) == 0) {
-        for (int i = tid; i < plane / 2; i += kBandThreads) reinterpret_cast<int4*>(cnt)[i] = make_int4(0, 0, 0, 0);
-    } else {
-        for (int i = tid; i < 2 * plane; i += kBandThreads) cnt[i] = 0;
-    }
-    if (tid < EAS_WAVE) {                   // the slice's event range [lo, hi): searched by the first wave (lower_bound_wave)
-        const int64_t a = offsets[b], e = offsets[b + 1];
-        int64_t lo = 0, hi = 0;
-        if (e > a) {
-            const uint32_t t0 = t[a];
-            const uint32_t win = (t[e - 1] - t0) / (uint32_t)Tm;
-            if (win != 0) {
-                lo = lower_bound_wave(t, a, e, t0 + (uint32_t)k * win);
-                hi = lower_bound_wave(t, lo, e, t0 + (uint32_t)(k + 1) * win);
-            }
-        }
-        if (tid == 0) {
-            range[0] = lo;
-            range[1] = hi;
-        }
-    }
+    BandBlock bb;
+    if (!band_of_block(nbands, B, Tm, rows, H, bb)) return;
+    const int tid = threadIdx.x, plane = rows * W;
+    band_zero(cnt, 2 * plane, (plane & 3) == 0);
+    band_slice_range(t, offsets, bb.b, bb.k, Tm, range);
     __syncthreads();
     const int64_t lo = range[0], hi = range[1];
     unsigned bad = 0;
-    constexpr int UN = 4;                   // events in flight per thread (all loads issued before the first LDS atomic)
+    constexpr int UN = 4;
     for (int64_t i0 = lo + tid; i0 < hi; i0 += (int64_t)UN * kBandThreads) {
         unsigned xs[UN], ys[UN], ps[UN];
 #pragma unroll
@@ -310,96 +389,49 @@ __global__ __launch_bounds__(kBandThreads) void event_hist_banded_kernel(const u
             ps[u] = in ? p[i] : 0u;
         }
 #pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            if (ys[u] == 0xffffffffu) continue;
-            if (xs[u] >= (unsigned)W || ys[u] >= (unsigned)H) {
-                ++bad;
-                continue;
-            }
-            if (ys[u] < (unsigned)y0 || ys[u] >= (unsigned)y1) continue;
-            atomicAdd(&cnt[(ps[u] != 0 ? plane : 0) + (int)(ys[u] - y0) * W + (int)xs[u]], 1);
-        }
+        for (int u = 0; u < UN; ++u)
+            if (ys[u] != 0xffffffffu) band_count_one(xs[u], ys[u], ps[u], H, W, bb.y0, bb.y1, plane, false, true, cnt, bad);
     }
-    if (band == 0 && oob && bad) atomicAdd(oob, bad);
     __syncthreads();
-    const int n = (y1 - y0) * W;
-    if (canvas) {
-        // fp32 frames straight into the zero-padded model canvas [B][Tm][2][Hc][Wc] (gen1.py:447-455 + trainer.py:99 cast):
-        // this band's rows with their right padding; the last band also writes the bottom padding rows
-        const int yend = band == nbands - 1 ? Hc : y1;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            float* dst = canvas + ((((int64_t)b * Tm + k) * 2 + c) * Hc + y0) * Wc;
-            const int total = (yend - y0) * Wc;
-            for (int i = tid; i < total; i += kBandThreads) {
-                const int r = i / Wc, col = i - r * Wc;
-                dst[i] = (r < y1 - y0 && col < W) ? (float)cnt[c * plane + r * W + col] : 0.0f;
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        int32_t* dst = out + ((((int64_t)b * Tm + k) * 2 + c) * H + y0) * W;
-        if ((n & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
-            for (int i = tid; i < n / 4; i += kBandThreads) reinterpret_cast<int4*>(dst)[i] = reinterpret_cast<const int4*>(cnt + c * plane)[i];
-        } else {
-            for (int i = tid; i < n; i += kBandThreads) dst[i] = cnt[c * plane + i];
-        }
-    }
+    band_write_pass<true>(cnt, false, plane, W, bb.y0, bb.y1, bb.band == nbands - 1 ? Hc : bb.y1, ((int64_t)bb.b * Tm + bb.k) * 2, H, out, canvas,
+                          Hc, Wc);
+    if (bb.band == 0 && oob && bad) atomicAdd(oob, bad);
 }
 
-// The same band form with 16-bit counters, two per LDS word: a band is twice as many rows (2 bands instead of 4 for the 240-row sensor:
-// every event is read by half as many blocks and the grid is two rounds of blocks instead of four), and the events come in aligned
-// groups of four (one 8-byte load each for x and y, one 4-byte load for p, instead of twelve 1- and 2-byte loads).  A counter cannot
-// overflow while the slice holds < 65536 events; a block whose slice holds more (known only on the device) counts its band in two halves
-// with 32-bit counters, one after the other -- the same LDS, the events read twice by that block only.  Bit-exact like the other forms.
+// 16-bit counters, two per LDS word: a band is twice as many rows (2 bands instead of 4 for the 240-row sensor: every event is read by half
+// as many blocks and the grid is two rounds of blocks instead of four), and the events come in aligned groups of four (one 8-byte load each
+// for x and y, one 4-byte load for p, instead of twelve 1- and 2-byte loads).  A counter cannot overflow while the slice holds < 65536
+// events; a block whose slice holds more (known only on the device) counts its band in two halves with 32-bit counters
+// [2][ceil(rows / 2)][W], one after the other -- the same LDS, the events read twice by that block only.  Bit-exact like the other forms.
+// The counting loop stands here and not in a callee shared with the 32-bit kernel: inside any inlined callee the compiler allocates it 93
+// registers instead of 85 and the kernel takes 2 % longer (profiles/events_one_body_ab.txt).
 __global__ __launch_bounds__(kBandThreads) void event_hist_banded16_kernel(const uint32_t* __restrict__ t, const uint16_t* __restrict__ x,
                                                                            const uint16_t* __restrict__ y, const uint8_t* __restrict__ p,
                                                                            const int64_t* __restrict__ offsets, int64_t nev, int B, int Tm, int H,
                                                                            int W, int rows, int nbands, int32_t* __restrict__ out,
                                                                            uint32_t* __restrict__ oob, float* __restrict__ canvas, int Hc, int Wc) {
-    extern __shared__ int cnt[];            // packed: [2][rows][W] 16-bit counters; wide (fallback): [2][rows / 2 (rounded up)][W] 32-bit
+    extern __shared__ int cnt[];
     __shared__ int64_t range[2];
-    const int L = blockIdx.x, tid = threadIdx.x;
-    const int sl = (L & 7) + 8 * (L / (8 * nbands)), band = (L >> 3) % nbands;      // XCD-aware order, see event_hist_banded_kernel
-    if (sl >= B * Tm) return;
-    const int b = sl / Tm, k = sl - b * Tm;
-    const int y0 = band * rows, y1 = y0 + rows < H ? y0 + rows : H;
-    if (tid < EAS_WAVE) {                   // the slice's event range [lo, hi): searched by the first wave (lower_bound_wave)
-        const int64_t a = offsets[b], e = offsets[b + 1];
-        int64_t lo = 0, hi = 0;
-        if (e > a) {
-            const uint32_t t0 = t[a];
-            const uint32_t win = (t[e - 1] - t0) / (uint32_t)Tm;
-            if (win != 0) {
-                lo = lower_bound_wave(t, a, e, t0 + (uint32_t)k * win);
-                hi = lower_bound_wave(t, lo, e, t0 + (uint32_t)(k + 1) * win);
-            }
-        }
-        if (tid == 0) {
-            range[0] = lo;
-            range[1] = hi;
-        }
-    }
+    BandBlock bb;
+    if (!band_of_block(nbands, B, Tm, rows, H, bb)) return;
+    const int tid = threadIdx.x;
+    band_slice_range(t, offsets, bb.b, bb.k, Tm, range);
     __syncthreads();
     const int64_t lo = range[0], hi = range[1];
     const bool packed = hi - lo < 65536;
-    const int hrows = (rows + 1) / 2;                         // rows per pass of the wide fallback
     const int npass = packed ? 1 : 2;
+    const int prow = packed ? rows : (rows + 1) / 2;          // rows per polarity plane in a pass
+    const int plane = prow * W;
     unsigned bad = 0;
     for (int pass = 0; pass < npass; ++pass) {
-        const int ya = packed ? y0 : y0 + pass * hrows;
-        const int yb = packed ? y1 : (ya + hrows < y1 ? ya + hrows : y1);
-        const int prow = packed ? rows : hrows;               // rows per polarity plane in this pass
-        const int plane = prow * W;
-        const int words = packed ? (2 * plane + 1) / 2 : 2 * plane;
+        // (a last band shorter than prow leaves the second pass no rows: it starts at y1, where the canvas's bottom padding begins)
+        const int ya = pass == 0 ? bb.y0 : (bb.y0 + prow < bb.y1 ? bb.y0 + prow : bb.y1);
+        const int yb = ya + prow < bb.y1 ? ya + prow : bb.y1;
         __syncthreads();                                      // pass 1: pass 0's counters have been written out
-        for (int i = tid; i < words; i += kBandThreads) cnt[i] = 0;
+        band_zero(cnt, packed ? (2 * plane + 1) / 2 : 2 * plane, false);
         __syncthreads();
         constexpr int UN = 4;                                 // aligned groups of four events in flight per thread
-        const int64_t g0 = lo & ~(int64_t)3;
-        for (int64_t i0 = g0 + 4 * (int64_t)tid; i0 < hi; i0 += (int64_t)UN * 4 * kBandThreads) {
+        for (int64_t i0 = (lo & ~(int64_t)3) + 4 * (int64_t)tid; i0 < hi; i0 += (int64_t)UN * 4 * kBandThreads) {
             uint2 xs[UN], ys[UN];
             unsigned ps[UN];
 #pragma unroll
@@ -420,81 +452,20 @@ __global__ __launch_bounds__(kBandThreads) void event_hist_banded16_kernel(const
             }
 #pragma unroll
             for (int u = 0; u < UN; ++u) {
-                const int64_t i = i0 + (int64_t)u * 4 * kBandThreads;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int64_t e = i + j;
-                    if (e < lo || e >= hi) continue;
-                    const unsigned xv = ((j < 2 ? xs[u].x : xs[u].y) >> (16 * (j & 1))) & 0xffffu;
-                    const unsigned yv = ((j < 2 ? ys[u].x : ys[u].y) >> (16 * (j & 1))) & 0xffffu;
-                    const unsigned pv = (ps[u] >> (8 * j)) & 0xffu;
-                    if (xv >= (unsigned)W || yv >= (unsigned)H) {
-                        if (pass == 0) ++bad;
-                        continue;
-                    }
-                    if (yv < (unsigned)ya || yv >= (unsigned)yb) continue;
-                    const int idx = (pv != 0 ? plane : 0) + (int)(yv - ya) * W + (int)xv;
-                    if (packed) atomicAdd(&cnt[idx >> 1], (idx & 1) ? 65536 : 1);
-                    else atomicAdd(&cnt[idx], 1);
+                    const int64_t e = i0 + (int64_t)u * 4 * kBandThreads + j;
+                    if (e < lo || e >= hi) continue;          // the group's events outside the slice
+                    band_count_one(((j < 2 ? xs[u].x : xs[u].y) >> (16 * (j & 1))) & 0xffffu, ((j < 2 ? ys[u].x : ys[u].y) >> (16 * (j & 1))) & 0xffffu,
+                                   (ps[u] >> (8 * j)) & 0xffu, H, W, ya, yb, plane, packed, pass == 0, cnt, bad);
                 }
             }
         }
         __syncthreads();
-        auto count_at = [&](int c, int r, int col) -> int {
-            const int idx = c * plane + r * W + col;
-            return packed ? (int)(((unsigned)cnt[idx >> 1] >> (16 * (idx & 1))) & 0xffffu) : cnt[idx];
-        };
-        if (canvas) {
-            // this pass's rows with their right padding; the last pass of the last band also writes the bottom padding rows
-            const bool last = band == nbands - 1 && pass == npass - 1;
-            const int yend = last ? Hc : yb;
-            const bool quads = packed && (W & 3) == 0 && (Wc & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)canvas & 15) == 0;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                float* dst = canvas + ((((int64_t)b * Tm + k) * 2 + c) * Hc + ya) * Wc;
-                if (quads) {
-                    // four columns per thread: one 8-byte LDS read of four packed counters, one 16-byte store
-                    const int q4 = Wc / 4, total4 = (yend - ya) * q4;
-                    const unsigned short* c16 = reinterpret_cast<const unsigned short*>(cnt) + c * plane;
-                    for (int i = tid; i < total4; i += kBandThreads) {
-                        const int r = i / q4, col = (i - r * q4) * 4;
-                        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (r < yb - ya && col < W) {
-                            const uint2 w = *reinterpret_cast<const uint2*>(c16 + r * W + col);
-                            v = make_float4((float)(w.x & 0xffffu), (float)(w.x >> 16), (float)(w.y & 0xffffu), (float)(w.y >> 16));
-                        }
-                        *reinterpret_cast<float4*>(dst + (int64_t)r * Wc + col) = v;
-                    }
-                    continue;
-                }
-                const int total = (yend - ya) * Wc;
-                for (int i = tid; i < total; i += kBandThreads) {
-                    const int r = i / Wc, col = i - r * Wc;
-                    dst[i] = (r < yb - ya && col < W) ? (float)count_at(c, r, col) : 0.0f;
-                }
-            }
-        } else {
-            const int n = (yb - ya) * W;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                int32_t* dst = out + ((((int64_t)b * Tm + k) * 2 + c) * H + ya) * W;
-                if (packed && (n & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
-                    // the band's rows are contiguous in the output as in LDS: four packed counters per 8-byte read, one 16-byte store
-                    const unsigned short* c16 = reinterpret_cast<const unsigned short*>(cnt) + c * plane;
-                    for (int i = tid; i < n / 4; i += kBandThreads) {
-                        const uint2 w = *reinterpret_cast<const uint2*>(c16 + 4 * i);
-                        reinterpret_cast<int4*>(dst)[i] = make_int4((int)(w.x & 0xffffu), (int)(w.x >> 16), (int)(w.y & 0xffffu), (int)(w.y >> 16));
-                    }
-                    continue;
-                }
-                for (int i = tid; i < n; i += kBandThreads) {
-                    const int r = i / W, col = i - r * W;
-                    dst[i] = count_at(c, r, col);
-                }
-            }
-        }
+        const int yend = bb.band == nbands - 1 && pass == npass - 1 ? Hc : yb;
+        band_write_pass<false>(cnt, packed, plane, W, ya, yb, yend, ((int64_t)bb.b * Tm + bb.k) * 2, H, out, canvas, Hc, Wc);
     }
-    if (band == 0 && oob && bad) atomicAdd(oob, bad);
+    if (bb.band == 0 && oob && bad) atomicAdd(oob, bad);
 }
 
 __global__ __launch_bounds__(EAS_BLOCK) void counts_to_canvas_kernel(const int32_t* __restrict__ counts, int64_t F, int H,
@@ -541,11 +512,10 @@ __global__ __launch_bounds__(EAS_BLOCK) void voxel_cube_kernel(const uint32_t* _
                                                                int tbins, int H, int W, int32_t* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nev; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = find_sample(offsets, B, i);
-        const int64_t a = offsets[b], e = offsets[b + 1];
-        const uint32_t t0 = t[a];
-        const uint32_t win = (t[e - 1] - t0) / (uint32_t)ns;
+        const SampleWin w = sample_window(t, offsets, b, ns);
+        const uint32_t win = w.win;
         if (win == 0) continue;
-        const uint32_t tr = t[i] - t0;
+        const uint32_t tr = t[i] - w.t0;
         if ((uint64_t)tr >= (uint64_t)win * (uint64_t)ns) continue;        // tail beyond ns whole windows is dropped
         const uint32_t xx = x[i], yy = y[i];
         if (xx >= (uint32_t)W || yy >= (uint32_t)H) continue;
@@ -654,69 +624,81 @@ __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32
     }
 }
 
-}  // namespace
+// ---- host side of the band form: one plan, one launch ------------------------------------------------------------------------------
+struct BandPlan {
+    int rows, nbands;       // even bands of ``rows`` rows; the last one may be shorter
+    size_t lds_bytes;
+};
 
-extern "C" {
+// The row bands of an H x W frame with counters of ``counter_bytes`` (4, or 2 = packed with the wide two-pass fallback); false when
+// the frame does not split into at most kMaxBands bands of kBandLdsBytes.  The 16-bit capacity is rounded down to an even row count:
+// the fallback counts ceil(rows / 2) rows per pass in 32-bit words, which is the packed need of rows + 1 rows when rows is odd.
+bool hist_band_plan(int H, int W, int counter_bytes, BandPlan* plan) {
+    int64_t cap = kBandLdsBytes / ((int64_t)2 * counter_bytes * W);
+    if (counter_bytes == 2) cap &= ~(int64_t)1;
+    if (cap > H) cap = H;
+    if (cap < 1 || (H + cap - 1) / cap > kMaxBands) return false;
+    const int nb = (int)((H + cap - 1) / cap), rows = (H + nb - 1) / nb;          // even bands
+    const size_t wide = (size_t)2 * (counter_bytes == 2 ? (rows + 1) / 2 : rows) * W, packed = ((size_t)2 * rows * W + 1) / 2;
+    plan->rows = rows;
+    plan->nbands = (H + rows - 1) / rows;
+    plan->lds_bytes = 4 * (counter_bytes == 2 && packed > wide ? packed : wide);
+    return true;
+}
 
-// counts into ``out``; or, when ``canvas`` is given and the banded form applies, fp32 frames straight into the canvas
+// The form a call takes: 0 scatter, 1 band / 32-bit counters, 2 band / 16-bit counters (+ its plan).  Dense streams (>= 2048 events per
+// frame on average) whose frame has a band plan take the LDS form; 16-bit counters need 8- / 4-byte loads of x, y / p (aligned16).
+// EAS_HIST_FORM (development switch) forces "scatter" / "banded" / "banded32" (the 32-bit band form).
+int hist_form(int64_t nev, int B, int Tm, int H, int W, bool aligned16, BandPlan* plan) {
+    const char* force = getenv("EAS_HIST_FORM");
+    const bool band = force ? force[0] == 'b' : nev >= (int64_t)B * Tm * 2048;
+    if (!band || (int64_t)B * Tm >= (1 << 24)) return 0;
+    // (a 16-bit band is at least as tall as a 32-bit one: where both apply the 16-bit form has no more bands)
+    if (aligned16 && !(force && strcmp(force, "banded32") == 0) && hist_band_plan(H, W, 2, plan)) return 2;
+    return hist_band_plan(H, W, 4, plan) ? 1 : 0;
+}
+
+template <auto Kernel, typename... Args>
+int launch_band(const BandPlan& plan, int nslices, hipStream_t st, Args... args) {
+    static bool attr_set = false;           // per kernel: one instantiation each
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBandLdsBytes) != hipSuccess) return EAS_ERR_LAUNCH;
+        attr_set = true;
+    }
+    const int64_t groups = ((int64_t)nslices + 7) / 8;
+    EAS_LAUNCH(Kernel, dim3((unsigned)(groups * 8 * plan.nbands)), dim3(kBandThreads), plan.lds_bytes, st, args...);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+// zero the counts (``out`` may be NULL: a form that writes every element itself) and the out-of-range word (may be NULL)
+bool zero_counts(int32_t* out, size_t count_bytes, uint32_t* oob_count, hipStream_t st) {
+    if (out && hipMemsetAsync(out, 0, count_bytes, st) != hipSuccess) return false;
+    return !oob_count || hipMemsetAsync(oob_count, 0, sizeof(uint32_t), st) == hipSuccess;
+}
+
+// counts into ``out``; or, when ``canvas`` is given and a band form applies, fp32 frames straight into the canvas
 // (*wrote_canvas = 1) without touching ``out``
-static int histogram_impl(const uint32_t* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t nev,
-                          const int64_t* sample_offsets, int B, int Tm, int H, int W, int32_t* out,
-                          uint32_t* oob_count, float* canvas, int Hc, int Wc, int* wrote_canvas, eas_stream_t stream) {
+int histogram_impl(const uint32_t* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t nev,
+                   const int64_t* sample_offsets, int B, int Tm, int H, int W, int32_t* out,
+                   uint32_t* oob_count, float* canvas, int Hc, int Wc, int* wrote_canvas, eas_stream_t stream) {
     if (wrote_canvas) *wrote_canvas = 0;
     if (!out || !sample_offsets || B < 1 || Tm < 1 || H < 1 || W < 1 || nev < 0) return EAS_ERR_INVALID_ARG;
     if (nev > 0 && (!t || !x || !y || !p)) return EAS_ERR_INVALID_ARG;
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-    const size_t bytes = (size_t)B * Tm * 2 * H * W * sizeof(int32_t);
-    if (oob_count && hipMemsetAsync(oob_count, 0, sizeof(uint32_t), st) != hipSuccess) return EAS_ERR_LAUNCH;
-    // dense streams (>= 2048 events per frame on average) whose frame splits into at most 8 LDS-sized row bands: LDS form
-    int rows = kBandLdsBytes / (8 * W);
-    if (rows > H) rows = H;
-    const int nbands = rows > 0 ? (H + rows - 1) / rows : kMaxBands + 1;
-    const char* force = getenv("EAS_HIST_FORM");      // development switch: "scatter" / "banded"
-    const bool dense = nev >= (int64_t)B * Tm * 2048;
-    // 16-bit counters + vector loads when the event arrays allow 8- / 4-byte loads (EAS_HIST_FORM=banded32: the 32-bit form)
-    const bool al16 = ((((uintptr_t)x | (uintptr_t)y) & 7) | ((uintptr_t)p & 3)) == 0 && !(force && strcmp(force, "banded32") == 0);
-    int rows16 = kBandLdsBytes / (4 * W);
-    if (rows16 > H) rows16 = H;
-    const int nbands16 = rows16 > 0 ? (H + rows16 - 1) / rows16 : kMaxBands + 1;
-    if (al16 && nbands16 <= kMaxBands && (int64_t)B * Tm < (1 << 24) && (force ? force[0] == 'b' : dense)) {
-        const int r16 = (H + nbands16 - 1) / nbands16;
-        static bool attr16 = false;
-        if (!attr16) {
-            if (hipFuncSetAttribute((const void*)event_hist_banded16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBandLdsBytes) != hipSuccess)
-                return EAS_ERR_LAUNCH;
-            attr16 = true;
-        }
-        const int nb = (H + r16 - 1) / r16;
-        const int64_t groups = ((int64_t)B * Tm + 7) / 8;
-        // LDS: packed [2][r16][W] halves, or the fallback's [2][ceil(r16 / 2)][W] words -- the larger of the two
-        const size_t lds16 = (size_t)4 * (((size_t)2 * r16 * W + 1) / 2 > (size_t)2 * ((r16 + 1) / 2) * W ? ((size_t)2 * r16 * W + 1) / 2
-                                                                                                        : (size_t)2 * ((r16 + 1) / 2) * W);
-        EAS_LAUNCH(event_hist_banded16_kernel, dim3((unsigned)(groups * 8 * nb)), dim3(kBandThreads), lds16, st, t, x, y, p,
-                           sample_offsets, nev, B, Tm, H, W, r16, nb, out, oob_count, canvas, Hc, Wc);
-        EAS_CHECK_LAUNCH();
-        if (canvas && wrote_canvas) *wrote_canvas = 1;
-        return EAS_OK;
+    BandPlan plan;
+    const bool aligned16 = ((((uintptr_t)x | (uintptr_t)y) & 7) | ((uintptr_t)p & 3)) == 0;
+    const int form = hist_form(nev, B, Tm, H, W, aligned16, &plan);
+    if (!zero_counts(form ? nullptr : out, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), oob_count, st)) return EAS_ERR_LAUNCH;
+    if (form) {
+        const int rc = form == 2 ? launch_band<event_hist_banded16_kernel>(plan, B * Tm, st, t, x, y, p, sample_offsets, nev, B, Tm, H, W, plan.rows,
+                                                                           plan.nbands, out, oob_count, canvas, Hc, Wc)
+                                 : launch_band<event_hist_banded_kernel>(plan, B * Tm, st, t, x, y, p, sample_offsets, B, Tm, H, W, plan.rows,
+                                                                         plan.nbands, out, oob_count, canvas, Hc, Wc);
+        if (rc == EAS_OK && canvas && wrote_canvas) *wrote_canvas = 1;
+        return rc;
     }
-    if (nbands <= kMaxBands && (int64_t)B * Tm < (1 << 24) && (force ? force[0] == 'b' : dense)) {
-        rows = (H + nbands - 1) / nbands;              // even bands
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)event_hist_banded_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBandLdsBytes) != hipSuccess)
-                return EAS_ERR_LAUNCH;
-            attr_set = true;
-        }
-        const int nb = (H + rows - 1) / rows;
-        const int64_t groups = ((int64_t)B * Tm + 7) / 8;
-        EAS_LAUNCH(event_hist_banded_kernel, dim3((unsigned)(groups * 8 * nb)), dim3(kBandThreads), (size_t)2 * rows * W * 4, st, t, x, y,
-                           p, sample_offsets, B, Tm, H, W, rows, nb, out, oob_count, canvas, Hc, Wc);
-        EAS_CHECK_LAUNCH();
-        if (canvas && wrote_canvas) *wrote_canvas = 1;
-        return EAS_OK;
-    }
-    if (hipMemsetAsync(out, 0, bytes, st) != hipSuccess) return EAS_ERR_LAUNCH;
     if (nev == 0) return EAS_OK;
     const bool vec = (((uintptr_t)t & 15) | ((uintptr_t)x & 7) | ((uintptr_t)y & 7) | ((uintptr_t)p & 3)) == 0;
     if (vec) {
@@ -730,10 +712,24 @@ static int histogram_impl(const uint32_t* t, const uint16_t* x, const uint16_t* 
     return EAS_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int eas_event_histogram(const uint32_t* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t nev,
                         const int64_t* sample_offsets, int B, int Tm, int H, int W, int32_t* out,
                         uint32_t* oob_count, eas_stream_t stream) {
     return histogram_impl(t, x, y, p, nev, sample_offsets, B, Tm, H, W, out, oob_count, nullptr, 0, 0, nullptr, stream);
+}
+
+int eas_event_histogram_plan(int64_t nev, int B, int Tm, int H, int W, int aligned16, int* rows, int* nbands, int64_t* lds_bytes) {
+    if (B < 1 || Tm < 1 || H < 1 || W < 1 || nev < 0) return EAS_ERR_INVALID_ARG;
+    BandPlan plan = {0, 0, 0};
+    const int form = hist_form(nev, B, Tm, H, W, aligned16 != 0, &plan);
+    if (rows) *rows = form ? plan.rows : 0;
+    if (nbands) *nbands = form ? plan.nbands : 0;
+    if (lds_bytes) *lds_bytes = form ? (int64_t)plan.lds_bytes : 0;
+    return form;
 }
 
 int eas_event_window_search(const void* records, const int64_t* file_offsets, int F, const int32_t* file_id, const int64_t* label_t, int B,
@@ -752,15 +748,23 @@ int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, i
     if (!records || !ranges || !out || B < 1 || Tm < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7)) return EAS_ERR_INVALID_ARG;
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-    if (hipMemsetAsync(out, 0, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), st) != hipSuccess) return EAS_ERR_LAUNCH;
-    if (oob_count && hipMemsetAsync(oob_count, 0, sizeof(uint32_t), st) != hipSuccess) return EAS_ERR_LAUNCH;
+    if (!zero_counts(out, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), oob_count, st)) return EAS_ERR_LAUNCH;
     // the ranges live on the device (no host read): a fixed number of blocks per sample strides over whatever it holds
     EAS_LAUNCH(event_hist_dat_ranges_kernel, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, Tm, H, W, out, oob_count);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }
 
-int eas_counts_to_canvas(const int32_t* counts, int64_t F, int H, int W, int Hc, int Wc, float* out, eas_stream_t stream);
+int eas_counts_to_canvas(const int32_t* counts, int64_t F, int H, int W, int Hc, int Wc, float* out,
+                         eas_stream_t stream) {
+    if (!counts || !out || F < 0 || H < 1 || W < 1 || Hc < H || Wc < W) return EAS_ERR_INVALID_ARG;
+    if (F == 0) return EAS_OK;
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH(counts_to_canvas_kernel, dim3(eas_grid_1d(F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
+                       F, H, W, Hc, Wc, out);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
 
 int eas_event_frames(const uint32_t* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t nev,
                      const int64_t* sample_offsets, int B, int Tm, int H, int W, int Hc, int Wc, float* frames,
@@ -778,9 +782,7 @@ int eas_event_histogram_dat(const void* records, int64_t nev, const int64_t* sam
     if (nev > 0 && (!records || ((uintptr_t)records & 7))) return EAS_ERR_INVALID_ARG;
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-    const size_t bytes = (size_t)B * Tm * 2 * H * W * sizeof(int32_t);
-    if (hipMemsetAsync(out, 0, bytes, st) != hipSuccess) return EAS_ERR_LAUNCH;
-    if (oob_count && hipMemsetAsync(oob_count, 0, sizeof(uint32_t), st) != hipSuccess) return EAS_ERR_LAUNCH;
+    if (!zero_counts(out, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), oob_count, st)) return EAS_ERR_LAUNCH;
     if (nev == 0) return EAS_OK;
     const uint2* rec = (const uint2*)records;
     if (((uintptr_t)records & 15) == 0)
@@ -789,17 +791,6 @@ int eas_event_histogram_dat(const void* records, int64_t nev, const int64_t* sam
     else
         EAS_LAUNCH(event_hist_dat_kernel<false>, dim3(eas_grid_1d(nev)), dim3(EAS_BLOCK), 0, st, rec, nev, sample_offsets, B, Tm, H,
                            W, out, oob_count);
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
-}
-
-int eas_counts_to_canvas(const int32_t* counts, int64_t F, int H, int W, int Hc, int Wc, float* out,
-                         eas_stream_t stream) {
-    if (!counts || !out || F < 0 || H < 1 || W < 1 || Hc < H || Wc < W) return EAS_ERR_INVALID_ARG;
-    if (F == 0) return EAS_OK;
-    EAS_CLEAR_ERR();
-    EAS_LAUNCH(counts_to_canvas_kernel, dim3(eas_grid_1d(F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
-                       F, H, W, Hc, Wc, out);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

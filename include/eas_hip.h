@@ -70,6 +70,13 @@ int eas_event_histogram(const uint32_t* t, const uint16_t* x, const uint16_t* y,
                         const int64_t* sample_offsets, int B, int Tm, int H, int W, int32_t* out,
                         uint32_t* oob_count, eas_stream_t stream);
 
+/* The form eas_event_histogram / eas_event_frames take for such a call, by the launch's own rule; needs no GPU.  Returns 0 = global-atomic
+ * scatter, 1 = LDS row bands with 32-bit counters, 2 = row bands with 16-bit counters (aligned16: x and y 8-byte, p 4-byte aligned); for
+ * 1 and 2 *rows, *nbands and *lds_bytes (each may be NULL) receive the band plan: nbands <= 8 bands of `rows` rows (the last may be
+ * shorter), lds_bytes <= 150 KB of dynamic LDS per block.  Dense streams (nev >= 2048 * B * Tm) whose frame has such a plan take a band
+ * form; the development switch EAS_HIST_FORM = scatter / banded / banded32 forces one, for the launch and for this query alike. */
+int eas_event_histogram_plan(int64_t nev, int B, int Tm, int H, int W, int aligned16, int* rows, int* nbands, int64_t* lds_bytes);
+
 /* The same count frames straight from Prophesee .dat event records (8 bytes each: u32 t, u32 packed with x = bits 0..13,
  * y = bits 14..27, p = bit 28; load_td_data, yolox/utils/psee_loader/io/dat_events_tools.py:29-54): decode, micro-slice
  * window and histogram in one pass over the raw file bytes after the header.  `records` is 8-byte aligned. */

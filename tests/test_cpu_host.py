@@ -83,6 +83,45 @@ def test_stride2_input_gradient_query_is_the_launch_rule_and_the_route_follows_i
         assert ops.conv_route((NI, Cin, H, W), Cout, 3, 2, 3).dgrad == want, (NI, Cin, Cout, H, W)
 
 
+def _hist_plan(lib, nev, B, Tm, H, W, aligned16, _out=(ctypes.c_int(), ctypes.c_int(), ctypes.c_int64())):
+    rows, nbands, lds = _out
+    form = lib.eas_event_histogram_plan(nev, B, Tm, H, W, aligned16, ctypes.byref(rows), ctypes.byref(nbands), ctypes.byref(lds))
+    return form, rows.value, nbands.value, lds.value
+
+
+def test_event_histogram_plan_query_is_the_launch_rule(monkeypatch):
+    """eas_event_histogram_plan answers by the code eas_event_histogram / eas_event_frames launch by (events.hip hist_form / hist_band_plan;
+    no GPU needed, arguments only).  Every band plan over H 1..1200 x W 1..2048, both counter widths, asks for at most 150 KB of dynamic LDS
+    (what the kernels declare), has at most 8 bands, and its bands cover the frame with none of them empty; the plans of the sensors the
+    project names; 74 x 1024, where an odd 16-bit row capacity (37) once gave 2 bands of 37 rows and 155 648 B; and the form choice."""
+    monkeypatch.delenv('EAS_HIST_FORM', raising=False)
+    lib = eas_snn_amd.hip_library()
+    dense = 1 << 40
+    rows, nbands, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    out = (ctypes.byref(rows), ctypes.byref(nbands), ctypes.byref(lds))
+    query, nplans = lib.eas_event_histogram_plan, [0, 0]
+    for aligned16 in (1, 0):
+        for H in range(1, 1201):
+            for W in range(1, 2049):
+                form = query(dense, 1, 1, H, W, aligned16, *out)
+                if form == 0:
+                    continue
+                r, n = rows.value, nbands.value
+                assert form == (2 if aligned16 else 1) and lds.value <= 150 * 1024 and 1 <= n <= 8 and r * n >= H > r * (n - 1), (H, W, aligned16)
+                nplans[aligned16] += 1
+    assert nplans[1] > nplans[0] > 100_000                   # a 16-bit band is at least as tall: no frame has a 32-bit plan only
+    assert _hist_plan(lib, dense, 1, 1, 240, 304, 1) == (2, 120, 2, 145920) and _hist_plan(lib, dense, 1, 1, 240, 304, 0)[:3] == (1, 60, 4)
+    assert _hist_plan(lib, dense, 1, 1, 480, 640, 1) == (2, 60, 8, 153600) and _hist_plan(lib, dense, 1, 1, 480, 640, 0) == (0, 0, 0, 0)
+    assert _hist_plan(lib, dense, 1, 1, 720, 1280, 1) == _hist_plan(lib, dense, 1, 1, 720, 1280, 0) == (0, 0, 0, 0)
+    assert _hist_plan(lib, dense, 1, 1, 74, 1024, 1)[:3] == (2, 25, 3)
+    # the choice: density nev >= 2048 * B * Tm, 16-bit counters only for aligned event arrays, B * Tm < 2^24
+    assert _hist_plan(lib, 64 * 4 * 2048 - 1, 64, 4, 240, 304, 1)[0] == 0 and _hist_plan(lib, 64 * 4 * 2048, 64, 4, 240, 304, 1)[0] == 2
+    assert _hist_plan(lib, 64 * 4 * 2048, 64, 4, 240, 304, 0)[0] == 1 and _hist_plan(lib, dense, 1 << 22, 4, 240, 304, 1)[0] == 0
+    assert lib.eas_event_histogram_plan(dense, 1, 1, 0, 304, 1, None, None, None) < 0          # invalid argument; NULL outputs are allowed
+    monkeypatch.setenv('EAS_HIST_FORM', 'banded32')           # the development switch holds for the query as for the launch
+    assert _hist_plan(lib, 0, 1, 1, 240, 304, 1)[:3] == (1, 60, 4)
+
+
 def test_gfx950_code_object_only():
     out = subprocess.run(['/opt/rocm/lib/llvm/bin/clang-offload-bundler', '--list', '--type=o',
                           f'--input={eas_snn_amd._lib.LIB_PATH}'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout

@@ -112,7 +112,7 @@ def test_event_histogram_both_forms_golden_and_ragged(dev, form, monkeypatch):
     big = ops.event_histogram(_t(tb.view(np.int32), dev).view(torch.uint32), _t(xb.view(np.int16), dev).view(torch.uint16),
                               _t(yb.view(np.int16), dev).view(torch.uint16), _t(pb, dev), torch.tensor([0, 30000], device=dev), 2, 720, 1280)
     assert np.array_equal(big[0].cpu().numpy(), events_ref.micro_sum(tb, xb, yb, pb, 2, 720, 1280).astype(np.int32))
-    # 480 x 640 (VGA) takes 4 bands of 120 rows
+    # 480 x 640 (VGA) takes 8 bands of 60 rows with 16-bit counters; with 32-bit counters it would need 16 bands: banded32 falls back to scatter
     tv, xv, yv, pv = events_ref.synth_events(40000, 480, 640, seed=78)
     vga = ops.event_histogram(_t(tv.view(np.int32), dev).view(torch.uint32), _t(xv.view(np.int16), dev).view(torch.uint16),
                               _t(yv.view(np.int16), dev).view(torch.uint16), _t(pv, dev), torch.tensor([0, 40000], device=dev), 3, 480, 640)
@@ -159,6 +159,47 @@ def test_event_histogram_odd_geometries(dev, form, H, W, Tm, B, monkeypatch):
     fr = ops.event_frames(*args, Hc, Wc).cpu().numpy()
     assert np.array_equal(fr[..., :H, :W], ref.astype(np.float32)) and fr[..., H:, :].sum() == 0 and fr[..., :, W:].sum() == 0
 
+
+BAND_PLAN_CASES = [(37, 1024, 1, 1, (70_000,)), (74, 1024, 2, 2, (5_000, 9_001)), (17, 7700, 1, 1, (70_000,))]
+
+
+@pytest.mark.parametrize('form', ['banded', 'banded32'])
+@pytest.mark.parametrize('H,W,Tm,B,sizes', BAND_PLAN_CASES)
+def test_event_histogram_band_plan_corners(dev, form, H, W, Tm, B, sizes, monkeypatch):
+    """The band plan's corners (tests/test_cpu_host.py checks the plans themselves), counts and frames on a canvas of (H + 3, W + 5),
+    bit-exact against the oracle.  37 x 1024: the row capacity of a 16-bit band is odd (37) and equals H -- one band of 37 rows would
+    need 38 rows' worth of 32-bit words in the two-pass path, the plan is 2 bands of 19 -- and the one slice holds >= 65536 events, so
+    its blocks do count in two passes.  74 x 1024, two samples, two slices: 3 bands of 25 rows, short streams (one packed pass), a last
+    band of 24 rows, B * Tm no multiple of 8.  17 x 7700: 5 bands of 4 rows, the last one a single row -- less than the two rows of a
+    pass, so the second pass of the last band has no rows and writes the bottom padding of the canvas only."""
+    from eas_snn_amd import ops
+    from oracle import events_ref
+    monkeypatch.setenv('EAS_HIST_FORM', form)
+    assert len(sizes) == B
+    parts = [events_ref.synth_events(n, H, W, seed=120 + i) for i, n in enumerate(sizes)]
+    t, x, y, p = (np.concatenate([q[j] for q in parts]) for j in range(4))
+    off = np.cumsum([0] + list(sizes)).astype(np.int64)
+    ref = events_ref.micro_sum_batch(t, x, y, p, off, Tm, H, W)
+    # the reference alone: every event of the micro-slices is on the sensor and counted (only the tail at and beyond t0 + Tm * window is
+    # dropped, slice_bounds), and the first case's one slice is too long for 16-bit counters
+    per_slice = ref.sum(axis=(2, 3, 4))
+    for i in range(B):
+        assert per_slice[i].tolist() == [hi - lo for lo, hi in events_ref.slice_bounds(t[off[i]:off[i + 1]], Tm)]
+    assert (per_slice.max() >= 65536) == (max(sizes) > 65536)
+    args = (_t(t.view(np.int32), dev).view(torch.uint32), _t(x.view(np.int16), dev).view(torch.uint16),
+            _t(y.view(np.int16), dev).view(torch.uint16), _t(p, dev), _t(off, dev), Tm, H, W)
+    out, oob = ops.event_histogram(*args, return_oob=True)
+    assert int(oob) == 0 and np.array_equal(out.cpu().numpy(), ref)
+    # the frames through the C entry into a canvas filled with NaN: an element the call leaves unwritten shows
+    from eas_snn_amd import _lib
+    frames = torch.full((B, Tm, 2, H + 3, W + 5), float('nan'), dtype=torch.float32, device=dev)
+    scratch = torch.empty((B, Tm, 2, H, W), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().eas_event_frames(*(_lib.ptr(a) for a in args[:4]), len(t), _lib.ptr(args[4]), B, Tm, H, W, H + 3, W + 5,
+                                           _lib.ptr(frames), _lib.ptr(scratch), None, _lib.stream()), 'eas_event_frames')
+    fr = frames.cpu().numpy()
+    assert not np.isnan(fr).any()
+    assert np.array_equal(fr[..., :H, :W], ref.astype(np.float32)) and fr[..., H:, :].sum() == 0 and fr[..., :, W:].sum() == 0
+    assert torch.equal(ops.event_frames(*args, H + 3, W + 5), frames)
 
 def test_postprocess_score_ties_keep_anchor_order(dev):
     """identical boxes and scores: the stable descending sort keeps the lowest anchor index (torchvision's nms sorts stably)"""
