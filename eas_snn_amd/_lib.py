@@ -127,6 +127,9 @@ PROTOTYPES = {
     'eas_spike_sop_workspace_doubles': (C.c_int64, []),
     'eas_spike_sop': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     'eas_counts_letterbox': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    'eas_counts_letterbox_ex': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
+    'eas_event_histogram_atis_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    'eas_event_histogram_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [_P] * 5),
     'eas_postprocess_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'eas_postprocess': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P]),
     'eas_event_frames': (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -624,6 +624,69 @@ __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32
     }
 }
 
+// The same letterbox with cv2.resize(INTER_CUBIC) semantics (NCaltech.batch_resize, ncaltech.py:98-105, 293-295, 313, 342).  OpenCV's
+// generic cubic resize for float64 images, restated from OpenCV's resize.cpp (not in the reference tree, opencv-python pinned by
+// pip-requirements.txt; no cv2 in this image: parity unpinned): per axis f = float((j + 0.5) * (n_src / n_dst) - 0.5), s = floor(f),
+// f -= s without a clamp; float32 weights with A = -0.75 (interpolateCubic); taps s-1 .. s+2, each index clamped to the image; float64
+// arithmetic, horizontal pass first, the four products added left to right, then the vertical pass over the four row results in the
+// same form, then the cast to fp32.  No FMA contraction (this library is built with -ffp-contract=off; the pragma says so for this
+// function whatever the flags), so the result equals a numpy restatement bit for bit.
+struct CubicTap { int s[4]; float c[4]; };
+
+__device__ __forceinline__ CubicTap cubic_tap(int j, int n_src, int n_dst) {
+#pragma clang fp contract(off)
+    const double scale = (double)n_src / (double)n_dst;
+    float f = (float)(((double)j + 0.5) * scale - 0.5);
+    const int s = (int)floorf(f);
+    f -= (float)s;
+    const float A = -0.75f;
+    CubicTap t;
+    t.c[0] = ((A * (f + 1.f) - 5.f * A) * (f + 1.f) + 8.f * A) * (f + 1.f) - 4.f * A;
+    t.c[1] = ((A + 2.f) * f - (A + 3.f)) * f * f + 1.f;
+    t.c[2] = ((A + 2.f) * (1.f - f) - (A + 3.f)) * (1.f - f) * (1.f - f) + 1.f;
+    t.c[3] = 1.f - t.c[0] - t.c[1] - t.c[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = s - 1 + k;
+        t.s[k] = i < 0 ? 0 : (i > n_src - 1 ? n_src - 1 : i);
+    }
+    return t;
+}
+
+__global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_cubic_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ params,
+                                                                           int B, int F, int H, int W, int Hc, int Wc, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t total = (int64_t)B * F * Hc * Wc;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % Wc);
+        const int64_t r = i / Wc;
+        const int yy = (int)(r % Hc);
+        const int64_t f = r / Hc;
+        const int b = (int)(f / F);
+        const int32_t* pr = params + 5 * b;
+        const int nw = pr[0], nh = pr[1], dx = pr[2], dy = pr[3], flip = pr[4];
+        const int xs = (flip ? Wc - 1 - xx : xx) - dx, ys = yy - dy;
+        float v = 0.f;
+        if (xs >= 0 && xs < nw && ys >= 0 && ys < nh) {
+            const int32_t* src = counts + f * H * W;
+            if (nw == W && nh == H) {
+                v = (float)src[ys * W + xs];                  // cv2.resize with dsize == size is a copy
+            } else {
+                const CubicTap tx = cubic_tap(xs, W, nw), ty = cubic_tap(ys, H, nh);
+                double rows[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int32_t* row = src + ty.s[k] * W;
+                    rows[k] = (double)row[tx.s[0]] * (double)tx.c[0] + (double)row[tx.s[1]] * (double)tx.c[1] +
+                              (double)row[tx.s[2]] * (double)tx.c[2] + (double)row[tx.s[3]] * (double)tx.c[3];
+                }
+                v = (float)(rows[0] * (double)ty.c[0] + rows[1] * (double)ty.c[1] + rows[2] * (double)ty.c[2] + rows[3] * (double)ty.c[3]);
+            }
+        }
+        out[i] = v;
+    }
+}
+
 // ---- host side of the band form: one plan, one launch ------------------------------------------------------------------------------
 struct BandPlan {
     int rows, nbands;       // even bands of ``rows`` rows; the last one may be shorter
@@ -850,6 +913,18 @@ int eas_counts_letterbox(const int32_t* counts, const int32_t* params, int B, in
     if (!counts || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
     EAS_CLEAR_ERR();
     EAS_LAUNCH(counts_letterbox_kernel, dim3(eas_grid_1d((int64_t)B * F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
+                       params, B, F, H, W, Hc, Wc, out);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                            eas_stream_t stream) {
+    if (interp == 0) return eas_counts_letterbox(counts, params, B, F, H, W, Hc, Wc, out, stream);
+    if (interp != 1) return EAS_ERR_INVALID_ARG;
+    if (!counts || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH(counts_letterbox_cubic_kernel, dim3(eas_grid_1d((int64_t)B * F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
                        params, B, F, H, W, Hc, Wc, out);
     EAS_CHECK_LAUNCH();
     return EAS_OK;

@@ -1,0 +1,323 @@
+// N-Caltech101 front end: raw ATIS recordings (5 bytes per record) -> per-polarity count frames int32 [B][Tl][Tm][2][H][W].
+// Reference: NCaltech.read_ATIS, generate_slices and agrregate('micro_sum') with measure='count', overlap=0
+// (yolox/data/datasets/ncaltech.py:63-96, 179-183, 227-237, 264-269, 368-379).
+//   record b0..b4: x = b0, y = b1, p = b2 >> 7, raw = (b2 & 127) << 16 | b3 << 8 | b4;  y == 240 is an overflow record: no event, it adds
+//   8192 to the time of every later record of its recording, so t = raw + 8192 * (overflow records at or before the record).
+// Five launches, no allocation, no host read (graph-capturable):
+//   0. atis_zero_kernel             the frames
+//   1. atis_overflow_count_kernel  overflow records per chunk of kChunk records of the whole buffer (reads the y byte of every record)
+//   2. atis_overflow_scan_kernel    exclusive scan of the chunk counts, in place (one block)
+//   3. atis_plan_kernel             one wave per recording: last event, window, t0 / tL, and per macro slice the first / last member
+//                                   event (binary searches over decoded records; a probe's time = raw + 8192 * (chunk base + in-chunk
+//                                   count - the recording's own base)) -> one AtisHead per recording, one AtisSlice per macro slice
+//   4. atis_hist_kernel             blocks stride over the chunks of a recording: decode in registers, block scan of the overflow
+//                                   records of the chunk, window / macro slice / micro slice (the SampleWin rule of events.hip bin_one),
+//                                   int32 atomics -- bit-exact in any order
+// Algorithmic bytes per recording: 5 * nrec + 4 * Tl * Tm * 2 * H * W; the records are read twice (launches 1 and 4), the plan's probes
+// re-read O(Tl * log nrec) chunks.
+// The chunks are chunks of the BUFFER (record index / kChunk), not of a recording: the overflow count of a record inside recording
+// [a, e) is prefix(i) - prefix(a - 1), so recordings need no chunk tables of their own.
+#include <limits.h>
+
+#include "eas_common.h"
+
+namespace {
+
+constexpr int kChunk = 256;             // records per chunk = threads of a histogram block (a power of two <= 4096)
+constexpr int kChunkShift = 8;
+constexpr uint32_t kOverflowY = 240;
+constexpr uint32_t kTimeIncrement = 8192;   // the reference's 2 ** 13, kept as it is
+constexpr int kScanThreads = 1024;
+
+struct AtisHead {                       // per recording
+    int64_t wl, wh;                     // events with wl < t <= wh remain (no window: INT64_MIN, INT64_MAX)
+    int64_t t0, mw;                     // first remaining time, macro slice length (0: nothing is binned)
+    uint32_t ovf_base, pad;             // overflow records of the buffer in front of the recording
+};
+struct AtisSlice { uint32_t f, w; };    // per (recording, macro slice): time of its first member event, micro window (0: nothing is binned)
+
+__device__ __forceinline__ void clamp_range(const int64_t* __restrict__ offsets, int b, int64_t nrec, int64_t& a, int64_t& e) {
+    a = offsets[b];
+    e = offsets[b + 1];
+    if (a < 0) a = 0;
+    if (e > nrec) e = nrec;
+    if (e < a) e = a;                   // offsets that do not describe a range: an empty recording (flag bit 1), nothing past nrec is read
+}
+
+__device__ __forceinline__ uint32_t rec_y(const uint8_t* __restrict__ rec, int64_t i) { return rec[5 * i + 1]; }
+__device__ __forceinline__ uint32_t rec_raw(const uint8_t* __restrict__ rec, int64_t i) {
+    const uint8_t* p = rec + 5 * i;
+    return ((uint32_t)(p[2] & 127u) << 16) | ((uint32_t)p[3] << 8) | (uint32_t)p[4];
+}
+
+__global__ __launch_bounds__(kChunk) void atis_overflow_count_kernel(const uint8_t* __restrict__ rec, int64_t nrec, int64_t nchunks,
+                                                                      uint32_t* __restrict__ chunk_base) {
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int64_t i = c * kChunk + threadIdx.x;
+        const int n = __syncthreads_count(i < nrec && rec_y(rec, i) == kOverflowY);
+        if (threadIdx.x == 0) chunk_base[c] = (uint32_t)n;
+    }
+}
+
+// exclusive scan in place: thread t owns a contiguous segment, the segment totals are scanned through LDS
+__global__ __launch_bounds__(kScanThreads) void atis_overflow_scan_kernel(uint32_t* __restrict__ chunk_base, int64_t nchunks) {
+    __shared__ uint32_t tot[kScanThreads];
+    const int tid = threadIdx.x;
+    const int64_t seg = (nchunks + kScanThreads - 1) / kScanThreads;
+    const int64_t lo = tid * seg, hi = lo + seg < nchunks ? lo + seg : nchunks;
+    uint32_t s = 0;
+    for (int64_t i = lo; i < hi; ++i) s += chunk_base[i];
+    tot[tid] = s;
+    __syncthreads();
+    for (int off = 1; off < kScanThreads; off <<= 1) {         // inclusive Hillis-Steele
+        const uint32_t v = tid >= off ? tot[tid - off] : 0u;
+        __syncthreads();
+        tot[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = tot[tid] - s;
+    for (int64_t i = lo; i < hi; ++i) {
+        const uint32_t v = chunk_base[i];
+        chunk_base[i] = run;
+        run += v;
+    }
+}
+
+// ---- the plan: everything below is called by all 64 lanes of one wave with the same arguments and returns the same value in every lane
+// overflow records of the buffer at or before record i
+__device__ __forceinline__ uint32_t overflow_prefix(const uint8_t* __restrict__ rec, const uint32_t* __restrict__ chunk_base, int64_t i) {
+    const int lane = threadIdx.x & (EAS_WAVE - 1);
+    const int64_t c0 = i & ~(int64_t)(kChunk - 1);
+    uint32_t n = chunk_base[i >> kChunkShift];
+#pragma unroll
+    for (int j = 0; j < kChunk / EAS_WAVE; ++j) {
+        const int64_t k = c0 + j * EAS_WAVE + lane;
+        n += (uint32_t)__popcll(__ballot(k <= i && rec_y(rec, k) == kOverflowY));
+    }
+    return n;
+}
+
+// first event record in [i, hi), hi when there is none
+__device__ __forceinline__ int64_t next_event(const uint8_t* __restrict__ rec, int64_t i, int64_t hi) {
+    const int lane = threadIdx.x & (EAS_WAVE - 1);
+    for (; i < hi; i += EAS_WAVE) {
+        const unsigned long long m = __ballot(i + lane < hi && rec_y(rec, i + lane) != kOverflowY);
+        if (m) return i + __builtin_ctzll(m);
+    }
+    return hi;
+}
+
+// last event record in [lo, i], lo - 1 when there is none
+__device__ __forceinline__ int64_t prev_event(const uint8_t* __restrict__ rec, int64_t i, int64_t lo) {
+    const int lane = threadIdx.x & (EAS_WAVE - 1);
+    for (; i >= lo; i -= EAS_WAVE) {
+        const unsigned long long m = __ballot(i - lane >= lo && rec_y(rec, i - lane) != kOverflowY);
+        if (m) return i - __builtin_ctzll(m);
+    }
+    return lo - 1;
+}
+
+struct AtisRec {
+    const uint8_t* rec;
+    const uint32_t* chunk_base;
+    uint32_t ovf_base;
+    __device__ __forceinline__ int64_t time(int64_t i) const {
+        return (int64_t)(rec_raw(rec, i) + kTimeIncrement * (overflow_prefix(rec, chunk_base, i) - ovf_base));
+    }
+};
+
+// a record index r in [lo, hi]: every event in [lo, r) has t < key, every event in [r, hi) has t >= key (event times ascending)
+__device__ __forceinline__ int64_t lower_bound_events(const AtisRec& R, int64_t lo, int64_t hi, int64_t key) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int64_t m = next_event(R.rec, mid, hi);       // the probe steps over overflow records
+        if (m < hi && R.time(m) < key) lo = m + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
+                                                             const uint32_t* __restrict__ chunk_base, int64_t window_lo, int64_t window_hi,
+                                                             int Tl, int Tm, AtisHead* __restrict__ heads, AtisSlice* __restrict__ slices,
+                                                             uint32_t* __restrict__ oob, uint32_t* __restrict__ flags) {
+    const int b = blockIdx.x;
+    const bool writer = threadIdx.x == 0;
+    int64_t a, e;
+    clamp_range(offsets, b, nrec, a, e);
+    AtisRec R = {rec, chunk_base, 0u};
+    if (a > 0 && a < e) R.ovf_base = overflow_prefix(rec, chunk_base, a - 1);
+    AtisHead h = {LLONG_MIN, LLONG_MAX, 0, 0, R.ovf_base, 0u};
+    AtisSlice* rows = slices + (int64_t)b * Tl;
+    uint32_t flag = 0;
+    int64_t ia = a, ib = e;
+    const int64_t last = prev_event(rec, e - 1, a);
+    bool any = last >= a;
+    if (any && window_lo < 0) {
+        const int64_t t_end = R.time(last);
+        h.wl = t_end + window_lo;
+        h.wh = t_end + window_hi;
+        ia = lower_bound_events(R, a, e, h.wl + 1);
+        ib = lower_bound_events(R, ia, e, h.wh + 1);
+    }
+    int64_t first = ib, lastr = ia - 1;
+    if (any) {
+        first = next_event(rec, ia, ib);
+        lastr = prev_event(rec, ib - 1, ia);
+        any = first < ib;
+    }
+    if (any) {
+        h.t0 = R.time(first);
+        const int64_t tl = R.time(lastr);
+        h.mw = tl > h.t0 ? (tl - h.t0) / Tl : 0;
+    }
+    int64_t start = ia;
+    for (int k = 0; k < Tl; ++k) {
+        AtisSlice s = {0u, 0u};
+        bool members = false;
+        if (h.mw > 0) {
+            const int64_t end = lower_bound_events(R, start, ib, h.t0 + (int64_t)(k + 1) * h.mw);
+            const int64_t fe = next_event(rec, start, end);
+            if (fe < end) {
+                members = true;
+                const int64_t f = R.time(fe), l = R.time(prev_event(rec, end - 1, start));
+                s.f = (uint32_t)f;
+                s.w = l > f ? (uint32_t)((l - f) / Tm) : 0u;
+            }
+            start = end;
+        }
+        if (!members) flag |= 2u;
+        if (writer) rows[k] = s;
+    }
+    if (writer) {
+        heads[b] = h;
+        if (oob) oob[b] = 0u;
+        if (flags) flags[b] = flag;
+    }
+}
+
+// The 5 bytes of record i in the low 40 bits.  Two aligned 32-bit loads wherever both words lie inside the buffer -- a record spans
+// exactly two aligned words at every alignment of the base address --, byte loads for the few records at the ends whose words do not.
+__device__ __forceinline__ uint64_t load_record(const uint8_t* __restrict__ rec, int64_t nrec, int64_t i) {
+    const uint8_t* p = rec + 5 * i;
+    const uintptr_t o = (uintptr_t)p & 3;
+    const uint8_t* w = p - o;
+    if (w >= rec && w + 8 <= rec + 5 * nrec) {
+        const uint32_t w0 = reinterpret_cast<const uint32_t*>(w)[0], w1 = reinterpret_cast<const uint32_t*>(w)[1];
+        return (((uint64_t)w1 << 32) | w0) >> (8 * o);
+    }
+    return (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24) | ((uint64_t)p[4] << 32);
+}
+
+__global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
+                                                           const uint32_t* __restrict__ chunk_base, const AtisHead* __restrict__ heads,
+                                                           const AtisSlice* __restrict__ slices, int Tl, int Tm, int H, int W,
+                                                           int32_t* __restrict__ out, uint32_t* __restrict__ oob, uint32_t* __restrict__ flags) {
+    __shared__ uint32_t wave_total[kChunk / EAS_WAVE];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & (EAS_WAVE - 1), wid = tid / EAS_WAVE;
+    int64_t a, e;
+    clamp_range(offsets, b, nrec, a, e);
+    if (e <= a) return;
+    const AtisHead h = heads[b];
+    const AtisSlice* rows = slices + (int64_t)b * Tl;
+    const int64_t c_last = (e - 1) >> kChunkShift;
+    for (int64_t c = (a >> kChunkShift) + blockIdx.x; c <= c_last; c += gridDim.x) {
+        const int64_t i = c * kChunk + tid;
+        const uint64_t v = i < nrec ? load_record(rec, nrec, i) : 0ull;
+        const uint32_t xx = (uint32_t)(v & 255u), yy = (uint32_t)((v >> 8) & 255u), b2 = (uint32_t)((v >> 16) & 255u);
+        const uint32_t raw = ((b2 & 127u) << 16) | ((uint32_t)((v >> 24) & 255u) << 8) | (uint32_t)((v >> 32) & 255u);
+        // overflow records of the chunk at or before this record (the chunk's records of a neighbouring recording count too: they are
+        // part of the buffer-wide prefix that ovf_base is taken from)
+        const unsigned long long m = __ballot(i < nrec && yy == kOverflowY);
+        uint32_t before = (uint32_t)__popcll(m & (~0ull >> (EAS_WAVE - 1 - lane)));
+        if (lane == 0) wave_total[wid] = (uint32_t)__popcll(m);
+        __syncthreads();
+        for (int w = 0; w < wid; ++w) before += wave_total[w];
+        __syncthreads();
+        if (i < a || i >= e || yy == kOverflowY) continue;
+        const uint32_t nov = chunk_base[c] + before - h.ovf_base;
+        const uint32_t t = raw + kTimeIncrement * nov;
+        if (flags) {                                               // bit 0: the event in front of this one has a later time
+            int64_t j = i - 1;
+            while (j >= a && rec_y(rec, j) == kOverflowY) --j;   // (the records between the two events are overflow records)
+            if (j >= a && rec_raw(rec, j) + kTimeIncrement * (nov - (uint32_t)(i - j - 1)) > t) atomicOr(flags + b, 1u);
+        }
+        if ((int64_t)t <= h.wl || (int64_t)t > h.wh || h.mw == 0 || (int64_t)t < h.t0) continue;
+        const uint32_t k = (t - (uint32_t)h.t0) / (uint32_t)h.mw;
+        if (k >= (uint32_t)Tl) continue;                           // the events on the last timestamp (Tl == 1) and the tail beyond Tl * mw
+        const AtisSlice s = rows[k];
+        if (s.w == 0 || t < s.f) continue;
+        const uint32_t q = (t - s.f) / s.w;
+        if (q >= (uint32_t)Tm) continue;
+        if (xx >= (uint32_t)W || yy >= (uint32_t)H) {
+            if (oob) atomicAdd(oob + b, 1u);
+            continue;
+        }
+        const int ch = (b2 >> 7) != 0 ? 1 : 0;
+        atomicAdd(out + (((((int64_t)b * Tl + k) * Tm + q) * 2 + ch) * H + yy) * W + xx, 1);
+    }
+}
+
+// the frames are zeroed by a kernel of the call's own (16-byte stores; torch hands out 16-byte aligned frames, a scalar loop otherwise)
+__global__ __launch_bounds__(EAS_BLOCK) void atis_zero_kernel(int32_t* __restrict__ out, int64_t n) {
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if (((uintptr_t)out & 15) == 0) {
+        for (int64_t i = i0; i < n / 4; i += stride) reinterpret_cast<int4*>(out)[i] = make_int4(0, 0, 0, 0);
+        for (int64_t i = (n & ~(int64_t)3) + i0; i < n; i += stride) out[i] = 0;
+    } else {
+        for (int64_t i = i0; i < n; i += stride) out[i] = 0;
+    }
+}
+
+inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+inline int64_t chunks_of(int64_t nrec) { return (nrec + kChunk - 1) / kChunk; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
+    if (nrec < 0 || B < 1 || Tl < 1) return 0;
+    return align16((chunks_of(nrec) + 1) * (int64_t)sizeof(uint32_t)) + align16((int64_t)B * sizeof(AtisHead)) +
+           align16((int64_t)B * Tl * sizeof(AtisSlice));
+}
+
+int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                             int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                             eas_stream_t stream) {
+    if (!out || !sample_offsets || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
+    if ((nrec > 0 && !records) || ((uintptr_t)workspace & 15) || nrec > (INT64_MAX >> 3)) return EAS_ERR_INVALID_ARG;
+    if ((int64_t)B * Tl >= (1 << 24) || B > 65535) return EAS_ERR_UNSUPPORTED;
+    const int64_t far = (int64_t)1 << 40;                  // decoded times fit 32 bits: a bound beyond +-2^40 selects what 2^40 selects
+    window_lo = window_lo < -far ? -far : window_lo;
+    window_hi = window_hi > far ? far : (window_hi < -far ? -far : window_hi);
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    const uint8_t* rec = (const uint8_t*)records;
+    const int64_t nchunks = chunks_of(nrec);
+    uint32_t* chunk_base = (uint32_t*)workspace;
+    AtisHead* heads = (AtisHead*)((char*)workspace + align16((nchunks + 1) * (int64_t)sizeof(uint32_t)));
+    AtisSlice* slices = (AtisSlice*)((char*)heads + align16((int64_t)B * sizeof(AtisHead)));
+    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W;
+    EAS_LAUNCH(atis_zero_kernel, dim3(eas_grid_1d((nout + 3) / 4)), dim3(EAS_BLOCK), 0, st, out, nout);
+    EAS_CHECK_LAUNCH();
+    if (nchunks > 0) {
+        EAS_LAUNCH(atis_overflow_count_kernel, dim3(eas_grid_1d(nchunks, 1)), dim3(kChunk), 0, st, rec, nrec, nchunks, chunk_base);
+        EAS_CHECK_LAUNCH();
+        EAS_LAUNCH(atis_overflow_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, chunk_base, nchunks);
+        EAS_CHECK_LAUNCH();
+    }
+    EAS_LAUNCH(atis_plan_kernel, dim3(B), dim3(EAS_WAVE), 0, st, rec, nrec, sample_offsets, chunk_base, window_lo, window_hi, Tl, Tm, heads, slices,
+               oob_count, flags);
+    EAS_CHECK_LAUNCH();
+    if (nchunks > 0) {
+        // the recordings' lengths live on the device: a fixed number of blocks per recording strides over whatever it holds
+        int64_t per = nchunks / B + 1;
+        if (per > 64) per = 64;
+        EAS_LAUNCH(atis_hist_kernel, dim3((unsigned)per, B), dim3(kChunk), 0, st, rec, nrec, sample_offsets, chunk_base, heads, slices, Tl, Tm, H, W,
+                   out, oob_count, flags);
+        EAS_CHECK_LAUNCH();
+    }
+    return EAS_OK;
+}
+
+}  // extern "C"

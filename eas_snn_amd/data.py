@@ -158,6 +158,73 @@ def transform_boxes(bboxes, params, ih, iw, h, w, rng=None):
     return box[keep].astype(np.float32)
 
 
+# ------------------------------------------------------------------------------------------------ N-Caltech101 (ATIS recordings)
+ATIS_OVERFLOW_Y = 240            # a record with this y is no event: it adds ATIS_TIME_INCREMENT to every later time of its recording
+ATIS_TIME_INCREMENT = 1 << 13
+
+
+def encode_atis(t, x, y, p, overflow_before=()):
+    """Events -> the byte image of an ATIS recording (N-Caltech101 ``.bin``), numpy uint8 [5 * records].  Record b0..b4: x = b0, y = b1,
+    p = b2 >> 7, raw time = (b2 & 127) << 16 | b3 << 8 | b4.  ``overflow_before``: event indices in front of which an overflow record is
+    put (``len(t)`` = behind the last event; an index may repeat); the raw times of the events behind it are lowered by 8192 each, so the
+    decoded times are ``t`` again.  Every raw time must stay inside 23 bits."""
+    t, x, y, p = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (t, x, y, p))
+    n = len(t)
+    assert len(x) == len(y) == len(p) == n and (y != ATIS_OVERFLOW_Y).all() and ((x >= 0) & (x < 256) & (y >= 0) & (y < 256)).all()
+    ov = np.sort(np.asarray(list(overflow_before), dtype=np.int64))
+    assert len(ov) == 0 or (ov[0] >= 0 and ov[-1] <= n)
+    raw = t - ATIS_TIME_INCREMENT * np.searchsorted(ov, np.arange(n), side='right')
+    assert ((raw >= 0) & (raw < (1 << 23))).all(), 'raw ATIS times are 23 bits'
+    rec = np.zeros((n + len(ov), 5), dtype=np.uint8)
+    pos = np.arange(n) + np.searchsorted(ov, np.arange(n), side='right')          # record index of every event
+    rec[pos, 0], rec[pos, 1] = x, y
+    rec[pos, 2] = ((p != 0).astype(np.int64) << 7) | (raw >> 16)
+    rec[pos, 3], rec[pos, 4] = (raw >> 8) & 255, raw & 255
+    is_ov = np.ones(n + len(ov), dtype=bool)
+    is_ov[pos] = False
+    rec[is_ov, 1] = ATIS_OVERFLOW_Y
+    return rec.reshape(-1)
+
+
+def synth_atis_batch(batch, n_events, height=180, width=240, span_us=300_000, seed=0):
+    """-> (bytes uint8 [5 * records], offsets int64 [batch + 1] in records): ``batch`` synthetic ATIS recordings of ``n_events`` events
+    each -- ``t`` sorted uniform over ``span_us`` from 0, ``x``, ``y`` uniform on the sensor, ``p`` Bernoulli(0.5) -- with an overflow
+    record in front of the first event of every further 65536 us (the 23-bit raw field would not need them at these spans: they are
+    there so that the decode is exercised)."""
+    rng = np.random.default_rng(seed)
+    parts, off = [], [0]
+    for _ in range(batch):
+        t = np.sort(rng.integers(0, span_us, size=n_events, dtype=np.int64))
+        x = rng.integers(0, width, size=n_events, dtype=np.int64)
+        y = rng.integers(0, height, size=n_events, dtype=np.int64)
+        p = (rng.random(n_events) < 0.5).astype(np.int64)
+        marks = np.arange(1, span_us // 65536 + 1) * 65536
+        parts.append(encode_atis(t, x, y, p, overflow_before=np.searchsorted(t, marks)))
+        off.append(off[-1] + len(parts[-1]) // 5)
+    return np.concatenate(parts), np.asarray(off, dtype=np.int64)
+
+
+def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'):
+    """Raw ATIS recordings in HBM -> model input [B, Tl, Tm, 2, Hc, Wc] fp32: ``ops.event_histogram_atis`` then ``ops.counts_letterbox``,
+    nothing read back in between (graph-capturable).  ``exp_or_dims``: an experiment (fields ``Tl``, ``Tm``, ``input_size``, optionally
+    ``img_size`` -- the sensor, default (180, 240) -- and ``window`` in ms, as yolox/exp/event_yolox_base.py passes it: ``(window * 1000, 0)``) or a tuple
+    ``(Tl, Tm, (H, W), (Hc, Wc))`` with an optional fifth element ``window`` = (lo, hi) in us.  ``params``: per-sample
+    (nw, nh, dx, dy, flip) rows, a device int32 tensor or anything numpy reads.  N-Caltech101 resizes every sample, in evaluation too:
+    ``letterbox_params(180, 240, 192, 256)`` = (256, 192, 0, 0, 0).  Its random branch (NCaltech.get_random_data, ncaltech.py:330-350)
+    is ``jitter_params(..., jitter=.1)``, and the boxes go through ``transform_boxes`` as they are."""
+    if isinstance(exp_or_dims, (tuple, list)):
+        Tl, Tm, (H, W), (Hc, Wc) = exp_or_dims[:4]
+        window = exp_or_dims[4] if len(exp_or_dims) > 4 else None
+    else:
+        e = exp_or_dims
+        Tl, Tm, (H, W), (Hc, Wc) = e.Tl, e.Tm, getattr(e, 'img_size', (180, 240)), e.input_size
+        window = (e.window * 1000, 0) if getattr(e, 'window', None) is not None else None
+    counts = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
+    if not torch.is_tensor(params):
+        params = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5)).to(counts.device)
+    return ops.counts_letterbox(counts, params, Hc, Wc, interp=interp)
+
+
 def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params):
     """events -> histogram (K1) -> resize / paste / flip on the device -> [B, 1, Tm, 2, Hc, Wc] fp32; ``params``: per-sample
     (nw, nh, dx, dy, flip) rows."""

@@ -76,6 +76,29 @@ def event_histogram_dat_ranges(records, ranges, Tm, H, W, return_oob=False):
     return (out, oob) if return_oob else out
 
 
+def event_histogram_atis(records, sample_offsets, Tl, Tm, H, W, window=None, return_oob=False, return_flags=False):
+    """Count frames int32 [B, Tl, Tm, 2, H, W] straight from raw ATIS recordings (N-Caltech101 ``.bin``, 5 bytes per record) in HBM:
+    decode with overflow records, ``window`` (lo, hi) us relative to the last event (None or lo >= 0: no window), the reference's macro /
+    micro slicing and the count histogram on the device (NCaltech.read_ATIS / generate_slices / agrregate 'micro_sum').  ``records``: any
+    uint8 view, at any alignment; ``sample_offsets`` int64 [B+1] record indices.  Optional returns: out-of-sensor events per recording
+    (int32 [B]) and flags (int32 [B]; bit 0 event times decrease, bit 1 no event remains / a macro slice is empty)."""
+    _dev(records, sample_offsets)
+    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
+    rec = records if records.is_contiguous() else records.contiguous()
+    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    nrec = rec.numel() // 5
+    B = sample_offsets.numel() - 1
+    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
+    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.int32, device=rec.device)
+    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
+    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
+    ws = torch.empty(_lib.lib().eas_event_histogram_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
+    _call('eas_event_histogram_atis', 10 * nrec + 4 * out.numel(), _lib.lib().eas_event_histogram_atis, ptr(rec), nrec,
+          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
+    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return res if len(res) > 1 else out
+
+
 def event_frames(t, x, y, p, sample_offsets, Tm, H, W, Hc, Wc):
     """raw events -> fp32 count frames on the zero-padded model canvas [B, Tm, 2, Hc, Wc] in one call (K1 + canvas)."""
     _dev(t, x, y, p, sample_offsets)
@@ -116,16 +139,22 @@ def counts_to_canvas(counts, Hc, Wc):
     return out
 
 
-def counts_letterbox(counts, params, Hc, Wc):
-    """int32 counts [B, ..., H, W] -> fp32 [B, ..., Hc, Wc]: per-sample resize (cv2 INTER_LINEAR semantics) to (nw, nh), paste at
-    (dx, dy), optional left-right flip; ``params`` int32 [B, 5] = (nw, nh, dx, dy, flip) (see data.letterbox_params / jitter_params)."""
+def counts_letterbox(counts, params, Hc, Wc, interp='linear'):
+    """int32 counts [B, ..., H, W] -> fp32 [B, ..., Hc, Wc]: per-sample resize to (nw, nh) -- cv2 INTER_LINEAR semantics (Gen1), or
+    ``interp='cubic'``: cv2 INTER_CUBIC (N-Caltech101) --, paste at (dx, dy), optional left-right flip; ``params`` int32 [B, 5] =
+    (nw, nh, dx, dy, flip) (see data.letterbox_params / jitter_params)."""
     _dev(counts, params)
     assert counts.dtype == torch.int32 and params.dtype == torch.int32 and params.shape == (counts.shape[0], 5)
+    assert interp in ('linear', 'cubic')
     counts, params = counts.contiguous(), params.contiguous()
     B, (H, W) = counts.shape[0], counts.shape[-2:]
     F = counts.numel() // (B * H * W)
     out = torch.empty(counts.shape[:-2] + (Hc, Wc), dtype=torch.float32, device=counts.device)
-    check(_lib.lib().eas_counts_letterbox(ptr(counts), ptr(params), B, F, H, W, Hc, Wc, ptr(out), stream()), 'eas_counts_letterbox')
+    if interp == 'linear':
+        check(_lib.lib().eas_counts_letterbox(ptr(counts), ptr(params), B, F, H, W, Hc, Wc, ptr(out), stream()), 'eas_counts_letterbox')
+    else:
+        check(_lib.lib().eas_counts_letterbox_ex(ptr(counts), ptr(params), 1, B, F, H, W, Hc, Wc, ptr(out), stream()),
+              'eas_counts_letterbox_ex')
     return out
 
 

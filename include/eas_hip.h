@@ -102,6 +102,31 @@ int eas_event_frames(const uint32_t* t, const uint16_t* x, const uint16_t* y, co
  * inside the canvas.  cv2 itself is absent from this image: the resize follows OpenCV's published algorithm. */
 int eas_counts_letterbox(const int32_t* counts, const int32_t* params, int B, int F, int H, int W, int Hc, int Wc, float* out,
                          eas_stream_t stream);
+/* The same with a choice of the resize: interp 0 = linear (eas_counts_letterbox, bit-identical), 1 = cubic, cv2.INTER_CUBIC as
+ * NCaltech.batch_resize calls it (ncaltech.py:98-105, 293-295, 313, 342): OpenCV's generic cubic resize for float64 images (float32
+ * weights with A = -0.75, taps s-1 .. s+2 clamped to the image, no clamp of the fraction, float64 sums added left to right,
+ * horizontal pass first), no FMA contraction.  cv2 itself is absent from this image: the resize follows OpenCV's published
+ * algorithm, parity against cv2 unpinned. */
+int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc,
+                            float* out, eas_stream_t stream);
+
+/* N-Caltech101 input: raw ATIS recordings in HBM -> count frames int32 [B][Tl][Tm][2][H][W] (zeroed by the call).  NCaltech.read_ATIS,
+ * generate_slices and agrregate('micro_sum') with measure='count', overlap=0 (yolox/data/datasets/ncaltech.py:63-96, 179-183, 227-237,
+ * 264-269, 368-379).  `records`: nrec records of 5 bytes b0..b4 at ANY alignment, x = b0, y = b1, p = b2 >> 7,
+ * raw = (b2 & 127) << 16 | b3 << 8 | b4; recording b is records [sample_offsets[b], sample_offsets[b+1]) (device, record indices).
+ * A record with y == 240 is an overflow record: no event, it adds 8192 to the time of every later record of its recording.
+ * window_lo < 0: with t_end the time of the recording's last event only events with t_end + window_lo < t <= t_end + window_hi remain;
+ * window_lo >= 0: all remain.  Macro slice k (mw = (tL - t0) / Tl over the remaining first / last times t0, tL) holds
+ * t0 + k mw <= t < t0 + (k+1) mw; inside it, with f / l the times of its first / last member event and w = (l - f) / Tm, an event goes
+ * to micro slice (t - f) / w, dropped when that is >= Tm or w == 0.  Channel 1 for p != 0.  Events with x >= W or y >= H that would
+ * have been binned are dropped and counted in oob_count[b].  flags[b] bit 0: the decoded event times decrease somewhere (frames of
+ * that recording unspecified); bit 1: no event remains or a macro slice is empty (the reference raises; that slice's frames are zero).
+ * oob_count / flags: uint32 [B], may be NULL.  workspace: eas_event_histogram_atis_workspace_bytes(nrec, B, Tl) bytes, 16-byte
+ * aligned (the query needs no GPU).  Offsets outside [0, nrec] are clamped: nothing past nrec is read.  Integer atomics: bit-exact. */
+int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl);
+int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                             int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                             eas_stream_t stream);
 
 /* Bilinear-in-time voxel grid, to_voxel_grid_numpy (yolox/utils/event_reps.py:30-89).
  * out[b][bin][y][x] float64 (zeroed by the call); polarity 0 counts as -1. */
