@@ -240,6 +240,9 @@ PROTOTYPES = {
     'eas_cocoeval_match': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int,
                                      C.c_int64, _P, _P, _P, _P, _P, _P]),
     'eas_cocoeval_accumulate': (C.c_int, [_P] * 5 + [C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    'eas_psee_mark': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    'eas_psee_windows': (C.c_int, [_P] * 5 + [C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [_P] * 6),
+    'eas_psee_expand': (C.c_int, [_P] * 5 + [C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int64] + [_P] * 9),
 }
 
 

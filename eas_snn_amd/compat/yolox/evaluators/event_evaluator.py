@@ -152,14 +152,11 @@ class EventEvaluator:
                 return self._evaluate_loop(model, distributed, decoder, return_outputs, dev, graph_ok)
         return self._evaluate_loop(model, distributed, decoder, return_outputs, dev, graph_ok)
 
-    def _evaluate_loop(self, model, distributed, decoder, return_outputs, dev, graph_ok):
-        data_list, output_data, gt_dict = [], {}, {}
-        from eas_snn_amd._ctx import ctx
-        device_ap = dev.type == 'cuda' and ctx.device_ap
-        feed = [] if device_ap and not distributed else None          # single process: the detections stay on the device for the AP
-        inference_time = nms_time = 0.0
+    def _run_batches(self, model, decoder, dev, graph_ok, times):
+        """the inference loop proper, shared by the evaluators: per batch of the loader forward -> reset_net -> (decoder) -> postprocess,
+        as graph replays where possible; yields (outputs, labels, info_imgs, ids) and adds the two timed phases to
+        ``times`` = [inference, NMS] seconds"""
         n_batches = len(self.dataloader)
-        n_samples = max(n_batches - 1, 1)
         for cur_iter, (imgs, labels, info_imgs, ids) in enumerate(self.dataloader):
             with torch.no_grad():                       # (the reference: inference_mode; graph replays write ordinary static buffers)
                 imgs = imgs.to(dev, torch.float32)
@@ -179,11 +176,21 @@ class EventEvaluator:
                         outputs = decoder(outputs, dtype=outputs.type())
                 if timed:
                     infer_end = time_synchronized()
-                    inference_time += infer_end - start
+                    times[0] += infer_end - start
                 outputs = batch.post() if batch is not None else postprocess(outputs, self.num_classes, self.confthre, self.nmsthre)
                 if timed:
                     nms_end = time_synchronized()
-                    nms_time += nms_end - infer_end
+                    times[1] += nms_end - infer_end
+            yield outputs, labels, info_imgs, ids
+
+    def _evaluate_loop(self, model, distributed, decoder, return_outputs, dev, graph_ok):
+        data_list, output_data, gt_dict = [], {}, {}
+        from eas_snn_amd._ctx import ctx
+        device_ap = dev.type == 'cuda' and ctx.device_ap
+        feed = [] if device_ap and not distributed else None          # single process: the detections stay on the device for the AP
+        times = [0.0, 0.0]
+        n_samples = max(len(self.dataloader) - 1, 1)
+        for outputs, labels, info_imgs, ids in self._run_batches(model, decoder, dev, graph_ok, times):
             if feed is not None:
                 self._feed_device_rows(feed, outputs, info_imgs, ids, dev)
             elems, image_wise = self.convert_to_coco_format(outputs, info_imgs, ids, return_outputs=True)
@@ -193,6 +200,7 @@ class EventEvaluator:
                 label = torch.as_tensor(label)
                 gt_dict[int(img_id)] = {'bboxes': label[:, :4].tolist(), 'width': int(width), 'height': int(height),
                                         'category_ids': [int(c) for c in label[:, 4]]}
+        inference_time, nms_time = times
         statistics = torch.tensor([inference_time, nms_time, n_samples], dtype=torch.float32, device=dev)
         if distributed:
             # ranks finish at different times: meet first, then collect everything on rank 0 (:236-247)
@@ -318,16 +326,20 @@ class EventEvaluator:
         return float(stats[0]), float(stats[1]), text
 
     # ------------------------------------------------------------------ summary (:396-462)
+    def _timing_line(self, statistics):
+        """'Average forward time: .. ms, Average NMS time: .. ms, Average inference time: .. ms' per sample from the statistics triple"""
+        inference_time, nms_time, n_samples = (float(v) for v in statistics.tolist())
+        per = 1000.0 / (n_samples * self.dataloader.batch_size)
+        a_infer, a_nms = inference_time * per, nms_time * per
+        return ', '.join('Average {} time: {:.2f} ms'.format(k, v) for k, v in
+                         zip(['forward', 'NMS', 'inference'], [a_infer, a_nms, a_infer + a_nms])) + '\n'
+
     def evaluate_prediction(self, data_dict, gt_dict, statistics, device=None, feed=None):
         """``device``: where ``ops.coco_eval`` computes the AP (None: the host route); ``feed``: the detections as device arrays
         (``_feed_device_rows``), else ``data_dict`` is uploaded"""
         if not is_main_process():
             return 0, 0, None
-        inference_time, nms_time, n_samples = (float(v) for v in statistics.tolist())
-        per = 1000.0 / (n_samples * self.dataloader.batch_size)
-        a_infer, a_nms = inference_time * per, nms_time * per
-        info = ', '.join('Average {} time: {:.2f} ms'.format(k, v) for k, v in
-                         zip(['forward', 'NMS', 'inference'], [a_infer, a_nms, a_infer + a_nms])) + '\n'
+        info = self._timing_line(statistics)
         if not data_dict:
             return 0, 0, info
         names = getattr(getattr(self.dataloader, 'dataset', None), 'class_names', None) or [str(i) for i in range(self.num_classes)]

@@ -200,19 +200,36 @@ class EventExp(BaseExp):
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)
 
     def get_evaluator(self, batch_size, is_distributed, testdev=False, legacy=False):
-        """reference: event_yolox_base.py:509-534.  ``eval_proph`` (the Prophesee metric toolbox on real Gen1 / 1 Mpx recordings) has no
-        counterpart here: its inference loop is the same one (psee_evaluator.py:180-215), its metric code needs the datasets."""
+        """reference: event_yolox_base.py:509-534.  ``eval_proph`` on a gen* dataset selects PSEEEvaluator (the Prophesee protocol,
+        psee_evaluator.py) when the samples of the evaluation dataset carry their label time in their names (``<recording>a<time in us>``,
+        what the protocol matches on); the synthetic samples do not unless ``eval_label_period_us`` is set, and then EventEvaluator
+        answers, with a warning."""
         from yolox.evaluators import EventEvaluator
+        loader = self.get_eval_loader(batch_size, is_distributed, testdev=testdev, legacy=legacy)
         if 'gen' in str(self.data_name) and self.eval_proph not in (False, 'False', None, 0):
+            from yolox.evaluators.psee_evaluator import PSEEEvaluator, time_from_name
+            camera = str(self.data_name).lower()
+
+            def timed(name):
+                try:
+                    time_from_name(name)
+                    return True
+                except ValueError:
+                    return False
+            names = getattr(getattr(loader, 'dataset', None), 'sample_names', None)
+            if camera in ('gen1', 'gen4') and names is not None and all(timed(n) for n in names):
+                return PSEEEvaluator(dataloader=loader, img_size=self.test_size, confthre=self.test_conf, nmsthre=self.nmsthre,
+                                     num_classes=self.num_classes, testdev=testdev, snn_reset=self.use_spike, dataset=camera,
+                                     downsample_by_2=(camera == 'gen4'))
             # the README's eval line (readme.md:157-160, --eval_proh) selects PSEEEvaluator there: say so instead of substituting silently
             import warnings
-            warnings.warn('eval_proph is set: the reference would build PSEEEvaluator (Prophesee metric toolbox, event_yolox_base.py:512-523). '
-                          'Its metric code is outside this package (it needs the toolbox and the real Gen1 / 1 Mpx label files); this run uses '
-                          'EventEvaluator -- the same inference loop, timers and detection records, COCO-style AP instead of the toolbox\'s.',
-                          RuntimeWarning, stacklevel=2)
-        return EventEvaluator(dataloader=self.get_eval_loader(batch_size, is_distributed, testdev=testdev, legacy=legacy),
-                              img_size=self.test_size, confthre=self.test_conf, nmsthre=self.nmsthre, num_classes=self.num_classes,
-                              testdev=testdev, snn_reset=self.use_spike)
+            warnings.warn('eval_proph is set: the reference would build PSEEEvaluator (Prophesee protocol, event_yolox_base.py:512-523). '
+                          'The sample names of this evaluation dataset carry no label time (<recording>a<microseconds>; the synthetic '
+                          'dataset writes them when exp.eval_label_period_us is set), or data_name is neither gen1 nor gen4, so the '
+                          'protocol has nothing to match on; this run uses EventEvaluator -- the same inference loop, timers and '
+                          'detection records, COCO-style AP per sample.', RuntimeWarning, stacklevel=2)
+        return EventEvaluator(dataloader=loader, img_size=self.test_size, confthre=self.test_conf, nmsthre=self.nmsthre,
+                              num_classes=self.num_classes, testdev=testdev, snn_reset=self.use_spike)
 
     def get_trainer(self, args):
         from yolox.core import Trainer

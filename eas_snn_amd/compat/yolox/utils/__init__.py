@@ -1,5 +1,5 @@
 from .allreduce_norm import all_reduce_norm, get_async_norm_states
-from .boxes import postprocess
+from .boxes import postprocess, xyxy2xywh
 from .checkpoint import load_ckpt, save_checkpoint
 from .dist import (all_gather, ensure_process_group, gather, get_local_rank, get_local_size, get_num_devices, get_rank, get_world_size,
                    is_main_process, synchronize, time_synchronized, wait_for_the_master, wait_process_group_idle)

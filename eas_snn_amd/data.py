@@ -80,6 +80,11 @@ class SyntheticEvalDataset(SyntheticEventDataset):
         super().__init__(exp, length, n_events)
         self.class_names = [str(i) for i in range(exp.num_classes)]
         self.sample_names = [f'synthetic_{i:06d}' for i in range(length)]
+        # opt-in: names that carry a label time, <recording>a<microseconds> (what the Prophesee protocol reads from a Gen1 sample name):
+        # sample i is labelled at i * period
+        period = getattr(exp, 'eval_label_period_us', None)
+        if period:
+            self.sample_names = [f'synthetic_{i:06d}a{i * int(period)}' for i in range(length)]
 
 
 class SyntheticEvalLoader:

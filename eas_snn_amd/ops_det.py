@@ -164,6 +164,136 @@ def coco_summarize(result):
     return np.array([r[0] for r in rows], np.float64), [r[1] for r in rows]
 
 
+
+# ------------------------------------------------------------------------------------------------ Prophesee protocol
+PSEE_CLASSES = {'gen1': ('car', 'pedestrian'), 'gen4': ('pedestrian', 'two-wheeler', 'car')}
+PSEE_SKIP_TS = 500000
+PSEE_KEYS = ('AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L')
+
+
+def psee_thresholds(camera='gen1', downsampled_by_2=False):
+    """(min_box_diag, min_box_side) of evaluate_list (yolox/utils/psee_loader/evaluation.py:24-35)"""
+    if camera not in PSEE_CLASSES:
+        raise ValueError(f"camera must be 'gen1' or 'gen4', got {camera!r}")
+    diag, side = (60, 20) if camera == 'gen4' else (30, 10)
+    return (diag // 2, side // 2) if downsampled_by_2 else (diag, side)
+
+
+def _psee_set(s, with_score):
+    """one box set as contiguous device arrays of the kernels' types: (t int64 [N], box fp32 [N,4], cls int32 [N], score fp32 [N] | None,
+    file_offsets int64 [F+1])"""
+    if len(s) != (5 if with_score else 4):
+        raise ValueError('a box set is (t, box, cls, file_offsets) for ground truths and (t, box, cls, score, file_offsets) for detections')
+    t, box, cls = s[0], s[1], s[2]
+    score, off = (s[3], s[4]) if with_score else (None, s[3])
+    _dev(t, box, cls, score, off)
+    N = int(t.numel())
+    t, cls, off = t.to(torch.int64).contiguous().reshape(N), cls.to(torch.int32).contiguous().reshape(-1), off.to(torch.int64).contiguous().reshape(-1)
+    box = _f32c(box).reshape(-1, 4)
+    score = _f32c(score).reshape(-1) if with_score else None
+    if box.shape[0] != N or cls.numel() != N or (with_score and score.numel() != N) or off.numel() < 1:
+        raise ValueError('the arrays of a box set must have one entry per row, and file_offsets F + 1 entries')
+    return t, box, cls, score, off
+
+
+def _scan(flags, exclusive):
+    """int64 prefix sum of int32 flags: inclusive [N], or exclusive with the total appended [N + 1]"""
+    if not exclusive:
+        return torch.cumsum(flags, 0, dtype=torch.int64)
+    out = torch.zeros(flags.numel() + 1, dtype=torch.int64, device=flags.device)
+    torch.cumsum(flags, 0, dtype=torch.int64, out=out[1:])
+    return out
+
+
+@torch.no_grad()
+def psee_match(gt, dt, camera='gen1', downsampled_by_2=False, apply_bbox_filters=True, time_tol=50000, sizes=None):
+    """The Prophesee protocol in front of the COCO evaluation (``evaluate_list`` -> ``filter_boxes`` -> ``evaluate_detection`` /
+    ``_match_times`` -> ``_to_coco_format`` of yolox/utils/psee_loader), on the device (the eas_psee kernels).  ``gt`` = (t, box, cls,
+    file_offsets), ``dt`` = (t, box, cls, score, file_offsets): t int64 microseconds, box (x, y, w, h) float32, cls the 0-based class id;
+    the rows of file f are [file_offsets[f], file_offsets[f + 1]) and ascend in t; both sets list the same files.
+
+    Boxes of the first 0.5 s and boxes below the camera's size thresholds leave both sets (``apply_bbox_filters``); every distinct
+    timestamp of a file's remaining ground truths is one image, numbered over the files in order, then by time; its detections are the
+    file's remaining detections within +-``time_tol`` of it, both ends included -- a detection is copied into every image whose window
+    holds it, and detections of a file without remaining ground truth disappear.
+
+    -> dict: the arguments of ``ops.coco_eval`` (det_img int32 [D], det_cls int32, det_box, det_score, gt_img int32 [G], gt_cls, gt_box,
+    gt_id = 1..G int64; rows image-major, inside an image in file row order), num_images, num_classes (from the camera), image_file
+    int32 [I], image_t int64 [I], max_gt (the most ground truths in one (image, class)).
+
+    The numbers only the device knows (images, detection rows, ground truths, max_gt) are read once in the middle: one host
+    synchronisation.  ``sizes`` = (num_images, D, G, max_gt) of an earlier call on inputs of the same content skips the read (graph
+    capture)."""
+    g_t, g_box, g_cls, _, g_off = _psee_set(gt, False)
+    d_t, d_box, d_cls, d_score, d_off = _psee_set(dt, True)
+    if g_off.numel() != d_off.numel():
+        raise ValueError(f'ground truths list {g_off.numel() - 1} files, detections {d_off.numel() - 1}')
+    min_diag, min_side = psee_thresholds(camera, downsampled_by_2)
+    K = len(PSEE_CLASSES[camera])
+    dev = g_box.device
+    Ng, Nd, F = int(g_t.numel()), int(d_t.numel()), int(g_off.numel()) - 1
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+
+    def result(I, D, G, max_gt, rows=None, image_file=None, image_t=None):
+        if rows is None:
+            rows = (torch.empty(0, **i32), torch.empty(0, **i32), torch.empty((0, 4), dtype=torch.float32, device=dev), torch.empty(0, **i64),
+                    torch.empty(0, **i32), torch.empty(0, **i32), torch.empty((0, 4), dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.float32, device=dev))
+        return dict(gt_img=rows[0], gt_cls=rows[1], gt_box=rows[2], gt_id=rows[3], det_img=rows[4], det_cls=rows[5], det_box=rows[6],
+                    det_score=rows[7], num_images=I, num_classes=K, max_gt=max_gt,
+                    image_file=torch.empty(0, **i32) if image_file is None else image_file[:I],
+                    image_t=torch.empty(0, **i64) if image_t is None else image_t[:I])
+    if Ng == 0 or F == 0:
+        return result(0, 0, 0, 0)
+    L = _lib.lib()
+    filt = int(bool(apply_bbox_filters))
+    g_keep, g_first, d_keep = torch.empty(Ng, **i32), torch.empty(Ng, **i32), torch.empty(Nd, **i32)
+    _call('eas_psee_mark', 32 * Ng, L.eas_psee_mark, ptr(g_t), ptr(g_box), Ng, ptr(g_off), F, PSEE_SKIP_TS, min_diag, min_side, filt,
+          ptr(g_keep), ptr(g_first), stream())
+    if Nd:
+        _call('eas_psee_mark', 28 * Nd, L.eas_psee_mark, ptr(d_t), ptr(d_box), Nd, ptr(d_off), F, PSEE_SKIP_TS, min_diag, min_side, filt,
+              ptr(d_keep), None, stream())
+    g_keep_scan, g_img_scan, d_keep_scan = _scan(g_keep, True), _scan(g_first, False), _scan(d_keep, True)
+    image_file, image_t = torch.empty(Ng, **i32), torch.empty(Ng, **i64)
+    win_lo, win_cnt, pair_count = torch.empty(Ng, **i64), torch.empty(Ng, **i64), torch.empty((Ng, K), **i32)
+    _call('eas_psee_windows', 60 * Ng, L.eas_psee_windows, ptr(g_t), ptr(g_cls), ptr(g_keep), ptr(g_first), ptr(g_img_scan), Ng, ptr(g_off),
+          ptr(d_t), ptr(d_off), ptr(d_keep_scan), Nd, F, int(time_tol), K, ptr(image_file), ptr(image_t), ptr(win_lo), ptr(win_cnt),
+          ptr(pair_count), stream())
+    det_off = _scan(win_cnt, True)
+    if sizes is None:
+        # the one read: images, expanded detection rows, kept ground truths, the most ground truths in one (image, class)
+        I, D, G, max_gt = torch.stack((g_img_scan[-1], det_off[-1], g_keep_scan[-1], pair_count.max().to(torch.int64))).tolist()
+    else:
+        I, D, G, max_gt = (int(v) for v in sizes)
+    if I == 0:
+        return result(0, 0, 0, 0)
+    rows = (torch.empty(G, **i32), torch.empty(G, **i32), torch.empty((G, 4), dtype=torch.float32, device=dev), torch.empty(G, **i64),
+            torch.empty(D, **i32), torch.empty(D, **i32), torch.empty((D, 4), dtype=torch.float32, device=dev),
+            torch.empty(D, dtype=torch.float32, device=dev))
+    _call('eas_psee_expand', 40 * Ng + 60 * D, L.eas_psee_expand, ptr(g_keep), ptr(g_keep_scan), ptr(g_img_scan), ptr(g_cls), ptr(g_box), Ng, G,
+          ptr(det_off), ptr(win_lo), I, ptr(d_keep_scan), ptr(d_cls), ptr(d_box), ptr(d_score), Nd, D, *(ptr(r) for r in rows), stream())
+    return result(I, D, G, max_gt, rows, image_file, image_t)
+
+
+@torch.no_grad()
+def psee_eval(gt, dt, camera='gen1', downsampled_by_2=False, apply_bbox_filters=True, time_tol=50000):
+    """``evaluate_list`` (yolox/utils/psee_loader/evaluation.py) on the device: ``psee_match``, then ``coco_eval`` with annotation ids
+    1..G (as _to_coco_format numbers them: no annotation has the id 0 that never counts as a match) and pycocotools' default parameters,
+    then ``coco_summarize``.  -> ({'AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L'} = stats[0:6], the ``coco_eval`` result with the
+    ``psee_match`` sizes added).  No image (no ground truth survives the filter) gives -1.0 six times.  ``coco_eval_supported`` is asked
+    with the matched sizes before any evaluation kernel is launched; a refusal raises with the numbers."""
+    m = psee_match(gt, dt, camera, downsampled_by_2, apply_bbox_filters, time_tol)
+    D, G, I, K, max_gt = int(m['det_score'].numel()), int(m['gt_img'].numel()), m['num_images'], m['num_classes'], m['max_gt']
+    if not coco_eval_supported(D, G, I, K, max_gt=max_gt):
+        raise _lib.EasHipError(f'psee_eval: the matched rows are beyond the limits of the eas_cocoeval kernels (D={D} G={G} images={I} '
+                               f'classes={K}, {max_gt} ground truths in one (image, category); include/eas_hip.h lists them)')
+    res = coco_eval(m['det_img'], m['det_cls'], m['det_box'], m['det_score'], m['gt_img'], m['gt_cls'], m['gt_box'], I, K, gt_id=m['gt_id'],
+                    max_gt=max_gt)
+    stats, lines = coco_summarize(res)
+    res = dict(res, detections=D, ground_truths=G, images=I, lines=lines, stats=stats)
+    return {k: float(stats[j]) for j, k in enumerate(PSEE_KEYS)}, res
+
+
 def simota_supported(gt_valid, bbox_preds):
     return bbox_preds.is_cuda and bbox_preds.dtype == torch.float32 and gt_valid.shape[1] <= 255 and bbox_preds.shape[1] <= 12288
 

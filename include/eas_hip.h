@@ -867,6 +867,36 @@ int eas_cocoeval_accumulate(const int64_t* key2, const int64_t* order2, const in
                             int64_t D, const int32_t* npig, int K, int T, const double* rec_thr, int R, int A, const int32_t* max_dets, int M,
                             double* precision, double* recall, void* workspace, eas_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prophesee-protocol matching in front of the evaluation above (additive, ABI 9): the box filter of evaluate_list / filter_boxes
+ * (yolox/utils/psee_loader/evaluation.py:24-40, io/box_filtering.py:36-41), the time matching of evaluate_detection / _match_times
+ * (metrics/coco_eval.py:42-91) and the rows of _to_coco_format (:128-179), left on the device for eas_cocoeval_*.
+ * A box set: t int64 [N], box float32 [N][4] (x, y, w, h), cls int32 [N], score float32 [N] (detections), file_offsets int64 [F+1]; the
+ * rows of a file are contiguous and ascending in t; both sets have the same F files.
+ * Call order: eas_psee_mark (each set) -> int64 scans by the caller (gt_keep_scan [Ng+1] and dt_keep_scan [Nd+1] exclusive with the total
+ * in the last entry, gt_img_scan [Ng] inclusive over `first`) -> eas_psee_windows -> det_off [Ng+1] = exclusive scan of win_cnt by the
+ * caller; I = gt_img_scan[Ng-1] images, D = det_off[I] detection rows, G = gt_keep_scan[Ng] ground truths: sizes only the device knows,
+ * read once by the caller -> eas_psee_expand.  Limits: N, F, D < 2^31; K <= 1024; min_diag <= 32767.  Zero rows or files are valid and
+ * launch nothing.  Indices read from the device arrays are clamped into their tables. */
+/* keep[r] = t > skip_ts && w*w + h*h >= min_diag^2 && w >= min_side && h >= min_side in float32 (products and sum rounded one by one, no
+ * fma), 1 for every row with apply_filters = 0; first (nullable; needs file_offsets) = kept and no earlier kept row of the file has this t. */
+int eas_psee_mark(const int64_t* t, const float* box, int64_t N, const int64_t* file_offsets, int64_t F, int64_t skip_ts, int min_diag,
+                  int min_side, int apply_filters, int32_t* keep, int32_t* first, eas_stream_t stream);
+/* per image i < I (arrays of Ng entries): image_file, image_t, win_lo = position of the window's first row among the kept detections,
+ * win_cnt = kept detections of the image's file with image_t - time_tol <= t <= image_t + time_tol (0 behind the last image);
+ * pair_count [Ng][K] = kept ground truths per (image, class 0..K-1). */
+int eas_psee_windows(const int64_t* gt_t, const int32_t* gt_cls, const int32_t* gt_keep, const int32_t* gt_first, const int64_t* gt_img_scan,
+                     int64_t Ng, const int64_t* gt_file_offsets, const int64_t* dt_t, const int64_t* dt_file_offsets,
+                     const int64_t* dt_keep_scan, int64_t Nd, int64_t F, int64_t time_tol, int K, int32_t* image_file, int64_t* image_t,
+                     int64_t* win_lo, int64_t* win_cnt, int32_t* pair_count, eas_stream_t stream);
+/* the flat rows: out_gt_* [G] (image, class, box, id = 1..G) and out_det_* [D] (image, class, box, score), image-major, inside an image
+ * in file row order; a detection appears once per image whose window holds it. */
+int eas_psee_expand(const int32_t* gt_keep, const int64_t* gt_keep_scan, const int64_t* gt_img_scan, const int32_t* gt_cls,
+                    const float* gt_box, int64_t Ng, int64_t G, const int64_t* det_off, const int64_t* win_lo, int64_t I,
+                    const int64_t* dt_keep_scan, const int32_t* dt_cls, const float* dt_box, const float* dt_score, int64_t Nd, int64_t D,
+                    int32_t* out_gt_img, int32_t* out_gt_cls, float* out_gt_box, int64_t* out_gt_id, int32_t* out_det_img,
+                    int32_t* out_det_cls, float* out_det_box, float* out_det_score, eas_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
