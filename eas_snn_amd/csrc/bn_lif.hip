@@ -10,8 +10,12 @@
 // HBM traffic per neuron-step: stats 4 B (read y); fwd 8 B (read y, write s);
 // bwd 20 B (pass 1 reads y, grad_s; pass 2 reads them again and writes grad_y).  Only y is kept
 // for backward: h_t is recomputed in registers from y (T <= 8).
+//
+// Shared with bn_act.hip through eas_common.h: the chunk plan (bn_pick_chunks, EAS_BN_MAX_CHUNKS), the pending-statistics rule (bn_fin_from),
+// mean / invstd from totals (bn_from_totals), and the BatchNorm backward skeleton -- chunk partials -> means (bn_bwd_means), one-pass block
+// totals (eas_block_totals), the apply expression (bn_bwd_apply).  The scalar parameter gradients' final stage (eas_lif_scalar_grads) and
+// the flag dispatch of the forward (eas_lif_dispatch) are the ones lif.hip uses.
 #include <stdlib.h>
-
 #include <string.h>
 
 #include "bn_lif_policy.h"
@@ -19,26 +23,14 @@
 
 namespace {
 
-constexpr int VEC = 4;
-constexpr int kMaxChunks = 64;
 constexpr int NW = EAS_BLOCK / EAS_WAVE;
-
-static inline int pick_chunks(int64_t groups_per_channel, int C) {
-    int64_t want = (groups_per_channel + EAS_BLOCK - 1) / EAS_BLOCK;  // one group per thread
-    int64_t cap = 8192 / (C > 0 ? C : 1);                                // keep the grid around <= 8k blocks
-    if (cap < 1) cap = 1;
-    if (cap > kMaxChunks) cap = kMaxChunks;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
 
 // ------------------------------------------------------------------------------------------------ stats
 __global__ __launch_bounds__(EAS_BLOCK) void bn_stats_partial(const float* __restrict__ y, int TN, int C, int HW,
                                                               double* __restrict__ part, int Cy) {
     __shared__ double red[NW];
     const int c = blockIdx.y;
-    const int hw4 = HW / VEC;
+    const int hw4 = HW / EAS_VEC;
     const int64_t groups = (int64_t)TN * hw4;
     double s = 0.0, ss = 0.0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -64,8 +56,8 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_stats_partial(const float* __res
     const double ts = eas_block_sum<double, NW>(s, red);
     const double tss = eas_block_sum<double, NW>(ss, red);
     if (threadIdx.x == 0) {
-        part[((int64_t)c * kMaxChunks + blockIdx.x) * 2 + 0] = ts;
-        part[((int64_t)c * kMaxChunks + blockIdx.x) * 2 + 1] = tss;
+        part[((int64_t)c * EAS_BN_MAX_CHUNKS + blockIdx.x) * 2 + 0] = ts;
+        part[((int64_t)c * EAS_BN_MAX_CHUNKS + blockIdx.x) * 2 + 1] = tss;
     }
 }
 
@@ -86,36 +78,19 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_stats_partial_scalar(const float
     const double ts = eas_block_sum<double, NW>(s, red);
     const double tss = eas_block_sum<double, NW>(ss, red);
     if (threadIdx.x == 0) {
-        part[((int64_t)c * kMaxChunks + blockIdx.x) * 2 + 0] = ts;
-        part[((int64_t)c * kMaxChunks + blockIdx.x) * 2 + 1] = tss;
+        part[((int64_t)c * EAS_BN_MAX_CHUNKS + blockIdx.x) * 2 + 0] = ts;
+        part[((int64_t)c * EAS_BN_MAX_CHUNKS + blockIdx.x) * 2 + 1] = tss;
     }
 }
 
-__global__ __launch_bounds__(EAS_WAVE) void bn_stats_finalize(const double* __restrict__ part, int nchunks, double count,
-                                                              int replicas, float eps, float momentum, float* __restrict__ mean,
-                                                              float* __restrict__ invstd, float* __restrict__ rmean,
-                                                              float* __restrict__ rvar) {
+// one wave per channel: the chunk partials of bn_stats_partial -> mean / invstd and the running statistics (identical replicas leave
+// mean / var unchanged, only the sample count grows)
+__global__ __launch_bounds__(EAS_WAVE) void bn_stats_finalize(BnFin fin) {
     const int c = blockIdx.x;
-    double s = 0.0, ss = 0.0;
-    if ((int)threadIdx.x < nchunks) {
-        s = part[((int64_t)c * kMaxChunks + threadIdx.x) * 2 + 0];
-        ss = part[((int64_t)c * kMaxChunks + threadIdx.x) * 2 + 1];
-    }
-    s = eas_wave_sum(s);
-    ss = eas_wave_sum(ss);
-    if (threadIdx.x == 0) {
-        const double m = s / count;
-        double var = ss / count - m * m;
-        if (var < 0.0) var = 0.0;
-        mean[c] = (float)m;
-        invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (rmean) {
-            const double full = count * replicas;   // identical replicas leave mean/var unchanged, only the sample count grows
-            const double unbiased = full > 1.0 ? var * full / (full - 1.0) : var;
-            rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-            rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-        }
-    }
+    double s, ss;
+    bn_wave_partials<2>(fin.part, (int64_t)c * fin.pitch, fin.nchunks, s, ss);
+    float mu, istd;
+    if (threadIdx.x == 0) bn_from_totals(fin, c, s, ss, true, mu, istd);
 }
 
 struct BnLifOut {
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_fwd_kernel(const float* __re
     const int64_t Mo = ox.out_ctot ? (int64_t)N * ox.out_ctot * HW : (int64_t)N * C * HW;
     const float k = eas_lif_k(p);
     const float omk = 1.0f - k;
-    const int hw4 = HW / VEC;
+    const int hw4 = HW / EAS_VEC;
     const int64_t groups = (int64_t)N * hw4;
     const int64_t M = (int64_t)N * C * HW;
     const int Cy = ox.y_ctot ? ox.y_ctot : C;
@@ -163,9 +138,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_fwd_kernel(const float* __re
     for (int64_t g = (int64_t)chunk * blockDim.x + threadIdx.x; g < groups; g += (int64_t)nchunks_g * blockDim.x, gw.next()) {
         const int64_t n = gw.n;
         const int q = gw.q;
-        const int64_t base = (n * C + c) * (int64_t)HW + (int64_t)q * VEC;
+        const int64_t base = (n * C + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
         float4 ys[T_];
-        const int64_t ybase = (n * Cy + c) * (int64_t)HW + (int64_t)q * VEC;
+        const int64_t ybase = (n * Cy + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
 #pragma unroll
         for (int t = 0; t < T_; ++t) ys[t] = *reinterpret_cast<const float4*>(y + (int64_t)t * yts + ybase);
         const float vr0 = HARD ? p.v_reset : 0.0f;
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_fwd_kernel(const float* __re
                 const float4 r = *reinterpret_cast<const float4*>(ox.residual + (int64_t)t * M + base);
                 s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
             }
-            const int64_t obase = ox.out_ctot ? (n * ox.out_ctot + c) * (int64_t)HW + (int64_t)q * VEC : base;
+            const int64_t obase = ox.out_ctot ? (n * ox.out_ctot + c) * (int64_t)HW + (int64_t)q * EAS_VEC : base;
             *reinterpret_cast<float4*>(spikes + (int64_t)t * Mo + obase) = s;
         }
         if (v_out) *reinterpret_cast<float4*>(v_out + base) = v;
@@ -350,7 +325,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
     const float k = eas_lif_k(p);
     const float omk = 1.0f - k;
     const bool detach = (p.flags & EAS_LIF_DETACH_RESET) != 0;
-    const int hw4 = HW / VEC;
+    const int hw4 = HW / EAS_VEC;
     const int64_t groups = (int64_t)N * hw4;
     const int64_t M = (int64_t)N * C * HW;
     const float invT = 1.0f / (float)T_;
@@ -360,37 +335,15 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
     const int64_t Mg = gs_ctot ? (int64_t)N * gs_ctot * HW : M;      // grad_s may be a channel slice of a wider tensor
     const int Cg = gs_ctot ? gs_ctot : C;
     float m1 = 0.f, m2 = 0.f;
-    if (APPLY) {
-        // fixed-order reduction of this channel's chunk partials (every block computes the same value)
-        if (threadIdx.x < EAS_WAVE) {
-            double s1 = 0.0, s2 = 0.0;
-            if ((int)threadIdx.x < nchunks) {
-                s1 = part[((int64_t)c * kMaxChunks + threadIdx.x) * 4 + 0];
-                s2 = part[((int64_t)c * kMaxChunks + threadIdx.x) * 4 + 1];
-            }
-            s1 = eas_wave_sum(s1);
-            s2 = eas_wave_sum(s2);
-            if (threadIdx.x == 0) {
-                const double cnt = (double)T_ * N * HW;
-                bc[0] = (float)(s1 / cnt);
-                bc[1] = (float)(s2 / cnt);
-                if (chunk == 0) {
-                    grad_beta[c] = (float)s1;
-                    grad_gamma[c] = (float)s2;
-                }
-            }
-        }
-        __syncthreads();
-        if (batch_stats) { m1 = bc[0]; m2 = bc[1]; }
-    }
+    if (APPLY) bn_bwd_means<4>(part, c, nchunks, (double)T_ * N * HW, chunk, batch_stats, grad_beta, grad_gamma, bc, m1, m2);
     float s1 = 0.f, s2 = 0.f, dk = 0.f, da = 0.f;
     GroupWalk gw((int64_t)chunk * blockDim.x + threadIdx.x, (int64_t)nchunks_g * blockDim.x, hw4);
     for (int64_t g = (int64_t)chunk * blockDim.x + threadIdx.x; g < groups; g += (int64_t)nchunks_g * blockDim.x, gw.next()) {
         const int64_t n = gw.n;
         const int q = gw.q;
-        const int64_t base = (n * C + c) * (int64_t)HW + (int64_t)q * VEC;
+        const int64_t base = (n * C + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
         float4 ys[T_], gsv[T_];
-        const int64_t ybase = (n * Cy + c) * (int64_t)HW + (int64_t)q * VEC;
+        const int64_t ybase = (n * Cy + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
 #pragma unroll
         for (int t = 0; t < T_; ++t) ys[t] = *reinterpret_cast<const float4*>(y + (int64_t)t * yts + ybase);
         float4 gm = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -402,8 +355,8 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
         for (int t = 0; t < T_; ++t) {
             gsv[t] = gm;
             if (FAST || grad_s) {
-                const int64_t gbase = FAST ? (n * Cg + c) * (int64_t)HW + (int64_t)q * VEC
-                                           : (gs_ctot ? (n * gs_ctot + c) * (int64_t)HW + (int64_t)q * VEC : base);
+                const int64_t gbase = FAST ? (n * Cg + c) * (int64_t)HW + (int64_t)q * EAS_VEC
+                                           : (gs_ctot ? (n * gs_ctot + c) * (int64_t)HW + (int64_t)q * EAS_VEC : base);
                 const float4 g4 = *reinterpret_cast<const float4*>(grad_s + (int64_t)t * Mg + gbase);
                 gsv[t].x += g4.x; gsv[t].y += g4.y; gsv[t].z += g4.z; gsv[t].w += g4.w;
             }
@@ -413,7 +366,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
         if (!FAST && v_init) v0 = *reinterpret_cast<const float4*>(v_init + base);
         float4 outv[T_];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
+        for (int e = 0; e < EAS_VEC; ++e) {
             float yv[T_], gs[T_], dz[T_];
 #pragma unroll
             for (int t = 0; t < T_; ++t) {
@@ -425,9 +378,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
             recompute_dz<T_, HARD, DI, STRICT, POL>(yv, gs, v0e, scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, da);
 #pragma unroll
             for (int t = 0; t < T_; ++t) {
-                const float xhat = (yv[t] - mu) * istd;
+                const float xhat = bn_xhat(yv[t], mu, istd);
                 if (APPLY) {
-                    reinterpret_cast<float*>(&outv[t])[e] = scale * (dz[t] - m1 - xhat * m2);
+                    reinterpret_cast<float*>(&outv[t])[e] = bn_bwd_apply(scale, dz[t], xhat, m1, m2);
                 } else {
                     s1 += dz[t];
                     s2 += dz[t] * xhat;
@@ -447,28 +400,15 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
             }
         }
     }
-    if (APPLY && grad_w && finalize && chunk == 0 && c == c_begin) {
-        // dL/dw of the (scalar) PLIF decay: fixed-order sum of every (channel, chunk) partial of pass 1, by one block
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < C * nchunks; i += blockDim.x) {
+    if (APPLY && finalize && chunk == 0 && c == c_begin) {
+        // dL/dw of the (scalar) PLIF decay and dL/dalpha of the learnable surrogate slope: fixed-order sums of every (channel, chunk) partial
+        // of pass 1 (slots 2 / 3), by one block
+        auto slot = [&](int i, int k_) {
             const int cc = i / nchunks, j = i - cc * nchunks;
-            acc += part[((int64_t)cc * kMaxChunks + j) * 4 + 2];
-        }
-        const double tot = eas_block_sum<double, NW>(acc, red);
-        if (threadIdx.x == 0) *grad_w = (float)tot * (k * (1.0f - k));
-    }
-    if (APPLY && grad_alpha && finalize && chunk == 0 && c == c_begin) {
-        // dL/dalpha of the learnable surrogate slope: same fixed-order sum over slot 3 of the partials
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < C * nchunks; i += blockDim.x) {
-            const int cc = i / nchunks, j = i - cc * nchunks;
-            acc += part[((int64_t)cc * kMaxChunks + j) * 4 + 3];
-        }
-        const double tot = eas_block_sum<double, NW>(acc, red);
-        if (threadIdx.x == 0) {
-            const float a = *alpha_dev;
-            *grad_alpha = (float)tot * (a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f));
-        }
+            return part[((int64_t)cc * EAS_BN_MAX_CHUNKS + j) * 4 + k_];
+        };
+        eas_lif_scalar_grads(C * nchunks, [&](int i) { return slot(i, 2); }, [&](int i) { return slot(i, 3); }, p.w_logit, alpha_dev, grad_w,
+                             grad_alpha, red);
     }
     if (!APPLY) {
         const double t1 = eas_block_sum<double, NW>((double)s1, red);
@@ -477,7 +417,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_kernel(
         double t4 = 0.0;
         if (sg_id == EAS_SG_PATAN) t4 = eas_block_sum<double, NW>((double)da, red);
         if (threadIdx.x == 0) {
-            double* o = part + ((int64_t)c * kMaxChunks + chunk) * 4;
+            double* o = part + ((int64_t)c * EAS_BN_MAX_CHUNKS + chunk) * 4;
             o[0] = t1; o[1] = t2; o[2] = t3; o[3] = t4;
         }
     }
@@ -510,7 +450,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
     const float k = eas_lif_k(p);
     const float omk = 1.0f - k;
     const bool detach = (p.flags & EAS_LIF_DETACH_RESET) != 0;
-    const int hw4 = HW / VEC;
+    const int hw4 = HW / EAS_VEC;
     const int groups = N * hw4;
     const int64_t M = (int64_t)N * C * HW;
     const int Cy = y_ctot ? y_ctot : C;
@@ -524,8 +464,8 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
         const int g = threadIdx.x + i * NT_;
         const int gg = g < groups ? g : groups - 1;          // surplus threads re-read the last group (their results are not used)
         const int n = gg / hw4, q = gg - n * hw4;
-        const int64_t base = ((int64_t)n * C + c) * (int64_t)HW + (int64_t)q * VEC;
-        ybase[i] = ((int64_t)n * Cy + c) * (int64_t)HW + (int64_t)q * VEC;
+        const int64_t base = ((int64_t)n * C + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
+        ybase[i] = ((int64_t)n * Cy + c) * (int64_t)HW + (int64_t)q * EAS_VEC;
 #pragma unroll
         for (int t = 0; t < T_; ++t) ys[i][t] = *reinterpret_cast<const float4*>(y + (int64_t)t * My + ybase[i]);
         float4 gm = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -537,7 +477,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
         for (int t = 0; t < T_; ++t) {
             gsv[i][t] = gm;
             if (grad_s) {
-                const int64_t gbase = gs_ctot ? ((int64_t)n * gs_ctot + c) * (int64_t)HW + (int64_t)q * VEC : base;
+                const int64_t gbase = gs_ctot ? ((int64_t)n * gs_ctot + c) * (int64_t)HW + (int64_t)q * EAS_VEC : base;
                 const float4 g4 = *reinterpret_cast<const float4*>(grad_s + (int64_t)t * Mg + gbase);
                 gsv[i][t].x += g4.x; gsv[i][t].y += g4.y; gsv[i][t].z += g4.z; gsv[i][t].w += g4.w;
             }
@@ -547,12 +487,12 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
         if (v_init) v0[i] = *reinterpret_cast<const float4*>(v_init + base);
     }
     // pass 1 (registers): the channel's sums
-    float s1 = 0.f, s2 = 0.f, dk = 0.f, da = 0.f;
+    float sum[4] = {0.f, 0.f, 0.f, 0.f};      // dz, dz * xhat, dL/dk, dL/d|alpha|
 #pragma unroll
     for (int i = 0; i < GPT; ++i) {
         const bool live = threadIdx.x + i * NT_ < groups;
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
+        for (int e = 0; e < EAS_VEC; ++e) {
             float yv[T_], gs[T_], dz[T_];
 #pragma unroll
             for (int t = 0; t < T_; ++t) {
@@ -564,30 +504,20 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
             if (live) {
 #pragma unroll
                 for (int t = 0; t < T_; ++t) {
-                    s1 += dz[t];
-                    s2 += dz[t] * ((yv[t] - mu) * istd);
+                    sum[0] += dz[t];
+                    sum[1] += dz[t] * bn_xhat(yv[t], mu, istd);
                 }
-                dk += dke;
-                da += dae;
+                sum[2] += dke;
+                sum[3] += dae;
             }
         }
     }
-    double t1 = eas_wave_sum((double)s1), t2 = eas_wave_sum((double)s2), t3 = eas_wave_sum((double)dk), t4 = eas_wave_sum((double)da);
-    if ((threadIdx.x & (EAS_WAVE - 1)) == 0) {
-        const int w = threadIdx.x / EAS_WAVE;
-        red[0][w] = t1; red[1][w] = t2; red[2][w] = t3; red[3][w] = t4;
-    }
-    __syncthreads();
+    double t[4];
+    eas_block_totals<NWV, 4>(sum, red, t);
     if (threadIdx.x == 0) {
-        t1 = t2 = t3 = t4 = 0.0;
-        for (int w = 0; w < NWV; ++w) { t1 += red[0][w]; t2 += red[1][w]; t3 += red[2][w]; t4 += red[3][w]; }
-        const double cnt = (double)T_ * N * HW;
-        bc[0] = (float)(t1 / cnt);
-        bc[1] = (float)(t2 / cnt);
-        grad_beta[c] = (float)t1;
-        grad_gamma[c] = (float)t2;
-        double* o = part + ((int64_t)c * kMaxChunks) * 4;      // chunk 0 of the two-pass layout: read by bn_lif_bwd_scalars_kernel
-        o[0] = t1; o[1] = t2; o[2] = t3; o[3] = sg_id == EAS_SG_PATAN ? t4 : 0.0;
+        bn_bwd_publish(t[0], t[1], (double)T_ * N * HW, true, c, grad_beta, grad_gamma, bc);
+        double* o = part + ((int64_t)c * EAS_BN_MAX_CHUNKS) * 4;      // chunk 0 of the two-pass layout: read by bn_lif_bwd_scalars_kernel
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = sg_id == EAS_SG_PATAN ? t[3] : 0.0;
     }
     __syncthreads();
     const float m1 = batch_stats ? bc[0] : 0.f, m2 = batch_stats ? bc[1] : 0.f;
@@ -597,7 +527,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
         if (threadIdx.x + i * NT_ >= groups) continue;
         float4 outv[T_];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
+        for (int e = 0; e < EAS_VEC; ++e) {
             float yv[T_], gs[T_], dz[T_];
 #pragma unroll
             for (int t = 0; t < T_; ++t) {
@@ -607,7 +537,7 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
             float dke = 0.f, dae = 0.f;
             recompute_dz<T_, HARD, DI, STRICT, POL>(yv, gs, reinterpret_cast<const float*>(&v0[i])[e], scale, shift, k, omk, p, detach, sg_id, alpha, dz, dke, dae);
 #pragma unroll
-            for (int t = 0; t < T_; ++t) reinterpret_cast<float*>(&outv[t])[e] = scale * (dz[t] - m1 - ((yv[t] - mu) * istd) * m2);
+            for (int t = 0; t < T_; ++t) reinterpret_cast<float*>(&outv[t])[e] = bn_bwd_apply(scale, dz[t], bn_xhat(yv[t], mu, istd), m1, m2);
         }
 #pragma unroll
         for (int t = 0; t < T_; ++t) *reinterpret_cast<float4*>(grad_y + (int64_t)t * My + ybase[i]) = outv[t];
@@ -619,22 +549,8 @@ __global__ __launch_bounds__(NT_) void bn_lif_bwd_small_kernel(
 __global__ __launch_bounds__(EAS_BLOCK) void bn_lif_bwd_scalars_kernel(const double* __restrict__ part, int C, EasLifParams p, float* __restrict__ grad_w,
                                                                        const float* __restrict__ alpha_dev, float* __restrict__ grad_alpha) {
     __shared__ double red[NW];
-    const float k = eas_lif_k(p);
-    if (grad_w) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < C; i += blockDim.x) acc += part[((int64_t)i * kMaxChunks) * 4 + 2];
-        const double tot = eas_block_sum<double, NW>(acc, red);
-        if (threadIdx.x == 0) *grad_w = (float)tot * (k * (1.0f - k));
-    }
-    if (grad_alpha) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < C; i += blockDim.x) acc += part[((int64_t)i * kMaxChunks) * 4 + 3];
-        const double tot = eas_block_sum<double, NW>(acc, red);
-        if (threadIdx.x == 0) {
-            const float a = *alpha_dev;
-            *grad_alpha = (float)tot * (a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f));
-        }
-    }
+    auto slot = [&](int i, int k_) { return part[((int64_t)i * EAS_BN_MAX_CHUNKS) * 4 + k_]; };
+    eas_lif_scalar_grads(C, [&](int i) { return slot(i, 2); }, [&](int i) { return slot(i, 3); }, p.w_logit, alpha_dev, grad_w, grad_alpha, red);
 }
 
 template <int T_, bool HARD, bool DI, bool STRICT>
@@ -653,14 +569,14 @@ int launch_fwd_t(const float* y, const float* mean, const float* invstd, const f
         // waves in flight (measured on config 2: 1.02 ms per step for all layers against 1.10 / 1.24 ms with 2 / 4 pixels per thread and
         // 1.10 ms for the fp32-writing kernel)
         constexpr int PV = 1;
-        const int chunks = pick_chunks((int64_t)N * (HW / PV), C / 8);
+        const int chunks = bn_pick_chunks((int64_t)N * (HW / PV), C / 8);
         EAS_LAUNCH((bn_lif_fwd_sp_kernel<T_, HARD, DI, STRICT, PV>), EAS_CHAN_GRID(chunks, C / 8), dim3(EAS_BLOCK), 0, st, y,
                            mean, invstd, gamma, beta, v_in,
                            v_out, p, planes, res_planes, mean_out, N, C, HW, bcast, ox.y_ctot, out_groups, res_groups);
         EAS_CHECK_LAUNCH();
         return EAS_OK;
     }
-    const int chunks = pick_chunks((int64_t)N * (HW / VEC), C);
+    const int chunks = bn_pick_chunks((int64_t)N * (HW / EAS_VEC), C);
     EAS_LAUNCH((bn_lif_fwd_kernel<T_, HARD, DI, STRICT>), EAS_CHAN_GRID(chunks, C), dim3(EAS_BLOCK), 0, st, y, mean,
                        invstd, gamma, beta, v_in, v_out, p, spikes, mean_out, N, C, HW, bcast, fin, ox);
     EAS_CHECK_LAUNCH();
@@ -706,17 +622,17 @@ static inline bool bwd_form(const char* word) {
 // one block per channel where a channel fits the registers of a block (bn_lif_bwd_small_kernel): groups per thread, 0 = two passes
 static inline int bwd_one_pass_gpt(const BwdCall& c) {
     const int gpt = c.T <= 3 ? 3 : (c.T <= 5 ? 2 : 1);                // 8 * T floats per group in registers
-    const int64_t groups = (int64_t)c.N * (c.HW / VEC);
+    const int64_t groups = (int64_t)c.N * (c.HW / EAS_VEC);
     return (!bwd_form("two") && !c.bcast && c.C >= 64 && groups <= 512 * gpt) ? gpt : 0;       // (1024-thread blocks are capped at 128 registers: they spill)
 }
 
 template <int T_, bool HARD, bool DI, bool STRICT, class POL>
 int launch_bwd_t(const BwdCall& c) {
     const int N = c.N, C = c.C, HW = c.HW;
-    const int chunks = pick_chunks((int64_t)N * (HW / VEC), C);
+    const int chunks = bn_pick_chunks((int64_t)N * (HW / EAS_VEC), C);
     if (bwd_one_pass_gpt(c)) {
         constexpr int GPT = T_ <= 3 ? 3 : (T_ <= 5 ? 2 : 1);
-        const int64_t groups = (int64_t)N * (HW / VEC);
+        const int64_t groups = (int64_t)N * (HW / EAS_VEC);
 #define EAS_SMALL(NT_) EAS_LAUNCH((bn_lif_bwd_small_kernel<T_, HARD, DI, STRICT, NT_, GPT, POL>), dim3(C), dim3(NT_), 0, c.st, c.grad_s, c.grad_mean, c.y, \
                                    c.mean, c.invstd, c.gamma, c.beta, c.v_init, c.p, c.sg, c.alpha, c.batch_stats, c.ws, c.grad_y, c.grad_gamma,       \
                                    c.grad_beta, N, C, HW, c.gs_ctot, c.y_ctot, c.alpha_dev)
@@ -800,18 +716,18 @@ int bwd_select(const BwdCall& c) {
 
 extern "C" {
 
-int64_t eas_bn_workspace_doubles(int C) { return (int64_t)C * kMaxChunks * 4; }
+int64_t eas_bn_workspace_doubles(int C) { return (int64_t)C * EAS_BN_MAX_CHUNKS * 4; }
 
 // launches the partial-sum kernel; returns the number of chunks per channel (> 0) or a negative status
 static int stats_partial(const float* y, int TN, int C, int HW, double* workspace, int y_ctot, hipStream_t st) {
     const int Cy = y_ctot ? y_ctot : C;
     int chunks;
-    if (HW % VEC == 0 && (((uintptr_t)y) & 15) == 0) {
-        chunks = pick_chunks((int64_t)TN * (HW / VEC), C);
+    if (HW % EAS_VEC == 0 && (((uintptr_t)y) & 15) == 0) {
+        chunks = bn_pick_chunks((int64_t)TN * (HW / EAS_VEC), C);
         EAS_LAUNCH(bn_stats_partial, dim3(chunks, C), dim3(EAS_BLOCK), 0, st, y, TN, C, HW, workspace, Cy);
     } else {
         if (Cy != C) return EAS_ERR_UNSUPPORTED;
-        chunks = pick_chunks((int64_t)TN * HW, C);
+        chunks = bn_pick_chunks((int64_t)TN * HW, C);
         EAS_LAUNCH(bn_stats_partial_scalar, dim3(chunks, C), dim3(EAS_BLOCK), 0, st, y, TN, C, HW, workspace);
     }
     if (hipGetLastError() != hipSuccess) return EAS_ERR_LAUNCH;
@@ -827,28 +743,17 @@ int eas_bn_stats(const float* y, int TN, int C, int HW, int replicas, float eps,
     EAS_CLEAR_ERR();
     const int chunks = stats_partial(y, TN, C, HW, workspace, 0, st);
     if (chunks < 0) return chunks;
-    EAS_LAUNCH(bn_stats_finalize, dim3(C), dim3(EAS_WAVE), 0, st, workspace, chunks, (double)TN * HW, replicas, eps,
-                       momentum, mean, invstd, running_mean, running_var);
+    const BnFin fin{workspace, chunks, EAS_BN_MAX_CHUNKS, replicas, (double)TN * HW, eps, momentum, mean, invstd, running_mean, running_var};
+    EAS_LAUNCH(bn_stats_finalize, dim3(C), dim3(EAS_WAVE), 0, st, fin);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }
 
 int eas_bn_stats_partial(const float* y, int y_ctot, int TN, int C, int HW, double* workspace, eas_stream_t stream) {
-    if (!y || !workspace || TN < 1 || C < 1 || HW < 1 || (y_ctot != 0 && y_ctot < C)) return EAS_ERR_INVALID_ARG;
+    if (!y || !workspace || TN < 1 || C < 1 || HW < 1 || !bn_slice(y_ctot, C)) return EAS_ERR_INVALID_ARG;
     if (C > 65535) return EAS_ERR_UNSUPPORTED;
     EAS_CLEAR_ERR();
-    return stats_partial(y, TN, C, HW, workspace, y_ctot == C ? 0 : y_ctot, eas_s(stream));
-}
-
-static int fin_from(const EasBnPending* pend, float* mean, float* invstd, BnFin& fin) {
-    fin = BnFin{};
-    if (!pend || !pend->partial) return EAS_OK;
-    if (pend->chunks < 1 || pend->chunks > (pend->pitch ? pend->pitch : kMaxChunks) || pend->pitch < 0 || !(pend->count >= 1.0) || pend->replicas < 1) return EAS_ERR_INVALID_ARG;
-    if ((pend->running_mean == nullptr) != (pend->running_var == nullptr)) return EAS_ERR_INVALID_ARG;
-    fin.part = pend->partial; fin.nchunks = pend->chunks; fin.pitch = pend->pitch ? pend->pitch : kMaxChunks; fin.replicas = pend->replicas; fin.count = pend->count;
-    fin.eps = pend->eps; fin.momentum = pend->momentum; fin.mean_out = mean; fin.invstd_out = invstd;
-    fin.rmean = pend->running_mean; fin.rvar = pend->running_var;
-    return EAS_OK;
+    return stats_partial(y, TN, C, HW, workspace, y_ctot, eas_s(stream));
 }
 
 int eas_bn_lif_fwd_ex(const float* y, int y_ctot, float* mean, float* invstd, const float* gamma, const float* beta,
@@ -858,35 +763,35 @@ int eas_bn_lif_fwd_ex(const float* y, int y_ctot, float* mean, float* invstd, co
                       int residual_ctot, eas_stream_t stream) {
     if (!y || !mean || !invstd || !gamma || !beta || (!spikes && !spikes_planes) || (spikes && spikes_planes) || T < 1 || N < 1 || C < 1 || HW < 1)
         return EAS_ERR_INVALID_ARG;
-    if (HW % VEC != 0 || C > 65535 || T > 8) return EAS_ERR_UNSUPPORTED;
+    if (HW % EAS_VEC != 0 || C > 65535 || T > 8) return EAS_ERR_UNSUPPORTED;
     if (((uintptr_t)y | (uintptr_t)v_in | (uintptr_t)v_out | (uintptr_t)spikes | (uintptr_t)mean_out | (uintptr_t)residual |
          (uintptr_t)spikes_planes | (uintptr_t)residual_planes) & 15)
         return EAS_ERR_INVALID_ARG;
-    if ((out_ctot != 0 && out_ctot < C) || (y_ctot != 0 && (y_ctot < C || y_bcast))) return EAS_ERR_INVALID_ARG;
+    // (the broadcast test reads y_ctot as given, before bn_slice turns y_ctot == C into 0)
+    if ((y_ctot != 0 && y_bcast) || !bn_slice(out_ctot, C) || !bn_slice(y_ctot, C)) return EAS_ERR_INVALID_ARG;
     if (spikes_planes) {
         // planes are blocks of 8 channels: the layer's channels, its slice of a concatenation and a residual must be whole blocks
-        if (C % 8 != 0 || (out_ctot % 8) != 0 || residual || (residual_planes && (residual_ctot % 8 != 0 || (residual_ctot != 0 && residual_ctot < C))))
+        if (C % 8 != 0 || (out_ctot % 8) != 0 || residual || (residual_planes && (residual_ctot % 8 != 0 || !bn_slice(residual_ctot, C))))
             return EAS_ERR_UNSUPPORTED;
     } else if (residual_planes) {
         return EAS_ERR_UNSUPPORTED;
     }
     BnFin fin;
-    if (int rc = fin_from(pending, mean, invstd, fin)) return rc;
-    const BnLifOut ox{residual, out_ctot == C ? 0 : out_ctot, y_ctot == C ? 0 : y_ctot};
+    if (int rc = bn_fin_from(pending, mean, invstd, fin)) return rc;
+    const BnLifOut ox{residual, out_ctot, y_ctot};
     EasLifParams p{w_logit, k_const, v_th, v_reset, flags};
-    const bool hard = flags & EAS_LIF_HARD_RESET, di = flags & EAS_LIF_DECAY_INPUT, strict = flags & EAS_LIF_FIRE_STRICT;
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
     const int out_groups = (out_ctot ? out_ctot : C) / 8, res_groups = (residual_ctot ? residual_ctot : C) / 8;
-#define EAS_DISPATCH(H, D, S)                                                                                                          \
-    return launch_fwd<H, D, S>(T, y, mean, invstd, gamma, beta, v_in, v_out, p, spikes, mean_out, N, C, HW, y_bcast, fin, ox,           \
-                               (bf16x8*)spikes_planes, (const bf16x8*)residual_planes, out_groups, res_groups, st)
-    if (!hard && !di && !strict) EAS_DISPATCH(false, false, false);
-    if (hard && !di && !strict) EAS_DISPATCH(true, false, false);
-    if (!hard && di && !strict) EAS_DISPATCH(false, true, false);
-    if (hard && di && !strict) EAS_DISPATCH(true, true, false);
-    return EAS_ERR_UNSUPPORTED;  // strict '>' firing only exists in the sampler / in-repo LIFCell
-#undef EAS_DISPATCH
+    return eas_lif_dispatch(flags, [&](auto h, auto d, auto strict) {
+        if constexpr (decltype(strict)::value) {
+            return (int)EAS_ERR_UNSUPPORTED;      // strict '>' firing only exists in the sampler / in-repo LIFCell
+        } else {
+            return launch_fwd<decltype(h)::value, decltype(d)::value, false>(T, y, mean, invstd, gamma, beta, v_in, v_out, p, spikes, mean_out, N, C, HW,
+                                                                             y_bcast, fin, ox, (bf16x8*)spikes_planes,
+                                                                             (const bf16x8*)residual_planes, out_groups, res_groups, st);
+        }
+    });
 }
 
 int eas_bn_lif_fwd(const float* y, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -909,14 +814,13 @@ static int bn_lif_bwd_impl(const float* grad_s, int grad_s_ctot, const float* gr
     if (surrogate < EAS_SG_ATAN || surrogate > EAS_SG_PATAN) return EAS_ERR_INVALID_ARG;
     if (surrogate == EAS_SG_PATAN ? !alpha_dev : !(alpha > 0.f)) return EAS_ERR_INVALID_ARG;
     if (grad_w && !w_logit) return EAS_ERR_INVALID_ARG;
-    if (HW % VEC != 0 || C > 65535 || T > 8) return EAS_ERR_UNSUPPORTED;
+    if (HW % EAS_VEC != 0 || C > 65535 || T > 8) return EAS_ERR_UNSUPPORTED;
     if (((uintptr_t)y | (uintptr_t)grad_s | (uintptr_t)grad_mean | (uintptr_t)v_init | (uintptr_t)grad_y) & 15)
         return EAS_ERR_INVALID_ARG;
-    if ((grad_s_ctot != 0 && grad_s_ctot < C) || (y_ctot != 0 && (y_ctot < C || y_bcast))) return EAS_ERR_INVALID_ARG;
-    const int gs_ctot = grad_s_ctot == C ? 0 : grad_s_ctot;
-    const int yc = y_ctot == C ? 0 : y_ctot;
+    // (the broadcast test reads y_ctot as given, before bn_slice turns y_ctot == C into 0)
+    if ((y_ctot != 0 && y_bcast) || !bn_slice(grad_s_ctot, C) || !bn_slice(y_ctot, C)) return EAS_ERR_INVALID_ARG;
     const BwdCall call{grad_s, grad_mean, y, mean, invstd, gamma, beta, v_init, EasLifParams{w_logit, k_const, v_th, v_reset, flags}, surrogate, alpha,
-                       batch_stats, grad_y, grad_gamma, grad_beta, grad_w, workspace, T, N, C, HW, y_bcast, gs_ctot, yc, alpha_dev, grad_alpha,
+                       batch_stats, grad_y, grad_gamma, grad_beta, grad_w, workspace, T, N, C, HW, y_bcast, grad_s_ctot, y_ctot, alpha_dev, grad_alpha,
                        eas_s(stream)};
     EAS_CLEAR_ERR();
     return bwd_select(call);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/eas_hip.h"
 
 #define EAS_WAVE 64
@@ -92,6 +94,27 @@ __device__ __forceinline__ T eas_block_sum(T v, T* smem) {
     }
     __syncthreads();
     return r;
+}
+
+// One-pass block totals of NQ quantities over a block of NWV waves: wave sums in double, one LDS slot per wave and quantity, thread 0 adds
+// the waves 0..NWV-1 in order.  t[] is valid in thread 0 only; the caller publishes what the block needs and then synchronizes.
+template <int NWV, int NQ>
+__device__ __forceinline__ void eas_block_totals(const float (&v)[NQ], double (*red)[NWV], double (&t)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) t[q] = eas_wave_sum((double)v[q]);
+    if ((threadIdx.x & (EAS_WAVE - 1)) == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) red[q][threadIdx.x / EAS_WAVE] = t[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) t[q] = 0.0;
+        for (int w = 0; w < NWV; ++w) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) t[q] += red[q][w];
+        }
+    }
 }
 
 // ---- sums over the 32 lanes that share lane>>5 (the pixel columns of a 32x32 MFMA accumulator), DPP only (no LDS):
@@ -194,7 +217,30 @@ __device__ __forceinline__ void eas_conv_stats_store(const double* red, int wave
     *reinterpret_cast<double2*>(stats + ((int64_t)co * nb + block) * 2) = make_double2(s, q);
 }
 
-#define EAS_BN_MAX_CHUNKS 64   // chunk partials per channel in the BN workspaces (kMaxChunks of bn_lif.hip / bn_act.hip)
+// ------------------------------------------------------------------------------------------------ BN channel plan
+// The BatchNorm-fused kernels (bn_lif.hip, bn_act.hip) split a channel's float4 groups into chunks, one block each; a chunk leaves one
+// partial per channel in the workspaces, which the Python side sizes by eas_bn_workspace_doubles = C * EAS_BN_MAX_CHUNKS * 4.
+#define EAS_VEC 4              // floats per 16-byte access
+#define EAS_BN_MAX_CHUNKS 64   // chunk partials per channel in the BN workspaces: one wave adds them, lane i takes partial i
+
+static inline int bn_pick_chunks(int64_t groups_per_channel, int C) {
+    int64_t want = (groups_per_channel + EAS_BLOCK - 1) / EAS_BLOCK;  // one group per thread
+    int64_t cap = 8192 / (C > 0 ? C : 1);                                // keep the grid around <= 8k blocks
+    if (cap < 1) cap = 1;
+    if (cap > EAS_BN_MAX_CHUNKS) cap = EAS_BN_MAX_CHUNKS;
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    return (int)want;
+}
+
+// A channel-slice argument (0: dense, else the channel count of the wider tensor the C channels are a slice of): ctot == C is dense as well
+// and is normalised to 0; false: the tensor is narrower than the slice.  The argument is rewritten only when the call is reached: in a
+// chain of || a caller's later slices keep their given value after the first refusal (the call returns then), and a test that must see
+// the value AS GIVEN (a slice together with a broadcast frame is refused even for ctot == C) stands in front of the call.
+static inline bool bn_slice(int& ctot, int C) {
+    if (ctot == C) ctot = 0;
+    return ctot == 0 || ctot > C;
+}
 
 // ------------------------------------------------------------------------------------------------ fused finalize
 // Statistics finalize folded into the consumer: every block of channel c reduces that channel's chunk partials in the
@@ -212,6 +258,33 @@ struct BnFin {
     float* rmean;           // nullable
     float* rvar;
 };
+
+// The pending statistics of a forward call (EasBnPending: chunk partials that the consumer finalizes itself) as the kernels take them: the ONE
+// acceptance rule of eas_bn_lif_fwd_ex, eas_bn_silu_fwd_ex and eas_bn_silu_fwd_group.  No partials: fin.part = NULL, mean / invstd are inputs.
+static inline int bn_fin_from(const EasBnPending* pend, float* mean, float* invstd, BnFin& fin) {
+    fin = BnFin{};
+    if (!pend || !pend->partial) return EAS_OK;
+    const int pitch = pend->pitch ? pend->pitch : EAS_BN_MAX_CHUNKS;
+    if (pend->chunks < 1 || pend->chunks > pitch || pend->pitch < 0 || !(pend->count >= 1.0) || pend->replicas < 1) return EAS_ERR_INVALID_ARG;
+    if ((pend->running_mean == nullptr) != (pend->running_var == nullptr)) return EAS_ERR_INVALID_ARG;
+    fin = BnFin{pend->partial, pend->chunks, pitch, pend->replicas, pend->count, pend->eps, pend->momentum, mean, invstd, pend->running_mean,
+                pend->running_var};
+    return EAS_OK;
+}
+
+// Slots 0 and 1 of a channel's n <= EAS_WAVE partials (SLOTS doubles each, the channel's first at index `first`) added by the lanes of wave 0:
+// lane i takes partial i, then the wave tree -- the fixed order of every consumer.  Totals valid in lane 0.
+template <int SLOTS>
+__device__ __forceinline__ void bn_wave_partials(const double* __restrict__ part, int64_t first, int n, double& a, double& b) {
+    a = 0.0;
+    b = 0.0;
+    if ((int)threadIdx.x < n) {
+        a = part[(first + threadIdx.x) * SLOTS + 0];
+        b = part[(first + threadIdx.x) * SLOTS + 1];
+    }
+    a = eas_wave_sum(a);
+    b = eas_wave_sum(b);
+}
 
 // mean / invstd of channel c from its totals (sum, sum of squares); `publish` (one block per channel): write them for the backward
 // and update the running statistics.  Every thread may call it: same double arithmetic, same result.
@@ -263,10 +336,7 @@ __device__ __forceinline__ void bn_finalize_in_block(const BnFin& f, int c, floa
         if (threadIdx.x == 0) {
             s = 0.0; ss = 0.0;
             for (int w = 0; w < (int)(blockDim.x / EAS_WAVE); ++w) { s += fred[0][w]; ss += fred[1][w]; }
-            float m_, i_;
-            bn_from_totals(f, c, s, ss, publish, m_, i_);
-            st[0] = m_;
-            st[1] = i_;
+            bn_from_totals(f, c, s, ss, publish, st[0], st[1]);
         }
         __syncthreads();
         mu = st[0];
@@ -274,35 +344,46 @@ __device__ __forceinline__ void bn_finalize_in_block(const BnFin& f, int c, floa
         return;
     }
     if (threadIdx.x < EAS_WAVE) {
-        double s = 0.0, ss = 0.0;
-        if ((int)threadIdx.x < f.nchunks) {
-            s = f.part[((int64_t)c * f.pitch + threadIdx.x) * 2 + 0];
-            ss = f.part[((int64_t)c * f.pitch + threadIdx.x) * 2 + 1];
-        }
-        s = eas_wave_sum(s);
-        ss = eas_wave_sum(ss);
-        if (threadIdx.x == 0) {
-            const double m = s / f.count;
-            double var = ss / f.count - m * m;
-            if (var < 0.0) var = 0.0;
-            st[0] = (float)m;
-            st[1] = (float)(1.0 / sqrt(var + (double)f.eps));
-            if (publish) {                  // one block per channel
-                f.mean_out[c] = st[0];
-                f.invstd_out[c] = st[1];
-                if (f.rmean) {
-                    const double full = f.count * f.replicas;
-                    const double unbiased = full > 1.0 ? var * full / (full - 1.0) : var;
-                    f.rmean[c] = (float)((1.0 - f.momentum) * f.rmean[c] + f.momentum * m);
-                    f.rvar[c] = (float)((1.0 - f.momentum) * f.rvar[c] + f.momentum * unbiased);
-                }
-            }
-        }
+        double s, ss;
+        bn_wave_partials<2>(f.part, (int64_t)c * f.pitch, f.nchunks, s, ss);
+        if (threadIdx.x == 0) bn_from_totals(f, c, s, ss, publish, st[0], st[1]);      // publish: one block per channel
     }
     __syncthreads();
     mu = st[0];
     istd = st[1];
 }
+
+// ------------------------------------------------------------------------------------------------ BatchNorm backward
+// With dz = dL/dz (z = the BN output) and xhat = (y - mean) * invstd, the channel's totals s1 = sum dz and s2 = sum dz * xhat over `cnt`
+// values are grad_beta and grad_gamma, and grad_y = scale * (dz - s1 / cnt - xhat * s2 / cnt) (the means are 0 for running statistics).
+// The thread that holds the totals publishes them: the two means through bc[2] (LDS) to the block, the parameter gradients when `store`.
+__device__ __forceinline__ void bn_bwd_publish(double s1, double s2, double cnt, bool store, int c, float* __restrict__ grad_beta,
+                                               float* __restrict__ grad_gamma, float* bc) {
+    bc[0] = (float)(s1 / cnt);
+    bc[1] = (float)(s2 / cnt);
+    if (store) {
+        grad_beta[c] = (float)s1;
+        grad_gamma[c] = (float)s2;
+    }
+}
+
+// Prologue of an apply pass: the channel's chunk partials of the sum pass (PITCH doubles each, slots 0 / 1) added in the fixed order of
+// bn_wave_partials -- every block of the channel computes the same value -- and published; chunk 0 stores grad_beta / grad_gamma.
+template <int PITCH>
+__device__ __forceinline__ void bn_bwd_means(const double* __restrict__ part, int c, int nchunks, double cnt, int chunk, int batch_stats,
+                                             float* __restrict__ grad_beta, float* __restrict__ grad_gamma, float* bc, float& m1, float& m2) {
+    if (threadIdx.x < EAS_WAVE) {
+        double s1, s2;
+        bn_wave_partials<PITCH>(part, (int64_t)c * EAS_BN_MAX_CHUNKS, nchunks, s1, s2);
+        if (threadIdx.x == 0) bn_bwd_publish(s1, s2, cnt, chunk == 0, c, grad_beta, grad_gamma, bc);
+    }
+    __syncthreads();
+    m1 = batch_stats ? bc[0] : 0.f;
+    m2 = batch_stats ? bc[1] : 0.f;
+}
+
+__device__ __forceinline__ float bn_xhat(float y, float mu, float istd) { return (y - mu) * istd; }
+__device__ __forceinline__ float bn_bwd_apply(float scale, float dz, float xhat, float m1, float m2) { return scale * (dz - m1 - xhat * m2); }
 
 // ------------------------------------------------------------------------------------------------ channel grids
 // The BN kernels decompose as (channel, chunk of the channel's pixel groups).  Grid = (8, chunks, ceil(C / 8)), channel = blockIdx.z * 8 +
@@ -341,6 +422,15 @@ __device__ __forceinline__ float eas_lif_k(const EasLifParams& p) {
     return p.w_logit ? eas_sigmoidf(*p.w_logit) : p.k_const;
 }
 
+// Fire and reset: the spike s of the charged potential h and the potential after it.  (The backward of lif.hip keeps only h and recomputes
+// v_{t-1} from h_{t-1} with this.)
+template <bool HARD, bool STRICT>
+__device__ __forceinline__ float eas_lif_fire_reset(float h, float v_th, float v_reset, float& s) {
+    const float u = h - v_th;
+    s = STRICT ? (u > 0.0f ? 1.0f : 0.0f) : (u >= 0.0f ? 1.0f : 0.0f);
+    return HARD ? (1.0f - s) * h + s * v_reset : h - s * v_th;
+}
+
 // One LIF step, arithmetic ordered like the PyTorch expression it replaces
 // (-ffp-contract=off: every * and + rounds separately, as ATen elementwise kernels do).
 template <bool HARD, bool DI, bool STRICT>
@@ -351,9 +441,7 @@ __device__ __forceinline__ void eas_lif_step(float& v, float x, float k, float o
     } else {
         h = (HARD && v_reset != 0.0f) ? (v - (v - v_reset) * k) + x : v * omk + x;
     }
-    const float u = h - v_th;
-    s = STRICT ? (u > 0.0f ? 1.0f : 0.0f) : (u >= 0.0f ? 1.0f : 0.0f);
-    v = HARD ? (1.0f - s) * h + s * v_reset : h - s * v_th;
+    v = eas_lif_fire_reset<HARD, STRICT>(h, v_th, v_reset, s);
 }
 
 // dL/dh of one step and the pieces the caller needs.
@@ -390,4 +478,40 @@ __device__ __forceinline__ float eas_lif_step_bwd(float gs, float& gv, float h, 
     }
     gv = dh * omk;
     return dh;
+}
+
+// Final stage of the two scalar parameter gradients of a (P)LIF layer, by ONE block of EAS_BLOCK threads: the n partial sums of dL/dk
+// (term_w(i)) and of dL/d|alpha| (term_a(i)) are added in a fixed order (eas_block_sum, `red`: EAS_BLOCK / EAS_WAVE doubles) and multiplied
+// by dk/dw = k (1 - k) of k = sigmoid(w), resp. d|alpha|/dalpha = sign(alpha) (0 at 0, like torch.abs).  grad_w / grad_alpha NULL: not wanted.
+template <class FW, class FA>
+__device__ __forceinline__ void eas_lif_scalar_grads(int n, FW term_w, FA term_a, const float* __restrict__ w_logit,
+                                                     const float* __restrict__ alpha_dev, float* __restrict__ grad_w,
+                                                     float* __restrict__ grad_alpha, double* red) {
+    if (grad_w) {
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)term_w(i);
+        const double tot = eas_block_sum<double, EAS_BLOCK / EAS_WAVE>(acc, red);
+        if (threadIdx.x == 0) {
+            const float k = eas_sigmoidf(*w_logit);
+            *grad_w = (float)tot * (k * (1.0f - k));
+        }
+    }
+    if (grad_alpha) {
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)term_a(i);
+        const double tot = eas_block_sum<double, EAS_BLOCK / EAS_WAVE>(acc, red);
+        if (threadIdx.x == 0) {
+            const float a = *alpha_dev;
+            *grad_alpha = (float)tot * (a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f));
+        }
+    }
+}
+
+// The (reset, decay, firing) form of a LIF launch from its flags: f(hard, decay_input, strict) with three std::bool_constant arguments,
+// for the kernels that take the form as template constants.
+template <class F>
+static inline int eas_lif_dispatch(int flags, F&& f) {
+    auto strict = [&](auto h, auto d) { return (flags & EAS_LIF_FIRE_STRICT) ? f(h, d, std::true_type{}) : f(h, d, std::false_type{}); };
+    auto decay = [&](auto h) { return (flags & EAS_LIF_DECAY_INPUT) ? strict(h, std::true_type{}) : strict(h, std::false_type{}); };
+    return (flags & EAS_LIF_HARD_RESET) ? decay(std::true_type{}) : decay(std::false_type{});
 }

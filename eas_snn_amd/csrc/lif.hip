@@ -3,12 +3,44 @@
 // walks the T time steps with the membrane potential in registers, so each [T][M] tensor is
 // touched exactly once: fwd reads x (4 B) and writes s (4 B) [+ h (4 B) when training];
 // bwd reads grad_s, h (8 B) and writes grad_x (4 B) per neuron-step.
+//
+// The forward states its per-neuron work ONCE, for W neurons of a thread (Cols<W>): lif_walk runs it with W = 4 over the float4 columns
+// and with W = 1 over what is left; the backward does so for its float4 columns.  Its scalar columns and the time mean keep loops of
+// their own, where the shared form measured slower (notes at both).  The (reset, decay, firing) form reaches the kernels through eas_lif_dispatch (eas_common.h), the
+// fire-and-reset rule and the scalar parameter gradients' final stage are the ones of eas_common.h as well.
 #include "eas_common.h"
 
 namespace {
 
-constexpr int VEC = 4;
+// W consecutive floats of a row, W = 4: one 16-byte access
+template <int W>
+struct alignas(4 * W) Cols {
+    float e[W];
+};
+template <int W>
+__device__ __forceinline__ Cols<W> ld(const float* p) { return *reinterpret_cast<const Cols<W>*>(p); }
+template <int W>
+__device__ __forceinline__ void st(float* p, const Cols<W>& v) { *reinterpret_cast<Cols<W>*>(p) = v; }
 
+// The columns of a [T][M] tensor, grid-strided: body(width, j) for the W = width() columns from j on.  float4 columns where every row is
+// 16-byte aligned (M % 4 == 0, or a single row), scalar columns for the remainder (M % 4 columns, or all of them).
+// lif_walk_vec: the float4 columns only; returns the first column that is left for a scalar walk.
+template <class F>
+__device__ __forceinline__ int64_t lif_walk_vec(int T, int64_t M, F&& body) {
+    const int64_t nvec = (M % EAS_VEC == 0 || T == 1) ? M / EAS_VEC : 0;
+    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = first; i < nvec; i += stride) body(std::integral_constant<int, EAS_VEC>{}, i * EAS_VEC);
+    return nvec * EAS_VEC;
+}
+template <class F>
+__device__ __forceinline__ void lif_walk(int T, int64_t M, F&& body) {
+    const int64_t rest = lif_walk_vec(T, M, body);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = rest + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) body(std::integral_constant<int, 1>{}, j);
+}
+static inline int lif_grid(int64_t M) { return eas_grid_1d(M % EAS_VEC == 0 ? M / EAS_VEC : M); }
+
+// T_ = 1..8: the time steps as a template constant (all loads of x issued before the first step); 0: any T
 template <int T_, bool HARD, bool DI, bool STRICT>
 __global__ __launch_bounds__(EAS_BLOCK) void lif_fwd_kernel(const float* __restrict__ x, const float* v_in, float* v_out,
                                                             EasLifParams p, float* __restrict__ spikes,
@@ -17,69 +49,41 @@ __global__ __launch_bounds__(EAS_BLOCK) void lif_fwd_kernel(const float* __restr
     const float k = eas_lif_k(p);
     const float omk = 1.0f - k;
     const int T = T_ > 0 ? T_ : T_rt;
-    const int64_t nvec = (M % VEC == 0 || T == 1) ? M / VEC : 0;   // rows of [T][M] must be 16-B aligned for float4
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-        const float vr0 = HARD ? p.v_reset : 0.0f;
-        float4 v = v_in ? reinterpret_cast<const float4*>(v_in)[i] : make_float4(vr0, vr0, vr0, vr0);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (T_ > 0) {
-            float4 xs[T_ > 0 ? T_ : 1];
+    lif_walk(T, M, [&](auto width, int64_t j) {
+        constexpr int W = decltype(width)::value;
+        Cols<W> v, acc;
+        if (v_in) v = ld<W>(v_in + j);
 #pragma unroll
-            for (int t = 0; t < T_; ++t) xs[t] = reinterpret_cast<const float4*>(x + (int64_t)t * M)[i];
+        for (int e = 0; e < W; ++e) {
+            if (!v_in) v.e[e] = HARD ? p.v_reset : 0.0f;
+            acc.e[e] = 0.f;
+        }
+        auto step = [&](int t, const Cols<W>& xt) {
+            Cols<W> h, s;
 #pragma unroll
-            for (int t = 0; t < T_; ++t) {
-                float4 h, s;
-                eas_lif_step<HARD, DI, STRICT>(v.x, xs[t].x, k, omk, p.v_th, p.v_reset, h.x, s.x);
-                eas_lif_step<HARD, DI, STRICT>(v.y, xs[t].y, k, omk, p.v_th, p.v_reset, h.y, s.y);
-                eas_lif_step<HARD, DI, STRICT>(v.z, xs[t].z, k, omk, p.v_th, p.v_reset, h.z, s.z);
-                eas_lif_step<HARD, DI, STRICT>(v.w, xs[t].w, k, omk, p.v_th, p.v_reset, h.w, s.w);
-                reinterpret_cast<float4*>(spikes + (int64_t)t * M)[i] = s;
-                if (h_save) reinterpret_cast<float4*>(h_save + (int64_t)t * M)[i] = h;
-                acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
+            for (int e = 0; e < W; ++e) {
+                eas_lif_step<HARD, DI, STRICT>(v.e[e], xt.e[e], k, omk, p.v_th, p.v_reset, h.e[e], s.e[e]);
+                acc.e[e] += s.e[e];
             }
+            st<W>(spikes + (int64_t)t * M + j, s);
+            if (h_save) st<W>(h_save + (int64_t)t * M + j, h);
+        };
+        if constexpr (T_ > 0 && W > 1) {
+            Cols<W> xs[T_ > 0 ? T_ : 1];
+#pragma unroll
+            for (int t = 0; t < T_; ++t) xs[t] = ld<W>(x + (int64_t)t * M + j);
+#pragma unroll
+            for (int t = 0; t < T_; ++t) step(t, xs[t]);
         } else {
-            for (int t = 0; t < T; ++t) {
-                const float4 xt = reinterpret_cast<const float4*>(x + (int64_t)t * M)[i];
-                float4 h, s;
-                eas_lif_step<HARD, DI, STRICT>(v.x, xt.x, k, omk, p.v_th, p.v_reset, h.x, s.x);
-                eas_lif_step<HARD, DI, STRICT>(v.y, xt.y, k, omk, p.v_th, p.v_reset, h.y, s.y);
-                eas_lif_step<HARD, DI, STRICT>(v.z, xt.z, k, omk, p.v_th, p.v_reset, h.z, s.z);
-                eas_lif_step<HARD, DI, STRICT>(v.w, xt.w, k, omk, p.v_th, p.v_reset, h.w, s.w);
-                reinterpret_cast<float4*>(spikes + (int64_t)t * M)[i] = s;
-                if (h_save) reinterpret_cast<float4*>(h_save + (int64_t)t * M)[i] = h;
-                acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
-            }
+            for (int t = 0; t < T; ++t) step(t, ld<W>(x + (int64_t)t * M + j));
         }
-        if (v_out) reinterpret_cast<float4*>(v_out)[i] = v;
+        if (v_out) st<W>(v_out + j, v);
         if (mean_out) {
-            const float Tf = (float)T;   // sum / T, like ATen's mean
-            reinterpret_cast<float4*>(mean_out)[i] = make_float4(acc.x / Tf, acc.y / Tf, acc.z / Tf, acc.w / Tf);
+#pragma unroll
+            for (int e = 0; e < W; ++e) acc.e[e] /= (float)T;   // sum / T, like ATen's mean
+            st<W>(mean_out + j, acc);
         }
-    }
-    // scalar remainder (M % 4 elements, or everything when rows are unaligned)
-    {
-        for (int64_t j = nvec * VEC + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-            float v = v_in ? v_in[j] : (HARD ? p.v_reset : 0.0f), acc = 0.f;
-            for (int t = 0; t < T; ++t) {
-                float h, s;
-                eas_lif_step<HARD, DI, STRICT>(v, x[(int64_t)t * M + j], k, omk, p.v_th, p.v_reset, h, s);
-                spikes[(int64_t)t * M + j] = s;
-                if (h_save) h_save[(int64_t)t * M + j] = h;
-                acc += s;
-            }
-            if (v_out) v_out[j] = v;
-            if (mean_out) mean_out[j] = acc / (float)T;
-        }
-    }
-}
-
-// v_{t-1} recomputed from h_{t-1} (spike = H(h - v_th)), so only h is stored.
-template <bool HARD, bool STRICT>
-__device__ __forceinline__ float v_after(float h, float v_th, float v_reset) {
-    const float u = h - v_th;
-    const float s = STRICT ? (u > 0.0f ? 1.0f : 0.0f) : (u >= 0.0f ? 1.0f : 0.0f);
-    return HARD ? (1.0f - s) * h + s * v_reset : h - s * v_th;
+    });
 }
 
 template <int T_, bool HARD, bool DI, bool STRICT>
@@ -93,76 +97,77 @@ __global__ __launch_bounds__(EAS_BLOCK) void lif_bwd_kernel(const float* __restr
                                                             float* __restrict__ partial_a, int T_rt, int64_t M) {
     __shared__ float red[EAS_BLOCK / EAS_WAVE];
     if (alpha_dev) alpha = fabsf(*alpha_dev);    // learnable slope (EAS_SG_PATAN)
-    float da = 0.f;
     const float k = eas_lif_k(p);
     const float omk = 1.0f - k;
     const bool detach = (p.flags & EAS_LIF_DETACH_RESET) != 0;
     const int T = T_ > 0 ? T_ : T_rt;
     const float invT = 1.0f / (float)T;
-    const int64_t nvec = (M % VEC == 0 || T == 1) ? M / VEC : 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float dk = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-        float gv[VEC] = {0.f, 0.f, 0.f, 0.f};
-        float gm[VEC] = {0.f, 0.f, 0.f, 0.f};
-        if (grad_mean) {
-            const float4 g = reinterpret_cast<const float4*>(grad_mean)[i];
-            gm[0] = g.x * invT; gm[1] = g.y * invT; gm[2] = g.z * invT; gm[3] = g.w * invT;
-        }
-        float4 hn = reinterpret_cast<const float4*>(h_save + (int64_t)(T - 1) * M)[i];
-        for (int t = T - 1; t >= 0; --t) {
-            const float4 hc = hn;
-            float vp[VEC];
-            if (t > 0) {
-                hn = reinterpret_cast<const float4*>(h_save + (int64_t)(t - 1) * M)[i];
-                vp[0] = v_after<HARD, STRICT>(hn.x, p.v_th, p.v_reset);
-                vp[1] = v_after<HARD, STRICT>(hn.y, p.v_th, p.v_reset);
-                vp[2] = v_after<HARD, STRICT>(hn.z, p.v_th, p.v_reset);
-                vp[3] = v_after<HARD, STRICT>(hn.w, p.v_th, p.v_reset);
-            } else if (v_init) {
-                const float4 v0 = reinterpret_cast<const float4*>(v_init)[i];
-                vp[0] = v0.x; vp[1] = v0.y; vp[2] = v0.z; vp[3] = v0.w;
-            } else {
-                vp[0] = vp[1] = vp[2] = vp[3] = HARD ? p.v_reset : 0.f;
-            }
-            float gs[VEC] = {gm[0], gm[1], gm[2], gm[3]};
-            if (grad_s) {
-                const float4 g = reinterpret_cast<const float4*>(grad_s + (int64_t)t * M)[i];
-                gs[0] += g.x; gs[1] += g.y; gs[2] += g.z; gs[3] += g.w;
-            }
-            float xv[VEC] = {0.f, 0.f, 0.f, 0.f};
-            if (DI && x) {
-                const float4 xt = reinterpret_cast<const float4*>(x + (int64_t)t * M)[i];
-                xv[0] = xt.x; xv[1] = xt.y; xv[2] = xt.z; xv[3] = xt.w;
-            }
-            const float hh[VEC] = {hc.x, hc.y, hc.z, hc.w};
-            float gx[VEC];
+    float dk = 0.f, da = 0.f;
+    const int64_t rest = lif_walk_vec(T, M, [&](auto width, int64_t j) {
+        constexpr int W = decltype(width)::value;
+        Cols<W> gv, gm;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                float dkt;
-                eas_lif_step_bwd<HARD, DI, STRICT>(gs[e], gv[e], hh[e], vp[e], xv[e], k, omk, p.v_th, p.v_reset,
-                                                   detach, sg_id, alpha, dkt, gx[e], da);
-                dk += dkt;
-            }
-            reinterpret_cast<float4*>(grad_x + (int64_t)t * M)[i] = make_float4(gx[0], gx[1], gx[2], gx[3]);
+        for (int e = 0; e < W; ++e) gv.e[e] = gm.e[e] = 0.f;
+        if (grad_mean) {
+            gm = ld<W>(grad_mean + j);
+#pragma unroll
+            for (int e = 0; e < W; ++e) gm.e[e] *= invT;
         }
-    }
-    {
-        for (int64_t j = nvec * VEC + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-            float gv = 0.f;
-            const float gm = grad_mean ? grad_mean[j] * invT : 0.f;
-            for (int t = T - 1; t >= 0; --t) {
-                const float h = h_save[(int64_t)t * M + j];
-                const float vp = t > 0 ? v_after<HARD, STRICT>(h_save[(int64_t)(t - 1) * M + j], p.v_th, p.v_reset)
-                                       : (v_init ? v_init[j] : (HARD ? p.v_reset : 0.f));
-                const float gs = gm + (grad_s ? grad_s[(int64_t)t * M + j] : 0.f);
-                const float xv = (DI && x) ? x[(int64_t)t * M + j] : 0.f;
-                float dkt, gx;
-                eas_lif_step_bwd<HARD, DI, STRICT>(gs, gv, h, vp, xv, k, omk, p.v_th, p.v_reset, detach, sg_id,
-                                                   alpha, dkt, gx, da);
-                dk += dkt;
-                grad_x[(int64_t)t * M + j] = gx;
+        Cols<W> hn = ld<W>(h_save + (int64_t)(T - 1) * M + j);
+        for (int t = T - 1; t >= 0; --t) {
+            const Cols<W> hc = hn;
+            // v_{t-1} recomputed from h_{t-1}, so only h is stored
+            Cols<W> vp, gs = gm, xv, gx;
+            if (t > 0) {
+                hn = ld<W>(h_save + (int64_t)(t - 1) * M + j);
+#pragma unroll
+                for (int e = 0; e < W; ++e) {
+                    float s;
+                    vp.e[e] = eas_lif_fire_reset<HARD, STRICT>(hn.e[e], p.v_th, p.v_reset, s);
+                }
+            } else if (v_init) {
+                vp = ld<W>(v_init + j);
+            } else {
+#pragma unroll
+                for (int e = 0; e < W; ++e) vp.e[e] = HARD ? p.v_reset : 0.f;
             }
+            if (grad_s) {
+                const Cols<W> g = ld<W>(grad_s + (int64_t)t * M + j);
+#pragma unroll
+                for (int e = 0; e < W; ++e) gs.e[e] += g.e[e];
+            }
+            if (DI && x) {
+                xv = ld<W>(x + (int64_t)t * M + j);
+            } else {
+#pragma unroll
+                for (int e = 0; e < W; ++e) xv.e[e] = 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                float dkt;
+                eas_lif_step_bwd<HARD, DI, STRICT>(gs.e[e], gv.e[e], hc.e[e], vp.e[e], xv.e[e], k, omk, p.v_th, p.v_reset, detach, sg_id,
+                                                   alpha, dkt, gx.e[e], da);
+                dk += dkt;
+            }
+            st<W>(grad_x + (int64_t)t * M + j, gx);
+        }
+    });
+    // The scalar columns keep a loop of their own: the body above instantiated for one column (h_{t-1} carried or read again) measured
+    // 3.5 % slower on rows that are not 16-byte aligned than this form, which reads h_t and h_{t-1} in every step
+    // (profiles/bn_family_one_rule_ab.txt).  Same arithmetic per neuron-step.
+    for (int64_t j = rest + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += (int64_t)gridDim.x * blockDim.x) {
+        float gv = 0.f, s_;
+        const float gm = grad_mean ? grad_mean[j] * invT : 0.f;
+        for (int t = T - 1; t >= 0; --t) {
+            const float h = h_save[(int64_t)t * M + j];
+            const float vp = t > 0 ? eas_lif_fire_reset<HARD, STRICT>(h_save[(int64_t)(t - 1) * M + j], p.v_th, p.v_reset, s_)
+                                   : (v_init ? v_init[j] : (HARD ? p.v_reset : 0.f));
+            const float gs = gm + (grad_s ? grad_s[(int64_t)t * M + j] : 0.f);
+            const float xv = (DI && x) ? x[(int64_t)t * M + j] : 0.f;
+            float dkt, gx;
+            eas_lif_step_bwd<HARD, DI, STRICT>(gs, gv, h, vp, xv, k, omk, p.v_th, p.v_reset, detach, sg_id, alpha, dkt, gx, da);
+            dk += dkt;
+            grad_x[(int64_t)t * M + j] = gx;
         }
     }
     if (partial) {
@@ -175,9 +180,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void lif_bwd_kernel(const float* __restr
     }
 }
 
-// final stage of the grad_w reduction: sum the per-block partials in a fixed order (deterministic)
-// and apply dk/dw = k (1 - k).
-// and, for the learnable surrogate slope, d|alpha|/dalpha = sign(alpha) (0 at 0, like torch.abs).
+// final stage of the grad_w / grad_alpha reduction: the per-block partials in a fixed order (deterministic), eas_lif_scalar_grads
 __global__ __launch_bounds__(EAS_BLOCK) void lif_gradw_finalize(const float* __restrict__ partial, int n,
                                                                 const float* __restrict__ w_logit,
                                                                 float* __restrict__ grad_w,
@@ -185,29 +188,14 @@ __global__ __launch_bounds__(EAS_BLOCK) void lif_gradw_finalize(const float* __r
                                                                 const float* __restrict__ alpha_dev,
                                                                 float* __restrict__ grad_alpha) {
     __shared__ double red[EAS_BLOCK / EAS_WAVE];
-    if (grad_w) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)partial[i];
-        const double tot = eas_block_sum<double, EAS_BLOCK / EAS_WAVE>(acc, red);
-        if (threadIdx.x == 0) {
-            const float k = eas_sigmoidf(*w_logit);
-            *grad_w = (float)tot * (k * (1.0f - k));
-        }
-    }
-    if (grad_alpha) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)partial_a[i];
-        const double tot = eas_block_sum<double, EAS_BLOCK / EAS_WAVE>(acc, red);
-        if (threadIdx.x == 0) {
-            const float a = *alpha_dev;
-            *grad_alpha = (float)tot * (a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f));
-        }
-    }
+    eas_lif_scalar_grads(n, [&](int i) { return partial[i]; }, [&](int i) { return partial_a[i]; }, w_logit, alpha_dev, grad_w, grad_alpha, red);
 }
 
+// (two loops written out: the shared walk with its 64-bit column index costs this kernel, which has nothing but its loads, 4 registers
+// and measured 0.2 to 0.5 us slower per call -- profiles/bn_family_one_rule_ab.txt)
 __global__ __launch_bounds__(EAS_BLOCK) void time_mean_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                               int T, int64_t M) {
-    const int64_t nvec = (M % VEC == 0 || T == 1) ? M / VEC : 0;
+    const int64_t nvec = (M % EAS_VEC == 0 || T == 1) ? M / EAS_VEC : 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const float Tf = (float)T;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -219,7 +207,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_mean_kernel(const float* __res
         reinterpret_cast<float4*>(out)[i] = make_float4(a.x / Tf, a.y / Tf, a.z / Tf, a.w / Tf);
     }
     {
-        for (int64_t j = nvec * VEC + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+        for (int64_t j = nvec * EAS_VEC + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
             float a = 0.f;
             for (int t = 0; t < T; ++t) a += x[(int64_t)t * M + j];
             out[j] = a / Tf;
@@ -232,19 +220,12 @@ constexpr int kReduceBlocks = 2048;
 template <bool HARD, bool DI, bool STRICT>
 int launch_fwd(const float* x, const float* v_in, float* v_out, EasLifParams p, float* spikes, float* h_save, float* mean_out, int T,
                int64_t M, hipStream_t st) {
-    const int grid = eas_grid_1d(M % VEC == 0 ? M / VEC : M);
-#define EAS_CASE(TT)                                                                                              \
-    case TT:                                                                                                      \
-        EAS_LAUNCH((lif_fwd_kernel<TT, HARD, DI, STRICT>), dim3(grid), dim3(EAS_BLOCK), 0, st, x, v_in, v_out, \
-                           p, spikes, h_save, mean_out, T, M);                                                       \
-        break;
-    switch (T) {
-        EAS_CASE(1) EAS_CASE(2) EAS_CASE(3) EAS_CASE(4) EAS_CASE(5) EAS_CASE(6) EAS_CASE(7) EAS_CASE(8)
-        default:
-            EAS_LAUNCH((lif_fwd_kernel<0, HARD, DI, STRICT>), dim3(grid), dim3(EAS_BLOCK), 0, st, x, v_in, v_out, p,
-                               spikes, h_save, mean_out, T, M);
-    }
-#undef EAS_CASE
+    // instance T for T = 1..8, instance 0 (runtime T) above
+    static constexpr decltype(&lif_fwd_kernel<0, HARD, DI, STRICT>) kern[9] = {
+        lif_fwd_kernel<0, HARD, DI, STRICT>, lif_fwd_kernel<1, HARD, DI, STRICT>, lif_fwd_kernel<2, HARD, DI, STRICT>,
+        lif_fwd_kernel<3, HARD, DI, STRICT>, lif_fwd_kernel<4, HARD, DI, STRICT>, lif_fwd_kernel<5, HARD, DI, STRICT>,
+        lif_fwd_kernel<6, HARD, DI, STRICT>, lif_fwd_kernel<7, HARD, DI, STRICT>, lif_fwd_kernel<8, HARD, DI, STRICT>};
+    EAS_LAUNCH(kern[T <= 8 ? T : 0], dim3(lif_grid(M)), dim3(EAS_BLOCK), 0, st, x, v_in, v_out, p, spikes, h_save, mean_out, T, M);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }
@@ -253,7 +234,7 @@ template <bool HARD, bool DI, bool STRICT>
 int launch_bwd(const float* grad_s, const float* grad_mean, const float* h_save, const float* v_init, const float* x,
                EasLifParams p, int sg, float alpha, const float* alpha_dev, float* grad_alpha, float* grad_x, float* grad_w,
                float* workspace, int T, int64_t M, hipStream_t st) {
-    int grid = eas_grid_1d(M % VEC == 0 ? M / VEC : M);
+    int grid = lif_grid(M);
     if (grid > kReduceBlocks) grid = kReduceBlocks;
     float* partial = grad_w ? workspace : nullptr;
     float* partial_a = grad_alpha ? workspace + kReduceBlocks : nullptr;
@@ -281,19 +262,11 @@ int eas_lif_fwd(const float* x, const float* v_in, float* v_out, const float* w_
     if (((uintptr_t)x | (uintptr_t)v_in | (uintptr_t)v_out | (uintptr_t)spikes | (uintptr_t)h_save | (uintptr_t)mean_out) & 15)
         return EAS_ERR_INVALID_ARG;
     EasLifParams p{w_logit, k_const, v_th, v_reset, flags};
-    const bool hard = flags & EAS_LIF_HARD_RESET, di = flags & EAS_LIF_DECAY_INPUT, strict = flags & EAS_LIF_FIRE_STRICT;
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-#define EAS_DISPATCH(H, D, S) return launch_fwd<H, D, S>(x, v_in, v_out, p, spikes, h_save, mean_out, T, M, st)
-    if (!hard && !di && !strict) EAS_DISPATCH(false, false, false);
-    if (!hard && !di && strict) EAS_DISPATCH(false, false, true);
-    if (!hard && di && !strict) EAS_DISPATCH(false, true, false);
-    if (!hard && di && strict) EAS_DISPATCH(false, true, true);
-    if (hard && !di && !strict) EAS_DISPATCH(true, false, false);
-    if (hard && !di && strict) EAS_DISPATCH(true, false, true);
-    if (hard && di && !strict) EAS_DISPATCH(true, true, false);
-    EAS_DISPATCH(true, true, true);
-#undef EAS_DISPATCH
+    return eas_lif_dispatch(flags, [&](auto h, auto d, auto s) {
+        return launch_fwd<decltype(h)::value, decltype(d)::value, decltype(s)::value>(x, v_in, v_out, p, spikes, h_save, mean_out, T, M, st);
+    });
 }
 
 static int lif_bwd_impl(const float* grad_s, const float* grad_mean, const float* h_save, const float* v_init,
@@ -308,22 +281,14 @@ static int lif_bwd_impl(const float* grad_s, const float* grad_mean, const float
     if (((uintptr_t)grad_s | (uintptr_t)grad_mean | (uintptr_t)h_save | (uintptr_t)v_init | (uintptr_t)x |
          (uintptr_t)grad_x) & 15)
         return EAS_ERR_INVALID_ARG;
-    const bool hard = flags & EAS_LIF_HARD_RESET, di = flags & EAS_LIF_DECAY_INPUT, strict = flags & EAS_LIF_FIRE_STRICT;
-    if (di && w_logit && grad_w && !x) return EAS_ERR_INVALID_ARG;
+    if ((flags & EAS_LIF_DECAY_INPUT) && w_logit && grad_w && !x) return EAS_ERR_INVALID_ARG;
     EasLifParams p{w_logit, k_const, v_th, v_reset, flags};
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-#define EAS_DISPATCH(H, D, S) \
-    return launch_bwd<H, D, S>(grad_s, grad_mean, h_save, v_init, x, p, surrogate, alpha, alpha_dev, grad_alpha, grad_x, grad_w, workspace, T, M, st)
-    if (!hard && !di && !strict) EAS_DISPATCH(false, false, false);
-    if (!hard && !di && strict) EAS_DISPATCH(false, false, true);
-    if (!hard && di && !strict) EAS_DISPATCH(false, true, false);
-    if (!hard && di && strict) EAS_DISPATCH(false, true, true);
-    if (hard && !di && !strict) EAS_DISPATCH(true, false, false);
-    if (hard && !di && strict) EAS_DISPATCH(true, false, true);
-    if (hard && di && !strict) EAS_DISPATCH(true, true, false);
-    EAS_DISPATCH(true, true, true);
-#undef EAS_DISPATCH
+    return eas_lif_dispatch(flags, [&](auto h, auto d, auto s) {
+        return launch_bwd<decltype(h)::value, decltype(d)::value, decltype(s)::value>(grad_s, grad_mean, h_save, v_init, x, p, surrogate, alpha, alpha_dev, grad_alpha, grad_x, grad_w,
+                                         workspace, T, M, st);
+    });
 }
 
 int eas_lif_bwd(const float* grad_s, const float* grad_mean, const float* h_save, const float* v_init,
@@ -348,7 +313,7 @@ int eas_time_mean(const float* x, float* out, int T, int64_t M, eas_stream_t str
     if (M == 0) return EAS_OK;
     if (((uintptr_t)x | (uintptr_t)out) & 15) return EAS_ERR_INVALID_ARG;
     EAS_CLEAR_ERR();
-    EAS_LAUNCH(time_mean_kernel, dim3(eas_grid_1d(M % VEC == 0 ? M / VEC : M)), dim3(EAS_BLOCK), 0, eas_s(stream), x, out, T, M);
+    EAS_LAUNCH(time_mean_kernel, dim3(lif_grid(M)), dim3(EAS_BLOCK), 0, eas_s(stream), x, out, T, M);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -150,3 +150,59 @@ def test_bn_silu_single_pair_and_group_are_bit_identical(dev):
     assert all(float(ref[k].abs().max()) > 0 for k in ref), 'a compared quantity is all zero'
     for form, cat in (('pair', False), ('single', True), ('pair', True), ('group', False)):
         _assert_same(ref, run(form, cat), f'BN+SiLU {form} cat={cat}')
+
+
+def test_bn_pending_statistics_refused_alike(dev):
+    """The three forward entry points that finalize pending statistics themselves (``EasBnPending``: eas_bn_lif_fwd_ex, eas_bn_silu_fwd_ex,
+    eas_bn_silu_fwd_group) accept and refuse the same structs: each invalid one is EAS_ERR_INVALID_ARG from all three without a launch,
+    the valid one runs in all three.  Through the C ABI (the operator layer never builds an invalid struct)."""
+    import ctypes
+    from eas_snn_amd import _lib
+    L, st = _lib.lib(), _lib.stream()
+    Tn, Nn, Cn, HW = 2, 2, 8, 24
+    y = torch.randn(Tn, Nn, Cn, HW, device=dev)
+    gamma, beta = torch.rand(Cn, device=dev) + 0.5, torch.randn(Cn, device=dev)
+    mean, invstd = torch.empty(Cn, device=dev), torch.empty(Cn, device=dev)
+    rmean, rvar = torch.zeros(Cn, device=dev), torch.ones(Cn, device=dev)
+    out = torch.empty_like(y)
+    stats = {}                      # images -> (workspace, chunks) of the statistics pass: T * N images for the neuron layer, N for SiLU
+    for tn in (Tn * Nn, Nn):
+        ws = torch.empty(L.eas_bn_workspace_doubles(Cn), dtype=torch.float64, device=dev)
+        stats[tn] = ws, L.eas_bn_stats_partial(y.data_ptr(), 0, tn, Cn, HW, ws.data_ptr(), st)
+        assert stats[tn][1] >= 1
+
+    def pending(tn, **change):
+        f = dict(partial=stats[tn][0].data_ptr(), chunks=stats[tn][1], replicas=1, count=float(tn * HW), eps=EPS, momentum=MOMENTUM,
+                 running_mean=rmean.data_ptr(), running_var=rvar.data_ptr(), pitch=0)
+        f.update(change)
+        return _lib.EasBnPending(**f)
+
+    def lif(tn, **change):
+        return L.eas_bn_lif_fwd_ex(y.data_ptr(), 0, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None, None, None, 0.5,
+                                   1.0, 0.0, 0, out.data_ptr(), None, Tn, Nn, Cn, HW, 0, ctypes.byref(pending(tn, **change)), None, 0, None,
+                                   None, 0, st)
+
+    def silu(tn, **change):
+        return L.eas_bn_silu_fwd_ex(y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), Nn, Cn,
+                                    HW, ctypes.byref(pending(tn, **change)), 0, 0, st)
+
+    def silu_group(tn, **change):
+        arr = (_lib.EasBnSiluFwdProblem * 1)(_lib.EasBnSiluFwdProblem(y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                                                                      beta.data_ptr(), out.data_ptr(), Nn, Cn, HW, 0, 0, pending(tn, **change)))
+        return L.eas_bn_silu_fwd_group(arr, 1, st)
+
+    invalid = {'chunks = 0': dict(chunks=0), 'chunks > pitch': dict(chunks=5, pitch=4), 'chunks > default pitch': dict(chunks=65),
+               'negative pitch': dict(pitch=-1), 'count = 0.5': dict(count=0.5), 'replicas = 0': dict(replicas=0),
+               'running_mean only': dict(running_var=None), 'running_var only': dict(running_mean=None)}
+    INVALID_ARG = -1                # include/eas_hip.h EAS_ERR_INVALID_ARG
+    for entry, tn in ((lif, Tn * Nn), (silu, Nn), (silu_group, Nn)):
+        for what, change in invalid.items():
+            before = L.eas_launch_counter()
+            rc = entry(tn, **change)
+            assert rc == INVALID_ARG, f'{entry.__name__}: {what}: status {rc}'
+            assert L.eas_launch_counter() == before, f'{entry.__name__}: {what}: a refused call launched a kernel'
+        before = L.eas_launch_counter()
+        assert entry(tn) == 0, f'{entry.__name__}: the valid struct is refused'
+        assert L.eas_launch_counter() == before + 1
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(mean).all()) and bool(torch.isfinite(invstd).all())

@@ -616,6 +616,72 @@ def test_lif_multistep_vs_oracle(dev, kind, sg, alpha, v_reset, decay_input, det
     assert isinstance(hip.v, float)
 
 
+def _lif_steps_fp32(x, v, k, v_th, v_reset, hard, di, strict):
+    """eas_lif_step (csrc/eas_common.h) restated step by step in fp32 torch on the CPU: every * and + rounds separately, as the kernel's do.
+    -> spikes [T, M], final potential, mean over T, charged potentials h [T, M]"""
+    omk = 1.0 - k
+    spikes, hs = [], []
+    acc = torch.zeros_like(v)
+    for xt in x:
+        if di:
+            h = v + (xt - (v - v_reset)) * k if hard else v + (xt - v) * k
+        else:
+            h = (v - (v - v_reset) * k) + xt if (hard and v_reset != 0.0) else v * omk + xt
+        u = h - v_th
+        s = ((u > 0) if strict else (u >= 0)).float()
+        v = (1.0 - s) * h + s * v_reset if hard else h - s * v_th
+        acc = acc + s
+        spikes.append(s)
+        hs.append(h)
+    return torch.stack(spikes), v, acc / float(len(x)), torch.stack(hs)
+
+
+@pytest.mark.parametrize('T', [3, 11])                    # a kernel instance with T as a constant (T <= 8), the one for any T
+@pytest.mark.parametrize('strict', [False, True])
+@pytest.mark.parametrize('decay_input', [False, True])
+@pytest.mark.parametrize('hard', [False, True])
+def test_lif_flag_forms_and_both_walks(dev, hard, decay_input, strict, T):
+    """Every (reset, decay, firing) form of the stand-alone neuron, on 36 columns (rows of whole float4 groups: the 16-byte walk) and on
+    the first 35 of them as a tensor of their own (rows not 16-byte aligned: the scalar walk).  k = 0.5 is a constant (w = None), so no
+    value depends on an exponential; potentials and some inputs are multiples of 1/8 chosen such that the first charge lands exactly on
+    the threshold ('>=' fires there, strict '>' does not).  Bit for bit: spikes, final potential and mean against the fp32 restatement of
+    the step on the CPU; the first 35 columns of one walk against the other; and grad_x of those columns between the walks, from one
+    grad_s and one grad_mean whose 36th column is zero.  (The scalar parameter gradients are block sums that depend on the layout: they
+    stay with the oracle tests.)"""
+    from eas_snn_amd import ops
+    M, k, v_th = 36, 0.5, 1.0
+    v_reset = -0.5 if hard else 0.0
+    flags = (ops.FLAG_HARD_RESET if hard else 0) | (ops.FLAG_DECAY_INPUT if decay_input else 0) | (ops.FLAG_FIRE_STRICT if strict else 0)
+    gen = torch.Generator().manual_seed(1000 * T + flags)
+    x = torch.randn(T, M, generator=gen) * 0.8 + 0.4
+    v0 = torch.randint(-4, 7, (M,), generator=gen).float() / 8
+    on_th = [0, 5, 17, 22, 33, 34, 35]                  # columns whose first charge is exactly v_th (every product below is exact)
+    vt = v0[on_th]
+    if decay_input:
+        x[0, on_th] = 2.0 * v_th - vt - v_reset if hard else 2.0 * v_th - vt
+    else:
+        x[0, on_th] = v_th - (vt - (vt - v_reset) * k) if hard else v_th - vt * (1.0 - k)
+    s_ref, v_ref, m_ref, h_ref = _lif_steps_fp32(x, v0, k, v_th, v_reset, hard, decay_input, strict)
+    assert torch.equal(h_ref[0, on_th], torch.full((len(on_th),), v_th))
+    assert torch.equal(s_ref[0, on_th], torch.full((len(on_th),), 0.0 if strict else 1.0))
+    g_s = torch.randn(T, M, generator=gen)
+    g_m = torch.randn(M, generator=gen)
+    g_s[:, 35] = 0.0
+    g_m[35] = 0.0
+    got = {}
+    for cols in (36, 35):
+        xd = x[:, :cols].contiguous().to(dev).requires_grad_(True)
+        s, v, mean = ops.lif_multistep(xd, v0[:cols].contiguous().to(dev), None, k, v_th, v_reset, flags, 'atan', 2.0, want_mean=True,
+                                       write_v=True)
+        ((s * g_s[:, :cols].to(dev)).sum() + (mean * g_m[:cols].to(dev)).sum()).backward()
+        got[cols] = {'spikes': s.detach().cpu(), 'v': v.cpu(), 'mean': mean.detach().cpu(), 'grad_x': xd.grad.cpu()}
+        for name, ref in (('spikes', s_ref), ('v', v_ref), ('mean', m_ref)):
+            assert torch.equal(got[cols][name], ref[..., :cols]), f'{cols} columns: {name} differs from the fp32 restatement'
+    for name in ('spikes', 'v', 'mean', 'grad_x'):
+        assert torch.equal(got[36][name][..., :35], got[35][name]), f'{name}: the float4 walk and the scalar walk differ'
+    assert bool(got[35]['grad_x'].abs().sum() > 0)
+
+
 def test_lif_golden_inrepo_liflayer(dev):
     """The reference's own LIFLayer vectors (strict '>' firing, Rectangle surrogate) through the C ABI flags."""
     from eas_snn_amd import ops
