@@ -175,6 +175,9 @@ class EventExp(BaseExp):
         from yolox.utils import get_world_size      # (answers from the launcher's parameters while the process group is still deferred)
         if is_distributed:
             batch_size = batch_size // get_world_size()
+        if getattr(self, 'train_input', None) == 'stacked_hist':       # opt-in: the 1 Mpx path (indices into a resident store -> augmented frames)
+            from eas_snn_amd.data import SyntheticStackedHistLoader
+            return SyntheticStackedHistLoader(self, batch_size)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):

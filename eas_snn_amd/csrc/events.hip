@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "eas_common.h"
+#include "linear_tap.h"
 
 namespace {
 
@@ -579,23 +580,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_surface_exp_kernel(const uint3
 // OpenCV's resize.cpp (not in the reference tree, opencv-python pinned by pip-requirements.txt; no cv2 in this image:
 // parity unpinned): fx = float((j + 0.5) * (iw / nw) - 0.5), sx = floor(fx), fx -= sx, clamped at both borders with
 // fx = 0; float32 weights, float64 arithmetic, horizontal pass first: out = (S[sy][sx]*a0 + S[sy][sx+1]*a1)*b0 + (...)*b1.
-struct AxisTap { int s0, s1; float w0, w1; };
-
-__device__ __forceinline__ AxisTap linear_tap(int j, int n_src, int n_dst) {
-    const double scale = (double)n_src / (double)n_dst;
-    float f = (float)(((double)j + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= n_src - 1) { f = 0.f; s = n_src - 1; }
-    AxisTap t;
-    t.s0 = s;
-    t.s1 = s + 1 < n_src ? s + 1 : n_src - 1;
-    t.w0 = 1.f - f;
-    t.w1 = f;
-    return t;
-}
-
+// The per-axis rule (AxisTap, linear_tap) lives in linear_tap.h: eas_stacked_hist_frames resizes with the same one.
 __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ params,
                                                                      int B, int F, int H, int W, int Hc, int Wc, float* __restrict__ out) {
     const int64_t total = (int64_t)B * F * Hc * Wc;

@@ -230,6 +230,136 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
     return ops.counts_letterbox(counts, params, Hc, Wc, interp=interp)
 
 
+# ------------------------------------------------------------------------------------------------ 1 Mpx (RVT stacked histograms)
+def rvt_first_index(obj2repr_idx, label_index, num_slice, offset=0):
+    """Index of the representation that feeds output slice 0 of a sample: RVTGEN4Dataset.generate_slices' ``start_idx`` (rvt_gen4.py:114-116:
+    ``end_idx = objframe_idx_2_repr_idx[time] + 1``, ``start_idx = end_idx - num_slice``) plus the recording's ``offset`` in a store that holds
+    several recordings.  May be negative (a young sequence: ``ops.stacked_hist_frames`` fills zero slices in front).  ``obj2repr_idx`` and
+    ``label_index`` are numpy arrays / integers on the host or torch tensors on the device; nothing is read back."""
+    return obj2repr_idx[label_index] + 1 - num_slice + offset
+
+
+def gen4_rescale_labels(rows, factor, img_size):
+    """The ``rescale`` closure of RVTGEN4Dataset.extract_labels (rvt_gen4.py:370-387) on the rows of one object frame: float32 [L, 7] =
+    (t, x, y, w, h, class_id, class_confidence) as the reference makes them; every coordinate times 1 / ``factor`` (down_sample_factor),
+    corners clipped to ``img_size`` (h, w) - 1, boxes that lose their area dropped.  Factor 1 or no rows: returned as they are, unclipped,
+    like the reference.  Returns a new float32 array."""
+    rows = np.array(rows, dtype=np.float32).reshape(-1, 7)
+    if len(rows) == 0 or 1.0 / factor == 1:
+        return rows
+    m = np.float32(1.0 / factor)
+    h, w = int(img_size[0]), int(img_size[1])
+    x2 = np.clip((rows[:, 1] + rows[:, 3]) * m, 0, w - 1)
+    y2 = np.clip((rows[:, 2] + rows[:, 4]) * m, 0, h - 1)
+    x1 = np.clip(rows[:, 1] * m, 0, w - 1)
+    y1 = np.clip(rows[:, 2] * m, 0, h - 1)
+    rows[:, 3], rows[:, 4], rows[:, 1], rows[:, 2] = x2 - x1, y2 - y1, x1, y1
+    return rows[(rows[:, 3] > 0) & (rows[:, 4] > 0)]
+
+
+def gen4_raw_boxes(rows):
+    """(x1, y1, x2, y2, class_id) float32 [L, 5] of label rows (t, x, y, w, h, class_id, ...), as RVTGEN4Dataset.__getitem__ builds
+    ``raw_bboxes`` (rvt_gen4.py:199-207).  The box side of get_random_data (rvt_gen4.py:510-598, line for line the arithmetic of
+    gen1.py:433-521) is ``letterbox_params`` / ``jitter_params(..., jitter=.3)`` and ``transform_boxes`` as they are."""
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 7)
+    return np.stack([rows[:, 1], rows[:, 2], rows[:, 1] + rows[:, 3], rows[:, 2] + rows[:, 4], rows[:, 5]], axis=-1)
+
+
+def rvt_to_frames(store, first, exp_or_dims, params, lo=None):
+    """Representations resident in HBM -> model input [B, 1, Tm, 2, Hc, Wc] fp32 by ``ops.stacked_hist_frames``: one launch, nothing read
+    back (graph-capturable when ``first``, ``params`` and ``lo`` are device tensors).  ``store`` u8 [R, 2*nbins, H, W]; ``first`` int64 [B]
+    (``rvt_first_index``); ``exp_or_dims``: an experiment (fields ``Tm``, ``input_size``, optionally ``nbins``, default 10) or a tuple
+    ``(Tm, (Hc, Wc))`` with an optional third element ``nbins``; ``params``: per-sample (nw, nh, dx, dy, flip) rows, a device int32
+    tensor or anything numpy reads, None = the sensor unscaled at the top left (validation at scale 1); ``lo``: first representation of
+    each sample's recording (None: 0)."""
+    if isinstance(exp_or_dims, (tuple, list)):
+        Tm, (Hc, Wc) = exp_or_dims[:2]
+        nbins = exp_or_dims[2] if len(exp_or_dims) > 2 else 10
+    else:
+        Tm, (Hc, Wc), nbins = exp_or_dims.Tm, exp_or_dims.input_size, getattr(exp_or_dims, 'nbins', 10)
+    if params is not None and not torch.is_tensor(params):
+        params = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5)).to(store.device)
+    return ops.stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=nbins, lo=lo, params=params)
+
+
+class SyntheticStackedHistLoader:
+    """Training loader of the 1 Mpx path on synthetic data: iterable of (frames [B, 1, Tm, 2, Hc, Wc] fp32 on the GPU, targets [B, 50, 5]
+    rows (cls, cx, cy, w, h), zero padded -- the layout of ``synth_targets``).  One synthetic recording of ``representations`` stacked
+    histograms (u8, Poisson(``rate``) clamped to 255, drawn as ``workloads`` config 4 draws its batch) stays on the device; every
+    representation carries one label (objframe_idx_2_repr_idx is the identity) with the boxes of ``raw_boxes``.  An epoch is a permutation
+    of the labels; each sample draws its own ``jitter_params(..., jitter=.3)``; frames come from ``rvt_to_frames``, targets from
+    ``transform_boxes`` (without the reference's shuffle of a sample's boxes: their order carries nothing).  ``batches(epoch)`` returns
+    the draws of an epoch -- a function of (seed, epoch) alone."""
+
+    def __init__(self, exp, batch_size, representations=64, sensor_hw=(360, 640), nbins=10, rate=0.03, seed=0, max_labels=50):
+        self.exp, self.batch_size, self.sensor_hw, self.nbins, self.seed, self.max_labels = exp, batch_size, tuple(sensor_hw), nbins, seed, max_labels
+        self.representations, self.rate = representations, rate
+        self.obj2repr = np.arange(representations, dtype=np.int64)
+        self.iters = representations // batch_size
+        assert self.iters >= 1, 'fewer labels than one batch'
+        self.dataset = SyntheticEventDataset(exp, length=representations)
+        self.epoch = 0
+        self._store = None
+
+    def __len__(self):
+        return self.iters
+
+    def close_mosaic(self):
+        pass
+
+    def store(self, device):
+        if self._store is None or self._store.device != device:
+            g = torch.Generator().manual_seed(1 + self.seed)
+            H, W = self.sensor_hw
+            hist = torch.poisson(torch.full((self.representations, 2 * self.nbins, H, W), float(self.rate)), generator=g)
+            self._store = hist.clamp_(max=255).to(torch.uint8).to(device)
+        return self._store
+
+    def raw_boxes(self, label):
+        """(x1, y1, x2, y2, class) rows of label ``label`` on the sensor: two boxes that move with the label index"""
+        H, W = self.sensor_hw
+        s = (int(label) % 8) / 16.0
+        nc = max(int(getattr(self.exp, 'num_classes', 2)), 1)
+        return np.array([[(0.10 + s) * W, 0.20 * H, (0.35 + s) * W, 0.55 * H, int(label) % nc],
+                         [0.50 * W, (0.30 + s / 2) * H, 0.80 * W, (0.60 + s / 2) * H, (int(label) + 1) % nc]], dtype=np.float32)
+
+    def batches(self, epoch):
+        """[(label indices int64 [B], params int32 [B, 5])] of an epoch"""
+        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
+        perm = rs.permutation(self.representations)
+        (H, W), (Hc, Wc) = self.sensor_hw, self.exp.input_size
+        out = []
+        for i in range(self.iters):
+            idx = perm[i * self.batch_size:(i + 1) * self.batch_size].astype(np.int64)
+            par = np.array([jitter_params(H, W, Hc, Wc, jitter=.3, rng=rs) for _ in idx], dtype=np.int32)
+            out.append((idx, par))
+        return out
+
+    def targets(self, idx, par):
+        """[B, max_labels, 5] float32 (cls, cx, cy, w, h) of the labels ``idx`` under the draws ``par``"""
+        (H, W), (Hc, Wc) = self.sensor_hw, self.exp.input_size
+        t = np.zeros((len(idx), self.max_labels, 5), dtype=np.float32)
+        for b, (label, p) in enumerate(zip(idx, par)):
+            box = transform_boxes(self.raw_boxes(label), tuple(int(v) for v in p), H, W, Hc, Wc)[:self.max_labels]
+            n = len(box)
+            if n:
+                t[b, :n, 0] = box[:, 4]
+                t[b, :n, 1], t[b, :n, 2] = (box[:, 0] + box[:, 2]) / 2, (box[:, 1] + box[:, 3]) / 2
+                t[b, :n, 3], t[b, :n, 4] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        return t
+
+    def __iter__(self):
+        dev = torch.device('cuda', torch.cuda.current_device())
+        store = self.store(dev)
+        obj2repr = torch.from_numpy(self.obj2repr).to(dev)
+        draws = self.batches(self.epoch)
+        self.epoch += 1
+        for idx, par in draws:
+            first = rvt_first_index(obj2repr, torch.from_numpy(idx).to(dev), self.exp.Tm)
+            frames = rvt_to_frames(store, first, (self.exp.Tm, self.exp.input_size, self.nbins), torch.from_numpy(par).to(dev))
+            yield frames, torch.from_numpy(self.targets(idx, par)).to(dev)
+
+
 def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params):
     """events -> histogram (K1) -> resize / paste / flip on the device -> [B, 1, Tm, 2, Hc, Wc] fp32; ``params``: per-sample
     (nw, nh, dx, dy, flip) rows."""

@@ -127,6 +127,34 @@ def stacked_hist_event_sum(hist, Hc, Wc, nbins=10, n_valid=None):
     return out
 
 
+def stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=10, lo=None, params=None, return_flags=False):
+    """The 1 Mpx training input from indices: ``store`` u8 [R, 2*nbins, H, W] (the representations of one or more recordings back to back,
+    resident in HBM), ``first`` int64 [B] (index of the representation that feeds output slice 0: ``data.rvt_first_index``) -> fp32 model
+    input [B, 1, Tm, 2, Hc, Wc]: bin sums of slices first[b] .. first[b] + Tm - 1, resized / pasted / flipped by ``params`` int32 [B, 5] =
+    (nw, nh, dx, dy, flip) with cv2 INTER_LINEAR semantics (None: (W, H, 0, 0, 0), the validation letterbox at scale 1), bit-identical to
+    ``counts_letterbox`` of the int32 bin sums (RVTGEN4Dataset.__getitem__, rvt_gen4.py:190-235).  ``lo`` int64 [B] (None: 0): first
+    representation of each sample's recording; slices below it are zero (a young sequence).  A slice at or behind R is zero too and sets
+    bit 0 of the sample's flag (``return_flags``: also int32 [B])."""
+    _dev(store, first, lo, params)
+    assert store.dtype == torch.uint8 and store.dim() == 4 and store.shape[1] == 2 * nbins
+    assert first.dtype == torch.int64 and first.dim() == 1
+    store, first = store.contiguous(), first.contiguous()
+    R, _, H, W = store.shape
+    B = first.numel()
+    if lo is not None:
+        assert lo.dtype == torch.int64 and lo.shape == (B,)
+        lo = lo.contiguous()
+    if params is not None:
+        assert params.dtype == torch.int32 and params.shape == (B, 5)
+        params = params.contiguous()
+    out = torch.empty((B, 1, Tm, 2, Hc, Wc), dtype=torch.float32, device=store.device)
+    flags = torch.empty(B, dtype=torch.int32, device=store.device) if return_flags else None
+    # bytes: every source row at most once per (sample, slice) + the frames (a downscale reads fewer rows)
+    _call('eas_stacked_hist_frames', B * Tm * 2 * nbins * H * W + 4 * out.numel(), _lib.lib().eas_stacked_hist_frames, ptr(store), R, ptr(first),
+          ptr(lo), ptr(params), B, int(Tm), int(nbins), H, W, Hc, Wc, ptr(out), ptr(flags), stream())
+    return (out, flags) if return_flags else out
+
+
 def counts_to_canvas(counts, Hc, Wc):
     """int32 [..., H, W] -> float32 [..., Hc, Wc], zero padded bottom/right."""
     _dev(counts)

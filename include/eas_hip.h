@@ -173,6 +173,21 @@ int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, i
  * (the model input [B][Tl=1][Tm][2][Hc][Wc]), Hc >= H, Wc >= W, Wc % 16 == 0.  Integer sums (<= 255*nbins): bit-exact. */
 int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int B, int Tm, int nbins, int H, int W, int Hc,
                                int Wc, float* out, eas_stream_t stream);
+/* The 1 Mpx TRAINING input: what RVTGEN4Dataset.__getitem__ does for a sample (rvt_gen4.py:190-235), from indices into a store of
+ * representations that stays in HBM.  store: u8 [R][2*nbins][H][W], the representations of one or more recordings back to back
+ * (channel = polarity*nbins + bin).  first (int64 [B]): index of the representation that feeds output slice 0 of sample b --
+ * objframe_idx_2_repr_idx[time] + 1 - num_slice (rvt_gen4.py:114-116) plus the recording's offset in the store; output slice j reads
+ * store[first[b] + j].  lo (int64 [B], nullable = 0): first representation of sample b's recording; a slice whose index is below
+ * lo[b] (or below 0) is zero: max(start_idx, 0) and reps_padding in front (rvt_gen4.py:119-124).  An index >= R is never read either:
+ * the slice is zero and bit 0 of flags[b] is set (flags: uint32 [B], nullable, every element written by the call).
+ * params (int32 [B][5], nullable = (W, H, 0, 0, 0) for every sample): the (nw, nh, dx, dy, flip) rows of eas_counts_letterbox,
+ * get_random_data's resize with cv2.INTER_LINEAR, paste and flip (rvt_gen4.py:510-598, the arithmetic of gen1.py:433-521).  They are
+ * never validated on the host: nw <= 0 or nh <= 0 is an empty canvas, a paste rectangle that leaves the canvas is clipped.
+ * out: fp32 [B][Tm][2][Hc][Wc], every element written; any Hc, Wc >= 1 with Wc % 16 == 0 (smaller than the sensor too), nbins <= 255.
+ * Bit-identical to the bin sums stored as int32 and passed through eas_counts_letterbox; with params NULL and Hc >= H, Wc >= W to
+ * eas_stacked_hist_event_sum on the gathered slices. */
+int eas_stacked_hist_frames(const uint8_t* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B,
+                            int Tm, int nbins, int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K2  multi-step (P)LIF neuron.  Replaces spikingjelly ParametricLIFNode / LIFNode

@@ -110,9 +110,53 @@ def dwconv(args):
         print(f'forward + both gradients, {form} input: native {a:.3f} ms | library {b:.3f} ms | x{b / a:.2f}')
 
 
+def gen4(args):
+    """The 1 Mpx training input at config-4 shape (B = 32, Tm = 4, 360 x 640 -> 384 x 640, nbins 10): ``stacked_hist_frames`` from indices
+    into a resident store with the letterbox row and with a scale-0.4 jitter row, against the composition it replaces
+    (``stacked_hist_event_sum`` of the gathered batch into a sensor-size canvas -> int32 -> ``counts_letterbox``; the gather of the batch is
+    not timed).  The forms alternate inside every round.  GB/s = algorithmic bytes over the time: the named source rows once (u8) and the
+    frames once (fp32) for the fused form; for the composition also the fp32 sums written and read, the int32 sums written and read."""
+    dev = torch.device('cuda:0')
+    B = int(args[0]) if args else 32
+    Tm, R, H, W, Hc, Wc, nb = 4, 96, 360, 640, 384, 640, 10
+    torch.manual_seed(1)
+    store = torch.cat([torch.poisson(torch.full((R // 4, 2 * nb, H, W), 0.03, device=dev)).clamp_(max=255).to(torch.uint8) for _ in range(4)])
+    first = torch.randperm(R - Tm)[:B].to(dev)                   # 442 MB of representations: more than the 256 MiB last-level cache
+    from eas_snn_amd import data
+    letter = torch.tensor([data.letterbox_params(H, W, Hc, Wc)] * B, dtype=torch.int32, device=dev)
+    nw, nh = int(.4 * Wc), int(int(.4 * Wc) / (W / H))
+    small = torch.tensor([(nw, nh, 100 + 3 * b, 50 + 2 * b, b & 1) for b in range(B)], dtype=torch.int32, device=dev)
+    gathered = torch.stack([store[int(f):int(f) + Tm] for f in first.tolist()])
+
+    def composition(par):
+        sums = ops.stacked_hist_event_sum(gathered, H, W)
+        return ops.counts_letterbox(sums.view(B, Tm, 2, H, W).to(torch.int32), par, Hc, Wc)
+    assert torch.equal(composition(letter).view(-1), ops.stacked_hist_frames(store, first, Tm, Hc, Wc, params=letter).view(-1))
+    assert torch.equal(composition(small).view(-1), ops.stacked_hist_frames(store, first, Tm, Hc, Wc, params=small).view(-1))
+    n_in, n_mid, n_out = B * Tm * 2 * nb * H * W, B * Tm * 2 * H * W, B * Tm * 2 * Hc * Wc
+    rows_small = min(2 * nh, H)                                 # source rows two taps per output row can name
+    forms = [('fused, letterbox row', lambda: ops.stacked_hist_frames(store, first, Tm, Hc, Wc, params=letter), n_in + 4 * n_out),
+             ('fused, params None', lambda: ops.stacked_hist_frames(store, first, Tm, Hc, Wc), n_in + 4 * n_out),
+             ('fused, scale 0.4 row', lambda: ops.stacked_hist_frames(store, first, Tm, Hc, Wc, params=small), n_in * rows_small // H + 4 * n_out),
+             ('composition, letterbox row', lambda: composition(letter), n_in + 16 * n_mid + 4 * n_out),
+             ('composition, scale 0.4 row', lambda: composition(small), n_in + 16 * n_mid + 4 * n_out),
+             ('event_sum alone (config 4 today)', lambda: ops.stacked_hist_event_sum(gathered, Hc, Wc), n_in + 4 * n_out)]
+    rounds = [[] for _ in forms]
+    for _ in range(5):
+        for k, (_, fn, _) in enumerate(forms):
+            rounds[k].append(timeit_spread(fn, reps=20, warm=3))
+    print(f'B={B} Tm={Tm} {H}x{W} -> {Hc}x{Wc}; ms = median of 5 rounds of (median of 20), (min..max over all)')
+    for (name, _, nbytes), r in zip(forms, rounds):
+        med = sorted(x[0] for x in r)[len(r) // 2]
+        print(f'{name:34s}: {med:7.3f} ms ({min(x[1] for x in r):.3f}..{max(x[2] for x in r):.3f})  {nbytes / 1e6:7.1f} MB  {nbytes / med / 1e6:7.0f} GB/s',
+              flush=True)
+
+
 if __name__ == '__main__':
     what = sys.argv[1] if len(sys.argv) > 1 else 'smallconv'
     if what == 'smallconv':
         smallconv(sys.argv[2:])
     elif what == 'dwconv':
         dwconv(sys.argv[2:])
+    elif what == 'gen4':
+        gen4(sys.argv[2:])
