@@ -8,7 +8,7 @@
 #include <string.h>
 
 #include "eas_common.h"
-#include "linear_tap.h"
+#include "count_resize.h"
 
 namespace {
 
@@ -574,13 +574,11 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_surface_exp_kernel(const uint3
     }
 }
 
-// Letterbox / jitter augmentation of count frames on the device (GEN1Dataset.get_random_data, gen1.py:433-521): every
-// frame of sample b is resized to (nw, nh) with cv2.resize(INTER_LINEAR) semantics, pasted at (dx, dy) into a zero canvas,
-// optionally mirrored left-right, and cast to fp32 (trainer.py:99).  cv2's linear resize for float64 images, restated from
-// OpenCV's resize.cpp (not in the reference tree, opencv-python pinned by pip-requirements.txt; no cv2 in this image:
-// parity unpinned): fx = float((j + 0.5) * (iw / nw) - 0.5), sx = floor(fx), fx -= sx, clamped at both borders with
-// fx = 0; float32 weights, float64 arithmetic, horizontal pass first: out = (S[sy][sx]*a0 + S[sy][sx+1]*a1)*b0 + (...)*b1.
-// The per-axis rule (AxisTap, linear_tap) lives in linear_tap.h: eas_stacked_hist_frames resizes with the same one.
+// Letterbox / jitter augmentation of count frames on the device (GEN1Dataset.get_random_data, gen1.py:433-521; NCaltech.batch_resize,
+// ncaltech.py:98-105): every frame of sample b is resized to (nw, nh) with the cv2.resize semantics of ``Rule`` (LinearRule: INTER_LINEAR,
+// CubicRule: INTER_CUBIC), pasted at (dx, dy) into a zero canvas, optionally mirrored left-right, and cast to fp32 (trainer.py:99).  The
+// paste rule, the tap rules and the tap-weighted sum live in count_resize.h: eas_stacked_hist_frames resizes with the same ones.
+template <typename Rule>
 __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ params,
                                                                      int B, int F, int H, int W, int Hc, int Wc, float* __restrict__ out) {
     const int64_t total = (int64_t)B * F * Hc * Wc;
@@ -589,84 +587,15 @@ __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32
         const int64_t r = i / Wc;
         const int yy = (int)(r % Hc);
         const int64_t f = r / Hc;
-        const int b = (int)(f / F);
-        const int32_t* pr = params + 5 * b;
-        const int nw = pr[0], nh = pr[1], dx = pr[2], dy = pr[3], flip = pr[4];
-        const int xs = (flip ? Wc - 1 - xx : xx) - dx, ys = yy - dy;
+        const Paste paste(params + 5 * (int)(f / F));
+        const int xs = paste.src_col(xx, Wc), ys = paste.src_row(yy);
         float v = 0.f;
-        if (xs >= 0 && xs < nw && ys >= 0 && ys < nh) {
+        if (paste.inside(xs, ys)) {
             const int32_t* src = counts + f * H * W;
-            if (nw == W && nh == H) {
-                v = (float)src[ys * W + xs];                  // cv2.resize with dsize == size is a copy
-            } else {
-                const AxisTap tx = linear_tap(xs, W, nw), ty = linear_tap(ys, H, nh);
-                const double r0 = (double)src[ty.s0 * W + tx.s0] * (double)tx.w0 + (double)src[ty.s0 * W + tx.s1] * (double)tx.w1;
-                const double r1 = (double)src[ty.s1 * W + tx.s0] * (double)tx.w0 + (double)src[ty.s1 * W + tx.s1] * (double)tx.w1;
-                v = (float)(r0 * (double)ty.w0 + r1 * (double)ty.w1);
-            }
-        }
-        out[i] = v;
-    }
-}
-
-// The same letterbox with cv2.resize(INTER_CUBIC) semantics (NCaltech.batch_resize, ncaltech.py:98-105, 293-295, 313, 342).  OpenCV's
-// generic cubic resize for float64 images, restated from OpenCV's resize.cpp (not in the reference tree, opencv-python pinned by
-// pip-requirements.txt; no cv2 in this image: parity unpinned): per axis f = float((j + 0.5) * (n_src / n_dst) - 0.5), s = floor(f),
-// f -= s without a clamp; float32 weights with A = -0.75 (interpolateCubic); taps s-1 .. s+2, each index clamped to the image; float64
-// arithmetic, horizontal pass first, the four products added left to right, then the vertical pass over the four row results in the
-// same form, then the cast to fp32.  No FMA contraction (this library is built with -ffp-contract=off; the pragma says so for this
-// function whatever the flags), so the result equals a numpy restatement bit for bit.
-struct CubicTap { int s[4]; float c[4]; };
-
-__device__ __forceinline__ CubicTap cubic_tap(int j, int n_src, int n_dst) {
-#pragma clang fp contract(off)
-    const double scale = (double)n_src / (double)n_dst;
-    float f = (float)(((double)j + 0.5) * scale - 0.5);
-    const int s = (int)floorf(f);
-    f -= (float)s;
-    const float A = -0.75f;
-    CubicTap t;
-    t.c[0] = ((A * (f + 1.f) - 5.f * A) * (f + 1.f) + 8.f * A) * (f + 1.f) - 4.f * A;
-    t.c[1] = ((A + 2.f) * f - (A + 3.f)) * f * f + 1.f;
-    t.c[2] = ((A + 2.f) * (1.f - f) - (A + 3.f)) * (1.f - f) * (1.f - f) + 1.f;
-    t.c[3] = 1.f - t.c[0] - t.c[1] - t.c[2];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = s - 1 + k;
-        t.s[k] = i < 0 ? 0 : (i > n_src - 1 ? n_src - 1 : i);
-    }
-    return t;
-}
-
-__global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_cubic_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ params,
-                                                                           int B, int F, int H, int W, int Hc, int Wc, float* __restrict__ out) {
-#pragma clang fp contract(off)
-    const int64_t total = (int64_t)B * F * Hc * Wc;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % Wc);
-        const int64_t r = i / Wc;
-        const int yy = (int)(r % Hc);
-        const int64_t f = r / Hc;
-        const int b = (int)(f / F);
-        const int32_t* pr = params + 5 * b;
-        const int nw = pr[0], nh = pr[1], dx = pr[2], dy = pr[3], flip = pr[4];
-        const int xs = (flip ? Wc - 1 - xx : xx) - dx, ys = yy - dy;
-        float v = 0.f;
-        if (xs >= 0 && xs < nw && ys >= 0 && ys < nh) {
-            const int32_t* src = counts + f * H * W;
-            if (nw == W && nh == H) {
-                v = (float)src[ys * W + xs];                  // cv2.resize with dsize == size is a copy
-            } else {
-                const CubicTap tx = cubic_tap(xs, W, nw), ty = cubic_tap(ys, H, nh);
-                double rows[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int32_t* row = src + ty.s[k] * W;
-                    rows[k] = (double)row[tx.s[0]] * (double)tx.c[0] + (double)row[tx.s[1]] * (double)tx.c[1] +
-                              (double)row[tx.s[2]] * (double)tx.c[2] + (double)row[tx.s[3]] * (double)tx.c[3];
-                }
-                v = (float)(rows[0] * (double)ty.c[0] + rows[1] * (double)ty.c[1] + rows[2] * (double)ty.c[2] + rows[3] * (double)ty.c[3]);
-            }
+            if (paste.identity(W, H))
+                v = (float)src[ys * W + xs];
+            else
+                v = resample<Rule::N>([src, W](int y) { return src + y * W; }, Rule::tap(xs, W, paste.nw), Rule::tap(ys, H, paste.nh));
         }
         out[i] = v;
     }
@@ -893,26 +822,23 @@ int eas_event_time_surface(const uint32_t* t, const uint16_t* x, const uint16_t*
     return EAS_OK;
 }
 
-int eas_counts_letterbox(const int32_t* counts, const int32_t* params, int B, int F, int H, int W, int Hc, int Wc, float* out,
-                         eas_stream_t stream) {
+int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                            eas_stream_t stream) {
+    if (interp != 0 && interp != 1) return EAS_ERR_INVALID_ARG;
     if (!counts || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
+    const dim3 grid(eas_grid_1d((int64_t)B * F * Hc * Wc));
     EAS_CLEAR_ERR();
-    EAS_LAUNCH(counts_letterbox_kernel, dim3(eas_grid_1d((int64_t)B * F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
-                       params, B, F, H, W, Hc, Wc, out);
+    if (interp == 0)
+        EAS_LAUNCH(counts_letterbox_kernel<LinearRule>, grid, dim3(EAS_BLOCK), 0, eas_s(stream), counts, params, B, F, H, W, Hc, Wc, out);
+    else
+        EAS_LAUNCH(counts_letterbox_kernel<CubicRule>, grid, dim3(EAS_BLOCK), 0, eas_s(stream), counts, params, B, F, H, W, Hc, Wc, out);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }
 
-int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
-                            eas_stream_t stream) {
-    if (interp == 0) return eas_counts_letterbox(counts, params, B, F, H, W, Hc, Wc, out, stream);
-    if (interp != 1) return EAS_ERR_INVALID_ARG;
-    if (!counts || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
-    EAS_CLEAR_ERR();
-    EAS_LAUNCH(counts_letterbox_cubic_kernel, dim3(eas_grid_1d((int64_t)B * F * Hc * Wc)), dim3(EAS_BLOCK), 0, eas_s(stream), counts,
-                       params, B, F, H, W, Hc, Wc, out);
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
+int eas_counts_letterbox(const int32_t* counts, const int32_t* params, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                         eas_stream_t stream) {
+    return eas_counts_letterbox_ex(counts, params, 0, B, F, H, W, Hc, Wc, out, stream);
 }
 
 }  // extern "C"

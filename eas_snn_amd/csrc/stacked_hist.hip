@@ -1,23 +1,96 @@
-// Config-4 input: RVT "stacked histogram" representation -> per-polarity event counts on the model canvas.
-// Replaces RVTGEN4Dataset.generate_slices(..., method='event_sum') + the zero padding of the validation letterbox
-// (yolox/data/datasets/rvt_gen4.py:109-125 and :516-533 with scale 1).
+// RVT "stacked histogram" representations -> per-polarity event counts on the model canvas: two kernels over shared pieces (SliceRule:
+// which representation feeds a slice; bin_sums16: the bin sum of 16 pixels; the paste and resize rule of count_resize.h).
 //
+// eas_stacked_hist_event_sum, the config-4 input: replaces RVTGEN4Dataset.generate_slices(..., method='event_sum') + the zero padding of the
+// validation letterbox (yolox/data/datasets/rvt_gen4.py:109-125 and :516-533 with scale 1).
 //   hist  u8  [B][Tm][2*nbins][H][W]   channel = polarity * nbins + bin  (the reference's reshape(n, 2, -1, H, W))
 //   out   f32 [B][Tm][2][Hc][Wc]       out[b][j][p] = sum over bins of hist[b][i][p*nbins + bin], zero outside H x W
 // A sample whose sequence is younger than Tm representations supplies only its first n_valid[b] slices; they are the
 // LAST n_valid[b] output slices (j = Tm - n_valid[b] + i), the leading ones are zero (rvt_gen4.py:122-123).
 //
-// HBM-bound integer work: per output element nbins bytes read + 4 bytes written (14 B at nbins = 10).  One thread owns 16
-// consecutive pixels of one (b, j, p, row): nbins 16-byte loads issued up front (64 lanes x 16 B = 1 KiB contiguous per plane
-// row), byte-wise unpack-accumulate in 16 integer registers, four float4 stores.  Sums <= 255 * nbins are exact in fp32.
+// HBM-bound integer work: per output element nbins bytes read + 4 bytes written (14 B at nbins = 10).  Sums <= 255 * nbins are exact in fp32.
 #include "eas_common.h"
-#include "linear_tap.h"
+#include "count_resize.h"
 
 namespace {
 
+// ---- shared pieces -------------------------------------------------------------------------------------------------------------------
+// Which representation of the store [R] feeds output slice j of sample b: f0 + j, where it lies in [low, R); a zero slice otherwise.
+//   store addressing: f0 = first[b], low = lo[b] (NULL: 0) -- any int64 may come in: f0 is clamped to [-Tm, R] before j is added, low to >= 0
+//   batch addressing (first == NULL): the store is a batch [B][Tm] whose sample b supplies its first n_valid[b] (NULL: Tm; clamped to
+//   [0, Tm]) slices as the last output slices: f0 = b * Tm - (Tm - n_valid[b]), low = b * Tm, R = B * Tm
+struct SliceRule {
+    int64_t f0, low, R;
 
+    __device__ __forceinline__ SliceRule(int64_t R_, const int64_t* __restrict__ first, const int64_t* __restrict__ lo,
+                                         const int32_t* __restrict__ n_valid, int b, int Tm) : R(R_) {
+        if (first) {
+            f0 = first[b];
+            f0 = f0 > R ? R : (f0 < -(int64_t)Tm ? -(int64_t)Tm : f0);
+            low = lo ? lo[b] : 0;
+            low = low < 0 ? 0 : low;
+        } else {
+            int nv = n_valid ? n_valid[b] : Tm;
+            nv = nv < 0 ? 0 : (nv > Tm ? Tm : nv);
+            low = (int64_t)b * Tm;
+            f0 = low - (Tm - nv);
+        }
+    }
+    __device__ __forceinline__ int64_t index(int j) const { return f0 + j; }
+    __device__ __forceinline__ bool have(int j) const { return f0 + j >= low && f0 + j < R; }
+    // the sample's flag word: bit 0 = one of its Tm slices lies at or behind the end of the store
+    __device__ __forceinline__ uint32_t flag(int Tm) const {
+        uint32_t fl = 0;
+        for (int k = 0; k < Tm; ++k) fl |= (f0 + k >= low && f0 + k >= R) ? 1u : 0u;
+        return fl;
+    }
+};
+
+// the 16 bytes of one bin's pixels onto the sums: even and odd bytes of a word go to accumulators of two 16-bit lanes each, two bytes per
+// operation (ev[q]: pixels 4q, 4q + 2; od[q]: pixels 4q + 1, 4q + 3)
+__device__ __forceinline__ void add_bytes16(const uint4& v, uint32_t (&ev)[4], uint32_t (&od)[4]) {
+    const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        ev[q] += wds[q] & 0x00ff00ffu;
+        od[q] += (wds[q] >> 8) & 0x00ff00ffu;
+    }
+}
+
+// 16 bin sums (pixels x0 .. x0 + 15 of one source row) as eight words of two 16-bit sums, pixel order.  NB > 0: the bin count at compile
+// time, all its loads issued before the first add (NB = 10 is the measured form)
 template <int NB>
-__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_sum_kernel(const uint8_t* __restrict__ hist, const int32_t* __restrict__ n_valid,
+__device__ __forceinline__ void bin_sums16(const uint8_t* __restrict__ src, int64_t plane, int nbins, bool vec, int n_left, uint32_t (&sum)[8]) {
+    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
+    if (vec && NB > 0) {
+        uint4 v[NB > 0 ? NB : 1];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) v[k] = *reinterpret_cast<const uint4*>(src + (int64_t)k * plane);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) add_bytes16(v[k], ev, od);
+    } else if (vec) {
+        for (int k = 0; k < nbins; ++k) add_bytes16(*reinterpret_cast<const uint4*>(src + (int64_t)k * plane), ev, od);
+    } else {                                  // rows that are not 16-byte aligned, ragged row end: n_left < 16 pixels exist
+        for (int k = 0; k < nbins; ++k) {
+            const uint8_t* row = src + (int64_t)k * plane;
+            uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                if (e < n_left) w[e >> 2] |= (uint32_t)row[e] << (8 * (e & 3));
+            add_bytes16(make_uint4(w[0], w[1], w[2], w[3]), ev, od);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        sum[2 * q] = (ev[q] & 0xffffu) | (od[q] << 16);
+        sum[2 * q + 1] = (ev[q] >> 16) | (od[q] & 0xffff0000u);
+    }
+}
+
+// eas_stacked_hist_event_sum: one thread owns 16 consecutive pixels of one (b, j, p, canvas row) -- their bin sums, four float4 stores; the
+// batch is a store of B * Tm representations in SliceRule's batch addressing
+template <int NB>
+__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_sum_kernel(const uint8_t* __restrict__ hist, const int32_t* __restrict__ n_valid, int B,
                                                                      int Tm, int nbins_rt, int H, int W, int Hc, int Wc,
                                                                      float* __restrict__ out, int64_t total_groups) {
     const int nbins = NB > 0 ? NB : nbins_rt;
@@ -34,123 +107,35 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_sum_kernel(const uint8
         const int b = (int)(r / Tm);
         const int x0 = xg * 16;
         float4* dst = reinterpret_cast<float4*>(out + ((((int64_t)b * Tm + j) * 2 + p) * Hc + y) * (int64_t)Wc + x0);
-        const int nv = n_valid ? n_valid[b] : Tm;
-        const int i = j - (Tm - nv);                     // input slice feeding output slice j
-        if (i < 0 || y >= H || x0 >= W) {
+        const SliceRule slice((int64_t)B * Tm, nullptr, nullptr, n_valid, b, Tm);
+        if (!slice.have(j) || y >= H || x0 >= W) {
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
             dst[0] = z; dst[1] = z; dst[2] = z; dst[3] = z;
             continue;
         }
-        const uint8_t* src = hist + ((((int64_t)b * Tm + i) * 2 + p) * nbins) * plane + (int64_t)y * W + x0;
-        uint32_t acc[16];
+        uint32_t sum[8];
+        bin_sums16<NB>(hist + ((slice.index(j) * 2 + p) * nbins) * plane + (int64_t)y * W + x0, plane, nbins, x0 + 16 <= W && (W & 15) == 0, W - x0, sum);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0;
-        if (x0 + 16 <= W && (W & 15) == 0) {
-            uint4 v[NB > 0 ? NB : 1];
-            if (NB > 0) {
-#pragma unroll
-                for (int k = 0; k < NB; ++k) v[k] = *reinterpret_cast<const uint4*>(src + (int64_t)k * plane);
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    const uint32_t wds[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        acc[4 * q + 0] += wds[q] & 0xffu;
-                        acc[4 * q + 1] += (wds[q] >> 8) & 0xffu;
-                        acc[4 * q + 2] += (wds[q] >> 16) & 0xffu;
-                        acc[4 * q + 3] += wds[q] >> 24;
-                    }
-                }
-            } else {
-                for (int k = 0; k < nbins; ++k) {
-                    const uint4 u = *reinterpret_cast<const uint4*>(src + (int64_t)k * plane);
-                    const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        acc[4 * q + 0] += wds[q] & 0xffu;
-                        acc[4 * q + 1] += (wds[q] >> 8) & 0xffu;
-                        acc[4 * q + 2] += (wds[q] >> 16) & 0xffu;
-                        acc[4 * q + 3] += wds[q] >> 24;
-                    }
-                }
-            }
-        } else {                                         // ragged row end or rows that are not 16-byte aligned: bytes one by one
-            for (int k = 0; k < nbins; ++k) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (x0 + e < W) acc[e] += src[(int64_t)k * plane + e];
-            }
-        }
-        dst[0] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
-        dst[1] = make_float4((float)acc[4], (float)acc[5], (float)acc[6], (float)acc[7]);
-        dst[2] = make_float4((float)acc[8], (float)acc[9], (float)acc[10], (float)acc[11]);
-        dst[3] = make_float4((float)acc[12], (float)acc[13], (float)acc[14], (float)acc[15]);
+        for (int q = 0; q < 4; ++q)
+            dst[q] = make_float4((float)(sum[2 * q] & 0xffffu), (float)(sum[2 * q] >> 16), (float)(sum[2 * q + 1] & 0xffffu), (float)(sum[2 * q + 1] >> 16));
     }
 }
 
 // ---- training input: indices into a resident store -> augmented frames (eas_stacked_hist_frames) --------------------------------------
 // RVTGEN4Dataset.__getitem__ for a training sample (rvt_gen4.py:190-235): the last Tm representations up to the label's
-// (generate_slices, :109-125, zero slices in front of a young sequence), the bin sum, then get_random_data's resize / paste / flip with
-// cv2.INTER_LINEAR (:510-598) -- the arithmetic of counts_letterbox_kernel (events.hip) on the integer bin sums, without the int32 frames in
-// between.
+// (generate_slices, :109-125, zero slices in front of a young sequence), the bin sum, then get_random_data's resize / paste / flip with cv2.INTER_LINEAR (:510-598) -- the arithmetic of
+// counts_letterbox_kernel<LinearRule> (events.hip) on the integer bin sums, without the int32 frames in between.
 //
 // One block takes a band of output rows of one (sample, slice, polarity).  The vertical taps of the band name at most 2 * rows source
 // rows; only those are read: their bin sums (<= 255 * nbins <= 65025: 16 bits) are staged in LDS, 16 pixels per lane and step with nbins
-// 16-byte loads issued up front (bytes one by one when rows are not 16-byte aligned), then every output pixel is a gather from LDS with
-// the horizontal taps of the band (one table per block) and the stores are float4.  Zero slices and bands outside the paste rectangle are
-// stores only.  params are device data nobody has validated: the paste rectangle is whatever part of [dx, dx + nw) x [dy, dy + nh) lies on
-// the canvas, nw <= 0 or nh <= 0 is an empty one, and a source row or column index comes out of linear_tap, which clamps to the sensor.
+// 16-byte loads issued up front (64 lanes x 16 B = 1 KiB contiguous per plane row; bytes one by one when rows are not 16-byte aligned), then
+// every output pixel is a gather from LDS with the horizontal taps of the band (one table per block) and the stores are float4.  Zero
+// slices and bands outside the paste rectangle are stores only.  Everything read from device memory is clamped: a slice index by
+// SliceRule, the paste row by Paste (count_resize.h), and a source row or column index comes out of linear_tap, which clamps to the sensor.
 constexpr int kFrameBandRows = 8;             // output rows per block at most (fewer on wide sensors: frames_band_rows)
 constexpr int kFrameLdsBytes = 48 * 1024;     // staged rows + tap tables
 
 struct XTap { uint32_t s01; float w1; };      // s0 | s1 << 16; w1 < 0: outside the paste rectangle
-
-// 16 bin sums (pixels x0 .. x0 + 15 of one source row) as eight words of two 16-bit sums, pixel order.  Two bytes of a word are added per
-// operation: even and odd bytes go to accumulators of two 16-bit lanes each.
-template <int NB>
-__device__ __forceinline__ void bin_sums16(const uint8_t* __restrict__ src, int64_t plane, int nbins, bool vec, int n_left, uint32_t (&sum)[8]) {
-    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};     // ev[q]: pixels 4q, 4q + 2; od[q]: pixels 4q + 1, 4q + 3
-    if (vec) {
-        if (NB > 0) {
-            uint4 v[NB > 0 ? NB : 1];
-#pragma unroll
-            for (int k = 0; k < NB; ++k) v[k] = *reinterpret_cast<const uint4*>(src + (int64_t)k * plane);
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                const uint32_t wds[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ev[q] += wds[q] & 0x00ff00ffu;
-                    od[q] += (wds[q] >> 8) & 0x00ff00ffu;
-                }
-            }
-        } else {
-            for (int k = 0; k < nbins; ++k) {
-                const uint4 u = *reinterpret_cast<const uint4*>(src + (int64_t)k * plane);
-                const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ev[q] += wds[q] & 0x00ff00ffu;
-                    od[q] += (wds[q] >> 8) & 0x00ff00ffu;
-                }
-            }
-        }
-    } else {                                  // rows that are not 16-byte aligned, ragged row end: n_left < 16 pixels exist
-        for (int k = 0; k < nbins; ++k) {
-            const uint8_t* row = src + (int64_t)k * plane;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t v = e < n_left ? (uint32_t)row[e] : 0u;
-                if (e & 1) od[e >> 2] += v << (8 * (e & 2)); else ev[e >> 2] += v << (8 * (e & 2));
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        sum[2 * q] = (ev[q] & 0xffffu) | (od[q] << 16);
-        sum[2 * q + 1] = (ev[q] >> 16) | (od[q] & 0xffff0000u);
-    }
-}
 
 template <int NB>
 __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const uint8_t* __restrict__ store, int64_t R, const int64_t* __restrict__ first,
@@ -176,67 +161,31 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const ui
     const int b = r / Tm;
     const int y0 = band * band_rows, rows = min(band_rows, Hc - y0);
 
-    // slice index: clamped to [-Tm, R] before j is added (any int64 may come in); below the recording's first representation: zero,
-    // at or behind the end of the store: zero and flagged
-    int64_t f0 = first[b];
-    f0 = f0 > R ? R : (f0 < -(int64_t)Tm ? -(int64_t)Tm : f0);
-    int64_t low = lo ? lo[b] : 0;
-    low = low < 0 ? 0 : low;
-    if (flags && band == 0 && p == 0 && j == 0 && tid == 0) {
-        uint32_t fl = 0;
-        for (int k = 0; k < Tm; ++k) fl |= (f0 + k >= low && f0 + k >= R) ? 1u : 0u;
-        flags[b] = fl;
-    }
-    const int64_t idx = f0 + j;
-    const bool have = idx >= low && idx < R;
-
-    int nw = W, nh = H, dx = 0, dy = 0, flip = 0;
-    if (params) {
-        const int32_t* pr = params + 5 * (int64_t)b;
-        nw = pr[0]; nh = pr[1]; dx = pr[2]; dy = pr[3]; flip = pr[4];
-    }
-    const bool identity = nw == W && nh == H;             // cv2.resize with dsize == size is a copy
+    const SliceRule slice(R, first, lo, nullptr, b, Tm);
+    if (flags && band == 0 && p == 0 && j == 0 && tid == 0) flags[b] = slice.flag(Tm);
+    const Paste paste = params ? Paste(params + 5 * (int64_t)b) : Paste(W, H);
+    const bool identity = paste.identity(W, H);
     float4* dst = reinterpret_cast<float4*>(out + ((((int64_t)b * Tm + j) * 2 + p) * Hc + y0) * (int64_t)Wc);
     const int wc4 = Wc / 4;
 
-    // vertical taps of the band's rows, and whether the band meets the paste rectangle at all (block-uniform)
-    const int64_t ys_first = (int64_t)y0 - dy, ys_last = ys_first + rows - 1;
-    const bool touches = have && nw > 0 && nh > 0 && ys_last >= 0 && ys_first < nh && (int64_t)dx < Wc && (int64_t)dx + nw > 0;
-    if (!touches) {
+    // a zero slice, or a band that does not meet the paste rectangle at all (block-uniform)
+    if (!slice.have(j) || !paste.touches(y0, rows, Wc)) {
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int i = tid; i < rows * wc4; i += EAS_BLOCK) dst[i] = z;
         return;
     }
+    // taps of the band's rows and of every canvas column; a copy is the tap (s, s) with weights (1, 0)
     if (tid < rows) {
-        const int64_t ys = ys_first + tid;
-        float w1 = -1.f;
-        int s0 = 0, s1 = 0;
-        if (ys >= 0 && ys < nh) {
-            if (identity) {
-                s0 = s1 = (int)ys;
-                w1 = 0.f;
-            } else {
-                const AxisTap t = linear_tap((int)ys, H, nh);
-                s0 = t.s0; s1 = t.s1; w1 = t.w1;
-            }
-        }
-        y_s0[tid] = s0; y_s1[tid] = s1; y_w1[tid] = w1;
+        const int ys = paste.src_row(y0 + tid);
+        Taps<2> t = {{0, 0}, {0.f, -1.f}};
+        if (paste.has_row(ys)) t = identity ? Taps<2>{{ys, ys}, {1.f, 0.f}} : linear_tap(ys, H, paste.nh);
+        y_s0[tid] = t.s[0]; y_s1[tid] = t.s[1]; y_w1[tid] = t.c[1];
     }
-    // horizontal taps of every canvas column
     for (int xx = tid; xx < Wc; xx += EAS_BLOCK) {
-        const int64_t xs = (int64_t)(flip ? Wc - 1 - xx : xx) - dx;
-        XTap t{0u, -1.f};
-        if (xs >= 0 && xs < nw) {
-            if (identity) {
-                t.s01 = (uint32_t)xs | ((uint32_t)xs << 16);
-                t.w1 = 0.f;
-            } else {
-                const AxisTap a = linear_tap((int)xs, W, nw);
-                t.s01 = (uint32_t)a.s0 | ((uint32_t)a.s1 << 16);
-                t.w1 = a.w1;
-            }
-        }
-        xtab[xx] = t;
+        const int xs = paste.src_col(xx, Wc);
+        Taps<2> t = {{0, 0}, {0.f, -1.f}};
+        if (paste.has_col(xs)) t = identity ? Taps<2>{{xs, xs}, {1.f, 0.f}} : linear_tap(xs, W, paste.nw);
+        xtab[xx] = XTap{(uint32_t)t.s[0] | ((uint32_t)t.s[1] << 16), t.c[1]};
     }
     __syncthreads();
     if (tid == 0) {                                       // the distinct source rows the band names -> staging slots (at most 2 * rows)
@@ -258,7 +207,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const ui
     // stage the bin sums of the named rows
     const int wg = wp / 16, n_groups = n_slots * wg;
     const int64_t plane = (int64_t)H * W;
-    const uint8_t* src0 = store + ((idx * 2 + p) * nbins) * plane;
+    const uint8_t* src0 = store + ((slice.index(j) * 2 + p) * nbins) * plane;
     const bool aligned = (W & 15) == 0;
     for (int g = tid; g < n_groups; g += EAS_BLOCK) {
         const int slot = g / wg, x0 = (g - slot * wg) * 16;
@@ -276,22 +225,16 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const ui
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         const float wy1 = y_w1[q];
         if (wy1 >= 0.f) {
-            const uint16_t* r0 = stage + (size_t)y_slot0[q] * wp;
-            const uint16_t* r1 = stage + (size_t)y_slot1[q] * wp;
-            const float wy0 = 1.f - wy1;
+            const Taps<2> ty = {{y_slot0[q], y_slot1[q]}, {1.f - wy1, wy1}};          // rows as staging slots
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const XTap t = xtab[x4 + e];
                 if (t.w1 < 0.f) continue;
-                const int s0 = t.s01 & 0xffffu, s1 = t.s01 >> 16;
-                if (identity) {
-                    v[e] = (float)(int)r0[s0];
-                } else {
-                    const float wx0 = 1.f - t.w1;
-                    const double a0 = (double)(int)r0[s0] * (double)wx0 + (double)(int)r0[s1] * (double)t.w1;
-                    const double a1 = (double)(int)r1[s0] * (double)wx0 + (double)(int)r1[s1] * (double)t.w1;
-                    v[e] = (float)(a0 * (double)wy0 + a1 * (double)wy1);
-                }
+                const Taps<2> tx = {{(int)(t.s01 & 0xffffu), (int)(t.s01 >> 16)}, {1.f - t.w1, t.w1}};
+                if (identity)
+                    v[e] = (float)(int)stage[(size_t)ty.s[0] * wp + tx.s[0]];
+                else
+                    v[e] = resample<2>([stage, wp](int y) { return stage + (size_t)y * wp; }, tx, ty);
             }
         }
         dst[i] = make_float4(v[0], v[1], v[2], v[3]);
@@ -311,17 +254,17 @@ int frames_band_rows(int W, int Wc) {
 extern "C" int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int B, int Tm, int nbins, int H, int W, int Hc,
                                           int Wc, float* out, eas_stream_t stream) {
     if (!hist || !out || B < 0 || Tm < 1 || nbins < 1 || H < 1 || W < 1 || Hc < H || Wc < W) return EAS_ERR_INVALID_ARG;
-    if (Wc % 16 != 0 || nbins > 255) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32
-    if (((uintptr_t)hist | (uintptr_t)out) & 15) return EAS_ERR_INVALID_ARG;
+    if (Wc % 16 != 0 || nbins > 255) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32; a bin sum is 16 bits
+    if ((((uintptr_t)hist | (uintptr_t)out) & 15) || ((uintptr_t)n_valid & 3)) return EAS_ERR_INVALID_ARG;
     if (B == 0) return EAS_OK;
     const int64_t groups = (int64_t)B * Tm * 2 * Hc * (Wc / 16);
     const int grid = eas_grid_1d(groups, EAS_BLOCK, 1 << 20);
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
     if (nbins == 10)
-        EAS_LAUNCH((stacked_hist_sum_kernel<10>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, n_valid, Tm, nbins, H, W, Hc, Wc, out, groups);
+        EAS_LAUNCH((stacked_hist_sum_kernel<10>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, n_valid, B, Tm, nbins, H, W, Hc, Wc, out, groups);
     else
-        EAS_LAUNCH((stacked_hist_sum_kernel<0>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, n_valid, Tm, nbins, H, W, Hc, Wc, out, groups);
+        EAS_LAUNCH((stacked_hist_sum_kernel<0>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, n_valid, B, Tm, nbins, H, W, Hc, Wc, out, groups);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -125,6 +125,14 @@ def letterbox_params(ih, iw, h, w, letterbox=True, center=False):
     return nw, nh, dx, dy, 0
 
 
+def params_on(params, device):
+    """per-sample (nw, nh, dx, dy, flip) rows -- a tensor, or anything numpy reads -- as the int32 [B, 5] tensor on ``device`` that the
+    kernels take; a tensor that is there already is returned as it is (nothing is read back: graph-capturable)"""
+    if not torch.is_tensor(params):
+        params = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5))
+    return params.to(device)
+
+
 def jitter_params(ih, iw, h, w, jitter=.3, rng=np.random):
     """(nw, nh, dx, dy, flip) of the random branch of get_random_data (gen1.py:485-504).  Six uniform draws from ``rng`` in the
     reference's order: two for the aspect-ratio distortion (numerator, denominator, each in [1-jitter, 1+jitter)), the scale in
@@ -225,9 +233,7 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
         Tl, Tm, (H, W), (Hc, Wc) = e.Tl, e.Tm, getattr(e, 'img_size', (180, 240)), e.input_size
         window = (e.window * 1000, 0) if getattr(e, 'window', None) is not None else None
     counts = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
-    if not torch.is_tensor(params):
-        params = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5)).to(counts.device)
-    return ops.counts_letterbox(counts, params, Hc, Wc, interp=interp)
+    return ops.counts_letterbox(counts, params_on(params, counts.device), Hc, Wc, interp=interp)
 
 
 # ------------------------------------------------------------------------------------------------ 1 Mpx (RVT stacked histograms)
@@ -277,9 +283,7 @@ def rvt_to_frames(store, first, exp_or_dims, params, lo=None):
         nbins = exp_or_dims[2] if len(exp_or_dims) > 2 else 10
     else:
         Tm, (Hc, Wc), nbins = exp_or_dims.Tm, exp_or_dims.input_size, getattr(exp_or_dims, 'nbins', 10)
-    if params is not None and not torch.is_tensor(params):
-        params = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5)).to(store.device)
-    return ops.stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=nbins, lo=lo, params=params)
+    return ops.stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=nbins, lo=lo, params=None if params is None else params_on(params, store.device))
 
 
 class SyntheticStackedHistLoader:
@@ -365,5 +369,4 @@ def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params):
     (nw, nh, dx, dy, flip) rows."""
     H, W = sensor_hw
     counts = ops.event_histogram(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W)
-    par = torch.as_tensor(np.asarray(params, dtype=np.int32).reshape(-1, 5)).to(counts.device)
-    return ops.counts_letterbox(counts, par, canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+    return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)

@@ -173,16 +173,12 @@ def counts_letterbox(counts, params, Hc, Wc, interp='linear'):
     (nw, nh, dx, dy, flip) (see data.letterbox_params / jitter_params)."""
     _dev(counts, params)
     assert counts.dtype == torch.int32 and params.dtype == torch.int32 and params.shape == (counts.shape[0], 5)
-    assert interp in ('linear', 'cubic')
     counts, params = counts.contiguous(), params.contiguous()
     B, (H, W) = counts.shape[0], counts.shape[-2:]
     F = counts.numel() // (B * H * W)
     out = torch.empty(counts.shape[:-2] + (Hc, Wc), dtype=torch.float32, device=counts.device)
-    if interp == 'linear':
-        check(_lib.lib().eas_counts_letterbox(ptr(counts), ptr(params), B, F, H, W, Hc, Wc, ptr(out), stream()), 'eas_counts_letterbox')
-    else:
-        check(_lib.lib().eas_counts_letterbox_ex(ptr(counts), ptr(params), 1, B, F, H, W, Hc, Wc, ptr(out), stream()),
-              'eas_counts_letterbox_ex')
+    check(_lib.lib().eas_counts_letterbox_ex(ptr(counts), ptr(params), ('linear', 'cubic').index(interp), B, F, H, W, Hc, Wc, ptr(out), stream()),
+          'eas_counts_letterbox_ex')
     return out
 
 

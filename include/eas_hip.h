@@ -170,7 +170,9 @@ int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, i
  * representations exist) followed by the validation letterbox at scale 1 = zero padding to the canvas (rvt_gen4.py:516-533).
  * hist: u8 [B][Tm][2*nbins][H][W] (channel = polarity*nbins + bin); n_valid (nullable, int32 [B]): sample b supplies
  * only its first n_valid[b] slices, which become the LAST n_valid[b] output slices.  out: fp32 [B][Tm][2][Hc][Wc]
- * (the model input [B][Tl=1][Tm][2][Hc][Wc]), Hc >= H, Wc >= W, Wc % 16 == 0.  Integer sums (<= 255*nbins): bit-exact. */
+ * (the model input [B][Tl=1][Tm][2][Hc][Wc]), Hc >= H, Wc >= W, Wc % 16 == 0.  Integer sums (<= 255*nbins): bit-exact.
+ * n_valid[b] is device data: it is clamped into [0, Tm], so no slice of a neighbouring sample and nothing behind the buffer is ever
+ * read.  EAS_ERR_UNSUPPORTED for Wc % 16 != 0 or nbins > 255 (a bin sum is held in 16 bits); B == 0 returns EAS_OK. */
 int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int B, int Tm, int nbins, int H, int W, int Hc,
                                int Wc, float* out, eas_stream_t stream);
 /* The 1 Mpx TRAINING input: what RVTGEN4Dataset.__getitem__ does for a sample (rvt_gen4.py:190-235), from indices into a store of

@@ -141,15 +141,40 @@ def gen4(args):
              ('composition, letterbox row', lambda: composition(letter), n_in + 16 * n_mid + 4 * n_out),
              ('composition, scale 0.4 row', lambda: composition(small), n_in + 16 * n_mid + 4 * n_out),
              ('event_sum alone (config 4 today)', lambda: ops.stacked_hist_event_sum(gathered, Hc, Wc), n_in + 4 * n_out)]
+    print(f'B={B} Tm={Tm} {H}x{W} -> {Hc}x{Wc}')
+    alternate(forms)
+
+
+def letterbox(args):
+    """``counts_letterbox`` at the two shapes the front ends run it at: linear at workload 2b's (Gen1, batch 32, Tm = 4, 240 x 304 -> 640 x 640,
+    the deterministic letterbox row) and cubic at N-Caltech101's (scripts/dev_atis.py: batch 64, Tl = 1, Tm = 8, 180 x 240 -> 192 x 256).
+    GB/s = the int32 counts once + the fp32 frames once over the time."""
+    dev = torch.device('cuda:0')
+    from eas_snn_amd import data, workloads
+    forms = []
+    w = workloads.WORKLOADS['2b']
+    for name, interp, B, F, (H, W), (Hc, Wc) in (('linear, workload 2b', 'linear', w['batch'], 2 * w['Tm'], w['sensor'], w['canvas']),
+                                                 ('cubic, N-Caltech101', 'cubic', 64, 16, (180, 240), (192, 256))):
+        counts = torch.poisson(torch.full((B, F, H, W), 0.6, device=dev)).to(torch.int32)
+        par = torch.tensor([data.letterbox_params(H, W, Hc, Wc)] * B, dtype=torch.int32, device=dev)
+        forms.append((f'{name} {B}x{F} {H}x{W} -> {Hc}x{Wc}', lambda c=counts, q=par, i=interp, hw=(Hc, Wc): ops.counts_letterbox(c, q, *hw, interp=i),
+                      4 * B * F * (H * W + Hc * Wc)))
+    alternate(forms)
+
+
+def alternate(forms):
+    """5 rounds, the forms (name, fn, algorithmic bytes) alternating inside every round, 20 timed calls each: the median of the round medians,
+    their spread (for a comparison of two libraries in one session: scripts/build_variant.sh, EAS_LIB), min..max over all calls"""
     rounds = [[] for _ in forms]
     for _ in range(5):
         for k, (_, fn, _) in enumerate(forms):
             rounds[k].append(timeit_spread(fn, reps=20, warm=3))
-    print(f'B={B} Tm={Tm} {H}x{W} -> {Hc}x{Wc}; ms = median of 5 rounds of (median of 20), (min..max over all)')
+    print('ms = median of 5 rounds of (median of 20) [smallest..largest round median] (min..max over all)')
     for (name, _, nbytes), r in zip(forms, rounds):
-        med = sorted(x[0] for x in r)[len(r) // 2]
-        print(f'{name:34s}: {med:7.3f} ms ({min(x[1] for x in r):.3f}..{max(x[2] for x in r):.3f})  {nbytes / 1e6:7.1f} MB  {nbytes / med / 1e6:7.0f} GB/s',
-              flush=True)
+        meds = sorted(x[0] for x in r)
+        med = meds[len(r) // 2]
+        print(f'{name:34s}: {med:7.4f} ms [{meds[0]:.4f}..{meds[-1]:.4f}] ({min(x[1] for x in r):.3f}..{max(x[2] for x in r):.3f})  {nbytes / 1e6:7.1f} MB'
+              f'  {nbytes / med / 1e6:7.0f} GB/s', flush=True)
 
 
 if __name__ == '__main__':
@@ -160,3 +185,5 @@ if __name__ == '__main__':
         dwconv(sys.argv[2:])
     elif what == 'gen4':
         gen4(sys.argv[2:])
+    elif what == 'letterbox':
+        letterbox(sys.argv[2:])

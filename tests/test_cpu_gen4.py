@@ -67,6 +67,25 @@ def test_bad_arguments_are_refused_before_any_launch():
     assert call(store=None, Wc=40) == INVALID                                                              # bad arguments first
 
 
+def test_event_sum_refuses_bad_arguments_before_any_launch():
+    """every call below returns from the argument checks of ``eas_stacked_hist_event_sum``: no device is touched (the pointers are made-up
+    addresses)"""
+    fn = eas_snn_amd.hip_library().eas_stacked_hist_event_sum
+    good = dict(hist=0x10000, n_valid=0x20000, B=2, Tm=3, nbins=10, H=18, W=32, Hc=32, Wc=48, out=0x50000)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(a['hist'], a['n_valid'], a['B'], a['Tm'], a['nbins'], a['H'], a['W'], a['Hc'], a['Wc'], a['out'], None)
+    for kw in (dict(hist=None), dict(out=None), dict(hist=0x10001), dict(out=0x50004), dict(n_valid=0x20002),
+               dict(Hc=17), dict(Wc=16), dict(W=40, Wc=32), dict(B=-1), dict(Tm=0), dict(nbins=0), dict(H=0), dict(W=0)):
+        assert call(**kw) == INVALID, kw
+    for kw in (dict(Wc=40), dict(nbins=256)):
+        assert call(**kw) == UNSUPPORTED, kw
+        assert call(B=0, **kw) == UNSUPPORTED, kw                                                          # limits before the empty batch
+    assert call(hist=None, Wc=40) == INVALID                                                               # bad arguments first
+    assert call(B=0) == 0 and call(B=0, n_valid=None) == 0                                                  # an empty batch is no work
+
+
 def test_cpu_tensors_raise():
     import torch
     with pytest.raises(eas_snn_amd._lib.EasHipError):

@@ -176,6 +176,24 @@ def test_same_as_the_two_existing_kernels(dev):
     assert torch.equal(plain[:2], got[:2])                                  # the letterbox row and the identity are params None
 
 
+def test_bands_shorter_than_eight_rows(dev):
+    """a 1280-pixel sensor: 8 output rows per block (16 staged rows + the column table) do not fit the kernel's 48 KiB of LDS, bands are 4
+    rows; the 11-row canvas takes three, the last one of 3 rows.  Both entry points."""
+    from oracle import events_ref
+    assert 2 * 8 * 1280 * 2 + 1280 * 8 > 48 * 1024 >= 2 * 4 * 1280 * 2 + 1280 * 8
+    store = np.random.default_rng(12).integers(0, 256, (2, 6, 10, 1280), dtype=np.uint8)
+    Hc, Wc = 11, 1280
+    for rows in (None, [(900, 7, 100, 2, 1), (1280, 10, 0, 0, 0)], [(1100, 9, 700, 5, 0), (640, 5, -300, -2, 1)]):
+        want, _ = gen4_ref.frames(store, [0, 1], 1, Hc, Wc, nbins=3, params=rows)
+        out, flags = run(dev, store, [0, 1], 1, Hc, Wc, 3, params=rows)
+        assert np.array_equal(out, want) and out[0].any() and out[1].any() and not flags.any(), rows
+    got = ops.stacked_hist_event_sum(torch.from_numpy(store).to(dev).view(2, 1, 6, 10, 1280), Hc, Wc, nbins=3).cpu().numpy()
+    for b in range(2):
+        want = events_ref.pad_to_canvas(events_ref.stacked_hist_event_sum(store[b:b + 1], 1, 10, 1280), Hc, Wc)
+        assert np.array_equal(got[b].astype(np.float64), want)
+    assert got[..., :10, :].any() and not got[..., 10:, :].any()
+
+
 def small_exp():
     return types.SimpleNamespace(Tm=3, input_size=(32, 48), num_classes=3)
 

@@ -364,6 +364,36 @@ def test_stacked_hist_event_sum_full_size_vs_oracle(dev):
         ops.stacked_hist_event_sum(hist, Hc, Wc)                 # CPU tensor: no fallback
 
 
+@pytest.mark.parametrize('W,nbins', [(32, 10), (30, 10), (32, 3)], ids=['w32', 'w30_bytes', 'bins3_generic'])
+def test_stacked_hist_event_sum_n_valid_is_clamped(dev, W, nbins):
+    """n_valid is device data: values outside [0, Tm] mean 0 and Tm -- no slice of the neighbouring sample, nothing past the buffer is
+    read.  Vector path, byte path (W % 16 != 0) and a run-time bin count, against the oracle."""
+    from eas_snn_amd import ops
+    from oracle import events_ref
+    B, Tm, H, Hc, Wc = 4, 3, 18, 32, 48
+    hist = np.random.default_rng(W + nbins).integers(0, 256, (B, Tm, 2 * nbins, H, W), dtype=np.uint8)
+    clamped = [0, 0, 3, 3]
+
+    def run(h, nv):
+        return ops.stacked_hist_event_sum(_t(h, dev), Hc, Wc, nbins=nbins, n_valid=torch.tensor(nv, dtype=torch.int32, device=dev)).cpu().numpy()
+
+    def oracle(valid):          # (the reference never sees a sample without a representation: its zero slices are written out here)
+        return np.stack([events_ref.pad_to_canvas(events_ref.stacked_hist_event_sum(hist[b, :n], Tm, H, W), Hc, Wc) if n else
+                         np.zeros((1, Tm, 2, Hc, Wc)) for b, n in enumerate(valid)])
+    want = oracle(clamped)
+    base = run(hist, clamped)
+    assert base.shape == (B, 1, Tm, 2, Hc, Wc) and np.array_equal(base.astype(np.float64), want)
+    assert not base[:2].any() and all(base[b, 0, j].any() for b in (2, 3) for j in range(Tm))
+    got = run(hist, [-3, 0, 3, 8])
+    assert np.array_equal(got, base)
+    # slots behind n_valid hold a sentinel: the result does not move
+    marked = hist.copy()
+    nv = [-3, 1, 2, 8]
+    for b, n in enumerate([0, 1, 2, 3]):
+        marked[b, n:] = 201
+    assert np.array_equal(run(marked, nv).astype(np.float64), oracle([0, 1, 2, 3]))
+
+
 def test_event_histogram_out_of_range_is_counted(dev):
     from eas_snn_amd import ops
     t = torch.arange(100, 200, dtype=torch.int32, device=dev).view(torch.uint32)
