@@ -578,8 +578,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_surface_exp_kernel(const uint3
 // ncaltech.py:98-105): every frame of sample b is resized to (nw, nh) with the cv2.resize semantics of ``Rule`` (LinearRule: INTER_LINEAR,
 // CubicRule: INTER_CUBIC), pasted at (dx, dy) into a zero canvas, optionally mirrored left-right, and cast to fp32 (trainer.py:99).  The
 // paste rule, the tap rules and the tap-weighted sum live in count_resize.h: eas_stacked_hist_frames resizes with the same ones.
-template <typename Rule>
-__global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ params,
+// ``Src``: int32 counts, or the float64 frames of a weighted measure (eas_frames_letterbox_f64: cv2.resize sees float64 images either way).
+template <typename Rule, typename Src>
+__global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const Src* __restrict__ counts, const int32_t* __restrict__ params,
                                                                      int B, int F, int H, int W, int Hc, int Wc, float* __restrict__ out) {
     const int64_t total = (int64_t)B * F * Hc * Wc;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -591,7 +592,7 @@ __global__ __launch_bounds__(EAS_BLOCK) void counts_letterbox_kernel(const int32
         const int xs = paste.src_col(xx, Wc), ys = paste.src_row(yy);
         float v = 0.f;
         if (paste.inside(xs, ys)) {
-            const int32_t* src = counts + f * H * W;
+            const Src* src = counts + f * H * W;
             if (paste.identity(W, H))
                 v = (float)src[ys * W + xs];
             else
@@ -822,18 +823,34 @@ int eas_event_time_surface(const uint32_t* t, const uint16_t* x, const uint16_t*
     return EAS_OK;
 }
 
-int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+}  // extern "C"
+
+// the letterbox of int32 counts and of float64 frames: one argument rule, one launch
+template <typename Src>
+static int letterbox_launch(const Src* frames, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
                             eas_stream_t stream) {
     if (interp != 0 && interp != 1) return EAS_ERR_INVALID_ARG;
-    if (!counts || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
+    if (!frames || !params || !out || B < 1 || F < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
     const dim3 grid(eas_grid_1d((int64_t)B * F * Hc * Wc));
     EAS_CLEAR_ERR();
     if (interp == 0)
-        EAS_LAUNCH(counts_letterbox_kernel<LinearRule>, grid, dim3(EAS_BLOCK), 0, eas_s(stream), counts, params, B, F, H, W, Hc, Wc, out);
+        EAS_LAUNCH((counts_letterbox_kernel<LinearRule, Src>), grid, dim3(EAS_BLOCK), 0, eas_s(stream), frames, params, B, F, H, W, Hc, Wc, out);
     else
-        EAS_LAUNCH(counts_letterbox_kernel<CubicRule>, grid, dim3(EAS_BLOCK), 0, eas_s(stream), counts, params, B, F, H, W, Hc, Wc, out);
+        EAS_LAUNCH((counts_letterbox_kernel<CubicRule, Src>), grid, dim3(EAS_BLOCK), 0, eas_s(stream), frames, params, B, F, H, W, Hc, Wc, out);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
+}
+
+extern "C" {
+
+int eas_counts_letterbox_ex(const int32_t* counts, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                            eas_stream_t stream) {
+    return letterbox_launch(counts, params, interp, B, F, H, W, Hc, Wc, out, stream);
+}
+
+int eas_frames_letterbox_f64(const double* frames, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                             eas_stream_t stream) {
+    return letterbox_launch(frames, params, interp, B, F, H, W, Hc, Wc, out, stream);
 }
 
 int eas_counts_letterbox(const int32_t* counts, const int32_t* params, int B, int F, int H, int W, int Hc, int Wc, float* out,

@@ -1,9 +1,10 @@
-// N-Caltech101 front end: raw ATIS recordings (5 bytes per record) -> per-polarity count frames int32 [B][Tl][Tm][2][H][W].
-// Reference: NCaltech.read_ATIS, generate_slices and agrregate('micro_sum') with measure='count', overlap=0
-// (yolox/data/datasets/ncaltech.py:63-96, 179-183, 227-237, 264-269, 368-379).
+// N-Caltech101 front end: raw ATIS recordings (5 bytes per record) -> per-polarity frames [B][Tl][Tm][2][H][W]: int32 counts
+// (eas_event_histogram_atis, measure='count') or float64 time-surface-weighted sums (eas_event_timesurface_atis, measure='timesurface').
+// Reference: NCaltech.read_ATIS, generate_slices and agrregate('micro_sum') with overlap=0
+// (yolox/data/datasets/ncaltech.py:63-96, 179-183, 218-237, 264-269, 368-379; yolox/utils/event_reps.py:9-19).
 //   record b0..b4: x = b0, y = b1, p = b2 >> 7, raw = (b2 & 127) << 16 | b3 << 8 | b4;  y == 240 is an overflow record: no event, it adds
 //   8192 to the time of every later record of its recording, so t = raw + 8192 * (overflow records at or before the record).
-// Five launches, no allocation, no host read (graph-capturable):
+// Five launches (six for the time surface), no allocation, no host read (graph-capturable):
 //   0. atis_zero_kernel             the frames
 //   1. atis_overflow_count_kernel  overflow records per chunk of kChunk records of the whole buffer (reads the y byte of every record)
 //   2. atis_overflow_scan_kernel    exclusive scan of the chunk counts, in place (one block)
@@ -12,8 +13,16 @@
 //                                   count - the recording's own base)) -> one AtisHead per recording, one AtisSlice per macro slice
 //   4. atis_hist_kernel             blocks stride over the chunks of a recording: decode in registers, block scan of the overflow
 //                                   records of the chunk, window / macro slice / micro slice (the SampleWin rule of events.hip bin_one),
-//                                   int32 atomics -- bit-exact in any order
-// Algorithmic bytes per recording: 5 * nrec + 4 * Tl * Tm * 2 * H * W; the records are read twice (launches 1 and 4), the plan's probes
+//                                   integer atomics -- bit-exact in any order.  The accumulate step is the kernel's template
+//                                   parameter, the only difference between the two measures: CountAcc adds 1 to an int32 bin,
+//                                   TimeSurfaceAcc adds llrint(w * 2^48), w = 1 - tanh((t_target - t) / tau) in fp64 with t_target =
+//                                   the time of the macro slice's last member event (a plan row), to a 64-bit bin
+//   5. atis_ts_finish_kernel        (time surface only) the 64-bit sums, in place, -> double * 2^-48
+// Time-surface sums are integers, so the frames do not depend on the order of the adds: bit-identical run to run, for any grid and any
+// neighbours in the buffer.  Each event is off by <= 2^-49 (the rounding of w * 2^48) + the error of tanh; a bin holds 65 535 events of
+// weight 1 (kTsCapacity): a macro slice of more records than that sets flag bit 2 (conservative: the records of ONE pixel would have to).
+// Algorithmic bytes per recording: 5 * nrec + 4 * Tl * Tm * 2 * H * W (time surface: 8 * ..., and the finishing pass reads and writes them
+// once more); the records are read twice (launches 1 and 4), the plan's probes
 // re-read O(Tl * log nrec) chunks.
 // The chunks are chunks of the BUFFER (record index / kChunk), not of a recording: the overflow count of a record inside recording
 // [a, e) is prefix(i) - prefix(a - 1), so recordings need no chunk tables of their own.
@@ -28,6 +37,8 @@ constexpr int kChunkShift = 8;
 constexpr uint32_t kOverflowY = 240;
 constexpr uint32_t kTimeIncrement = 8192;   // the reference's 2 ** 13, kept as it is
 constexpr int kScanThreads = 1024;
+constexpr double kTsOne = 281474976710656.0;            // 2^48: a time-surface weight of 1 in a 64-bit bin
+constexpr int64_t kTsCapacity = 65535;                  // weights of 1 an unsigned 64-bit bin holds: floor((2^64 - 1) / 2^48)
 
 struct AtisHead {                       // per recording
     int64_t wl, wh;                     // events with wl < t <= wh remain (no window: INT64_MIN, INT64_MAX)
@@ -139,7 +150,8 @@ __device__ __forceinline__ int64_t lower_bound_events(const AtisRec& R, int64_t 
 __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
                                                              const uint32_t* __restrict__ chunk_base, int64_t window_lo, int64_t window_hi,
                                                              int Tl, int Tm, AtisHead* __restrict__ heads, AtisSlice* __restrict__ slices,
-                                                             uint32_t* __restrict__ oob, uint32_t* __restrict__ flags) {
+                                                             uint32_t* __restrict__ t_target, uint32_t* __restrict__ oob,
+                                                             uint32_t* __restrict__ flags) {
     const int b = blockIdx.x;
     const bool writer = threadIdx.x == 0;
     int64_t a, e;
@@ -173,6 +185,7 @@ __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __re
     int64_t start = ia;
     for (int k = 0; k < Tl; ++k) {
         AtisSlice s = {0u, 0u};
+        uint32_t target = 0u;                               // time of the slice's last member event (the time surface's t_target)
         bool members = false;
         if (h.mw > 0) {
             const int64_t end = lower_bound_events(R, start, ib, h.t0 + (int64_t)(k + 1) * h.mw);
@@ -182,11 +195,16 @@ __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __re
                 const int64_t f = R.time(fe), l = R.time(prev_event(rec, end - 1, start));
                 s.f = (uint32_t)f;
                 s.w = l > f ? (uint32_t)((l - f) / Tm) : 0u;
+                target = (uint32_t)l;
+                if (t_target && end - start > kTsCapacity) flag |= 4u;     // more records than one 64-bit bin holds at weight 1
             }
             start = end;
         }
         if (!members) flag |= 2u;
-        if (writer) rows[k] = s;
+        if (writer) {
+            rows[k] = s;
+            if (t_target) t_target[(int64_t)b * Tl + k] = target;
+        }
     }
     if (writer) {
         heads[b] = h;
@@ -208,10 +226,28 @@ __device__ __forceinline__ uint64_t load_record(const uint8_t* __restrict__ rec,
     return (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24) | ((uint64_t)p[4] << 32);
 }
 
+// ---- the accumulate step of the histogram: what an event of time t in macro slice `row` (= b * Tl + k) adds to its bin
+struct CountAcc {                       // measure 'count': 1
+    typedef int32_t Bin;
+    __device__ __forceinline__ void operator()(Bin* bin, int64_t, uint32_t) const { atomicAdd(bin, 1); }
+};
+struct TimeSurfaceAcc {                 // measure 'timesurface' (decay 'tanh'): 1 - tanh((t_target - t) / tau) in units of 2^-48
+    typedef unsigned long long Bin;
+    const uint32_t* t_target;           // [B * Tl], written by the plan
+    double tau;
+    __device__ __forceinline__ void operator()(Bin* bin, int64_t row, uint32_t t) const {
+        // t <= t_target for every member of the slice (ascending times); the signed difference keeps w in [0, 2] whatever the records say
+        const double w = 1.0 - tanh((double)((int64_t)t_target[row] - (int64_t)t) / tau);
+        atomicAdd(bin, (Bin)llrint(w * kTsOne));
+    }
+};
+
+template <typename Acc>
 __global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
                                                            const uint32_t* __restrict__ chunk_base, const AtisHead* __restrict__ heads,
                                                            const AtisSlice* __restrict__ slices, int Tl, int Tm, int H, int W,
-                                                           int32_t* __restrict__ out, uint32_t* __restrict__ oob, uint32_t* __restrict__ flags) {
+                                                           typename Acc::Bin* __restrict__ out, uint32_t* __restrict__ oob,
+                                                           uint32_t* __restrict__ flags, const Acc acc) {
     __shared__ uint32_t wave_total[kChunk / EAS_WAVE];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & (EAS_WAVE - 1), wid = tid / EAS_WAVE;
     int64_t a, e;
@@ -253,7 +289,8 @@ __global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __rest
             continue;
         }
         const int ch = (b2 >> 7) != 0 ? 1 : 0;
-        atomicAdd(out + (((((int64_t)b * Tl + k) * Tm + q) * 2 + ch) * H + yy) * W + xx, 1);
+        const int64_t row = (int64_t)b * Tl + k;
+        acc(out + (((row * Tm + q) * 2 + ch) * H + yy) * W + xx, row, t);
     }
 }
 
@@ -268,37 +305,43 @@ __global__ __launch_bounds__(EAS_BLOCK) void atis_zero_kernel(int32_t* __restric
     }
 }
 
+// the time surface's finishing pass, in place: a bin's integer sum (units of 2^-48) -> the double the frame holds
+__global__ __launch_bounds__(EAS_BLOCK) void atis_ts_finish_kernel(unsigned long long* __restrict__ bins, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        bins[i] = __builtin_bit_cast(unsigned long long, (double)bins[i] * (1.0 / kTsOne));
+}
+
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t chunks_of(int64_t nrec) { return (nrec + kChunk - 1) / kChunk; }
 
-}  // namespace
+// the workspace of a call: chunk counts / bases, one head per recording, one row per (recording, macro slice), and -- behind what the
+// count entry uses -- the time surface's t_target rows
+struct AtisWorkspace {
+    int64_t heads, slices, t_target, count_bytes, ts_bytes;          // byte offsets and the two totals
+    AtisWorkspace(int64_t nrec, int B, int Tl) {
+        heads = align16((chunks_of(nrec) + 1) * (int64_t)sizeof(uint32_t));
+        slices = heads + align16((int64_t)B * sizeof(AtisHead));
+        t_target = count_bytes = slices + align16((int64_t)B * Tl * sizeof(AtisSlice));
+        ts_bytes = t_target + align16((int64_t)B * Tl * sizeof(uint32_t));
+    }
+};
 
-extern "C" {
-
-int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
-    if (nrec < 0 || B < 1 || Tl < 1) return 0;
-    return align16((chunks_of(nrec) + 1) * (int64_t)sizeof(uint32_t)) + align16((int64_t)B * sizeof(AtisHead)) +
-           align16((int64_t)B * Tl * sizeof(AtisSlice));
-}
-
-int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
-                             int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
-                             eas_stream_t stream) {
-    if (!out || !sample_offsets || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
-    if ((nrec > 0 && !records) || ((uintptr_t)workspace & 15) || nrec > (INT64_MAX >> 3)) return EAS_ERR_INVALID_ARG;
-    if ((int64_t)B * Tl >= (1 << 24) || B > 65535) return EAS_ERR_UNSUPPORTED;
+// The launches of both entry points (arguments checked by the caller).  t_target: NULL for the count measure.
+template <typename Acc>
+int atis_frames(const uint8_t* rec, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
+                int H, int W, typename Acc::Bin* out, uint32_t* oob_count, uint32_t* flags, void* workspace, uint32_t* t_target, const Acc& acc,
+                hipStream_t st) {
     const int64_t far = (int64_t)1 << 40;                  // decoded times fit 32 bits: a bound beyond +-2^40 selects what 2^40 selects
     window_lo = window_lo < -far ? -far : window_lo;
     window_hi = window_hi > far ? far : (window_hi < -far ? -far : window_hi);
-    hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
-    const uint8_t* rec = (const uint8_t*)records;
     const int64_t nchunks = chunks_of(nrec);
+    const AtisWorkspace ws(nrec, B, Tl);
     uint32_t* chunk_base = (uint32_t*)workspace;
-    AtisHead* heads = (AtisHead*)((char*)workspace + align16((nchunks + 1) * (int64_t)sizeof(uint32_t)));
-    AtisSlice* slices = (AtisSlice*)((char*)heads + align16((int64_t)B * sizeof(AtisHead)));
-    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W;
-    EAS_LAUNCH(atis_zero_kernel, dim3(eas_grid_1d((nout + 3) / 4)), dim3(EAS_BLOCK), 0, st, out, nout);
+    AtisHead* heads = (AtisHead*)((char*)workspace + ws.heads);
+    AtisSlice* slices = (AtisSlice*)((char*)workspace + ws.slices);
+    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W, nwords = nout * (int64_t)(sizeof(typename Acc::Bin) / sizeof(int32_t));
+    EAS_LAUNCH(atis_zero_kernel, dim3(eas_grid_1d((nwords + 3) / 4)), dim3(EAS_BLOCK), 0, st, (int32_t*)out, nwords);
     EAS_CHECK_LAUNCH();
     if (nchunks > 0) {
         EAS_LAUNCH(atis_overflow_count_kernel, dim3(eas_grid_1d(nchunks, 1)), dim3(kChunk), 0, st, rec, nrec, nchunks, chunk_base);
@@ -307,16 +350,68 @@ int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* s
         EAS_CHECK_LAUNCH();
     }
     EAS_LAUNCH(atis_plan_kernel, dim3(B), dim3(EAS_WAVE), 0, st, rec, nrec, sample_offsets, chunk_base, window_lo, window_hi, Tl, Tm, heads, slices,
-               oob_count, flags);
+               t_target, oob_count, flags);
     EAS_CHECK_LAUNCH();
     if (nchunks > 0) {
         // the recordings' lengths live on the device: a fixed number of blocks per recording strides over whatever it holds
         int64_t per = nchunks / B + 1;
         if (per > 64) per = 64;
-        EAS_LAUNCH(atis_hist_kernel, dim3((unsigned)per, B), dim3(kChunk), 0, st, rec, nrec, sample_offsets, chunk_base, heads, slices, Tl, Tm, H, W,
-                   out, oob_count, flags);
+        EAS_LAUNCH(atis_hist_kernel<Acc>, dim3((unsigned)per, B), dim3(kChunk), 0, st, rec, nrec, sample_offsets, chunk_base, heads, slices, Tl, Tm,
+                   H, W, out, oob_count, flags, acc);
         EAS_CHECK_LAUNCH();
     }
+    return EAS_OK;
+}
+
+// the argument rules the two entry points share
+int atis_check_args(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int Tl, int Tm, int H, int W, const void* out,
+                    const void* workspace) {
+    if (!out || !sample_offsets || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
+    if ((nrec > 0 && !records) || ((uintptr_t)workspace & 15) || nrec > (INT64_MAX >> 3)) return EAS_ERR_INVALID_ARG;
+    if ((int64_t)B * Tl >= (1 << 24) || B > 65535) return EAS_ERR_UNSUPPORTED;
+    return EAS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
+    if (nrec < 0 || B < 1 || Tl < 1) return 0;
+    return AtisWorkspace(nrec, B, Tl).count_bytes;
+}
+
+int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                             int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                             eas_stream_t stream) {
+    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
+    if (rc != EAS_OK) return rc;
+    return atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace,
+                       nullptr, CountAcc{}, eas_s(stream));
+}
+
+int64_t eas_event_timesurface_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
+    if (nrec < 0 || B < 1 || Tl < 1) return 0;
+    return AtisWorkspace(nrec, B, Tl).ts_bytes;
+}
+
+int64_t eas_event_timesurface_atis_capacity(void) { return kTsCapacity; }
+
+int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                               int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                               eas_stream_t stream) {
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
+    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
+    if (rc != EAS_OK) return rc;
+    hipStream_t st = eas_s(stream);
+    uint32_t* t_target = (uint32_t*)((char*)workspace + AtisWorkspace(nrec, B, Tl).t_target);
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    const int launched = atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, bins, oob_count, flags,
+                                     workspace, t_target, TimeSurfaceAcc{t_target, tau}, st);
+    if (launched != EAS_OK) return launched;
+    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W;
+    EAS_LAUNCH(atis_ts_finish_kernel, dim3(eas_grid_1d(nout)), dim3(EAS_BLOCK), 0, st, bins, nout);
+    EAS_CHECK_LAUNCH();
     return EAS_OK;
 }
 

@@ -217,9 +217,14 @@ def synth_atis_batch(batch, n_events, height=180, width=240, span_us=300_000, se
     return np.concatenate(parts), np.asarray(off, dtype=np.int64)
 
 
-def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'):
+ATIS_MEASURES = ('count', 'timesurface')
+
+
+def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic', measure=None, tau=500e3):
     """Raw ATIS recordings in HBM -> model input [B, Tl, Tm, 2, Hc, Wc] fp32: ``ops.event_histogram_atis`` then ``ops.counts_letterbox``,
-    nothing read back in between (graph-capturable).  ``exp_or_dims``: an experiment (fields ``Tl``, ``Tm``, ``input_size``, optionally
+    nothing read back in between (graph-capturable).  ``measure`` (None: the experiment's ``measure`` field, ``'count'`` without one):
+    ``'count'``, or ``'timesurface'`` = ``ops.event_timesurface_atis`` with ``tau`` (us) then ``ops.frames_letterbox``, the reference's
+    ``measure timesurface`` (NCaltech.get_measure_func, ncaltech.py:218-225); anything else raises ValueError.  ``exp_or_dims``: an experiment (fields ``Tl``, ``Tm``, ``input_size``, optionally
     ``img_size`` -- the sensor, default (180, 240) -- and ``window`` in ms, as yolox/exp/event_yolox_base.py passes it: ``(window * 1000, 0)``) or a tuple
     ``(Tl, Tm, (H, W), (Hc, Wc))`` with an optional fifth element ``window`` = (lo, hi) in us.  ``params``: per-sample
     (nw, nh, dx, dy, flip) rows, a device int32 tensor or anything numpy reads.  N-Caltech101 resizes every sample, in evaluation too:
@@ -232,6 +237,14 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
         e = exp_or_dims
         Tl, Tm, (H, W), (Hc, Wc) = e.Tl, e.Tm, getattr(e, 'img_size', (180, 240)), e.input_size
         window = (e.window * 1000, 0) if getattr(e, 'window', None) is not None else None
+        if measure is None:
+            measure = getattr(e, 'measure', None)
+    measure = 'count' if measure is None else measure
+    if measure not in ATIS_MEASURES:
+        raise ValueError(f"measure {measure!r}: the N-Caltech101 front end has {' and '.join(repr(m) for m in ATIS_MEASURES)}")
+    if measure == 'timesurface':
+        frames = ops.event_timesurface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=tau)
+        return ops.frames_letterbox(frames, params_on(params, frames.device), Hc, Wc, interp=interp)
     counts = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
     return ops.counts_letterbox(counts, params_on(params, counts.device), Hc, Wc, interp=interp)
 

@@ -99,6 +99,30 @@ def event_histogram_atis(records, sample_offsets, Tl, Tm, H, W, window=None, ret
     return res if len(res) > 1 else out
 
 
+def event_timesurface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, tau=500e3, return_oob=False, return_flags=False):
+    """``event_histogram_atis`` with the reference's measure 'timesurface': float64 frames [B, Tl, Tm, 2, H, W] in which every event adds
+    ``1 - tanh((t_target - t) / tau)`` instead of 1, ``t_target`` the time of the last event of its macro slice, ``tau`` in us
+    (NCaltech.get_measure_func, ncaltech.py:218-225; event_reps.py:13-19).  Same decode, window, slicing and optional returns; flags bit 2:
+    a macro slice spans more records than one bin can hold at weight 1 (``eas_event_timesurface_atis_capacity()``).  Bit-identical from run
+    to run (64-bit integer sums of the weights in units of 2^-48)."""
+    _dev(records, sample_offsets)
+    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
+    rec = records if records.is_contiguous() else records.contiguous()
+    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    nrec = rec.numel() // 5
+    B = sample_offsets.numel() - 1
+    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
+    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.float64, device=rec.device)
+    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
+    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
+    ws = torch.empty(_lib.lib().eas_event_timesurface_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
+    # bytes: the records twice, the 64-bit bins written, then read and written once more by the finishing pass
+    _call('eas_event_timesurface_atis', 10 * nrec + 24 * out.numel(), _lib.lib().eas_event_timesurface_atis, ptr(rec), nrec,
+          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, float(tau), ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
+    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return res if len(res) > 1 else out
+
+
 def event_frames(t, x, y, p, sample_offsets, Tm, H, W, Hc, Wc):
     """raw events -> fp32 count frames on the zero-padded model canvas [B, Tm, 2, Hc, Wc] in one call (K1 + canvas)."""
     _dev(t, x, y, p, sample_offsets)
@@ -179,6 +203,20 @@ def counts_letterbox(counts, params, Hc, Wc, interp='linear'):
     out = torch.empty(counts.shape[:-2] + (Hc, Wc), dtype=torch.float32, device=counts.device)
     check(_lib.lib().eas_counts_letterbox_ex(ptr(counts), ptr(params), ('linear', 'cubic').index(interp), B, F, H, W, Hc, Wc, ptr(out), stream()),
           'eas_counts_letterbox_ex')
+    return out
+
+
+def frames_letterbox(frames, params, Hc, Wc, interp='linear'):
+    """``counts_letterbox`` for float64 frames [B, ..., H, W] (``event_timesurface_atis``) -> fp32 [B, ..., Hc, Wc]: the same kernel body on a
+    double source, so frames that hold integers give exactly what their int32 counts give."""
+    _dev(frames, params)
+    assert frames.dtype == torch.float64 and params.dtype == torch.int32 and params.shape == (frames.shape[0], 5)
+    frames, params = frames.contiguous(), params.contiguous()
+    B, (H, W) = frames.shape[0], frames.shape[-2:]
+    F = frames.numel() // (B * H * W)
+    out = torch.empty(frames.shape[:-2] + (Hc, Wc), dtype=torch.float32, device=frames.device)
+    check(_lib.lib().eas_frames_letterbox_f64(ptr(frames), ptr(params), ('linear', 'cubic').index(interp), B, F, H, W, Hc, Wc, ptr(out), stream()),
+          'eas_frames_letterbox_f64')
     return out
 
 

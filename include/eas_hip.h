@@ -127,6 +127,25 @@ int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl);
 int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
                              int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                              eas_stream_t stream);
+/* The same recordings with measure='timesurface' (additive, ABI 9): frames float64 [B][Tl][Tm][2][H][W] in which an event of time t adds
+ * w = 1 - tanh((t_target - t) / tau) instead of 1, t_target = the time of the last member event of the event's MACRO slice, tau in us
+ * (the reference: 500e3).  NCaltech.get_measure_func / timesurface_measure(decay='tanh') handed to every micro slice (ncaltech.py:178-183,
+ * 218-237, 264-269; yolox/utils/event_reps.py:13-19).  Decode, window, slicing, oob_count and flag bits 0 and 1 are those of
+ * eas_event_histogram_atis (the same device code).  A bin sums llrint(w * 2^48) with 64-bit integer atomics and a finishing pass scales
+ * the sums by 2^-48: every event is within 2^-49 + the error of tanh of the fp64 weight, a bin is exactly 0 where no event fell, and the
+ * frames are bit-identical from run to run, for every batch composition and buffer alignment.  A bin holds
+ * eas_event_timesurface_atis_capacity() = 65 535 events of weight 1: flags[b] bit 2 is set when a macro slice of recording b spans more
+ * records than that (conservative: they would all have to fall on one pixel of one micro slice and polarity).
+ * tau <= 0 or NaN: EAS_ERR_INVALID_ARG.  workspace: eas_event_timesurface_atis_workspace_bytes(nrec, B, Tl) bytes, 16-byte aligned. */
+int64_t eas_event_timesurface_atis_workspace_bytes(int64_t nrec, int B, int Tl);
+int64_t eas_event_timesurface_atis_capacity(void);
+int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                               int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                               eas_stream_t stream);
+/* eas_counts_letterbox_ex on float64 frames [B][F][H][W] (those of eas_event_timesurface_atis): the same kernel body on a double source --
+ * cv2.resize of the reference sees float64 images for both measures --, so frames that hold integers give the bits the counts give. */
+int eas_frames_letterbox_f64(const double* frames, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
+                             eas_stream_t stream);
 
 /* Bilinear-in-time voxel grid, to_voxel_grid_numpy (yolox/utils/event_reps.py:30-89).
  * out[b][bin][y][x] float64 (zeroed by the call); polarity 0 counts as -1. */
