@@ -134,6 +134,8 @@ PROTOTYPES = {
     'eas_event_timesurface_atis_capacity': (C.c_int64, []),
     'eas_event_timesurface_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_double] + [_P] * 5),
     'eas_frames_letterbox_f64': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
+    'eas_event_latest_surface_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_double] + [_P] * 5),
+    'eas_event_latest_surface_dat_ranges': (C.c_int, [_P, _P] + [C.c_int] * 4 + [C.c_double, _P, _P, _P]),
     'eas_postprocess_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'eas_postprocess': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P]),
     'eas_event_frames': (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -9,6 +9,7 @@
 
 #include "eas_common.h"
 #include "count_resize.h"
+#include "latest_surface.h"
 
 namespace {
 
@@ -532,19 +533,28 @@ __global__ __launch_bounds__(EAS_BLOCK) void voxel_cube_kernel(const uint32_t* _
 // Pass 1: latest timestamp per (sample, slice, polarity, pixel) by integer atomic max (timestamps ascend, so the
 // maximum is the reference's "last write wins").  Pass 2: running maximum over the slices, then
 // exp(-((i + 1) * window + t0 - latest) / tau) in float64; untouched pixels keep latest = 0 exactly like the reference.
+// Both steps live in latest_surface.h; ``latest_one`` is the event's way to its bin, for decoded arrays and for .dat records.
+template <typename Bin>
+__device__ __forceinline__ void latest_one(uint32_t tt, uint32_t xx, uint32_t yy, uint32_t pp, const SampleWin& w, int b, int ns, int H, int W,
+                                           Bin* __restrict__ latest, uint32_t* __restrict__ oob) {
+    if (w.win == 0) return;
+    const uint32_t k = (tt - w.t0) / w.win;
+    if (k >= (uint32_t)ns) return;
+    if (xx >= (uint32_t)W || yy >= (uint32_t)H) {
+        if (oob) atomicAdd(oob, 1u);
+        return;
+    }
+    if (pp > 1u) return;
+    latest_time_max(latest + ((((int64_t)b * ns + k) * 2 + pp) * H + yy) * W + xx, tt);
+}
+
 __global__ __launch_bounds__(EAS_BLOCK) void time_surface_scatter_kernel(const uint32_t* __restrict__ t, const uint16_t* __restrict__ x,
                                                                          const uint16_t* __restrict__ y, const uint8_t* __restrict__ p,
                                                                          int64_t nev, const int64_t* __restrict__ offsets, int B,
                                                                          int ns, int H, int W, uint32_t* __restrict__ latest) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nev; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = find_sample(offsets, B, i);
-        const SampleWin w = sample_window(t, offsets, b, ns);
-        if (w.win == 0) continue;
-        const uint32_t k = (t[i] - w.t0) / w.win;
-        if (k >= (uint32_t)ns) continue;
-        const uint32_t xx = x[i], yy = y[i], pp = p[i];
-        if (xx >= (uint32_t)W || yy >= (uint32_t)H || pp > 1u) continue;
-        atomicMax(latest + ((((int64_t)b * ns + k) * 2 + pp) * H + yy) * W + xx, t[i]);
+        latest_one(t[i], x[i], y[i], p[i], sample_window(t, offsets, b, ns), b, ns, H, W, latest, nullptr);
     }
 }
 
@@ -554,23 +564,40 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_surface_exp_kernel(const uint3
     const int64_t plane = (int64_t)2 * H * W, total = (int64_t)B * plane;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)(i / plane);
-        const int64_t q = i - (int64_t)b * plane;
-        const int64_t a = offsets[b], e = offsets[b + 1];
+        const int64_t first = (int64_t)b * ns * plane + (i - (int64_t)b * plane);
+        SampleWin w{0u, 0u};                        // no events, or a window of zero length (invalid input): zeros
+        if (offsets[b + 1] > offsets[b]) w = sample_window(t, offsets, b, ns);
+        surface_walk(w.t0, w.win, ns, tau, [latest, first, plane](int k) { return latest[first + k * plane]; },
+                     [out, first, plane](int k, double v) { out[first + k * plane] = v; });
+    }
+}
+
+// The same surfaces for samples given as record ranges of a .dat image (eas_event_latest_surface_dat_ranges): blockIdx.y = sample, blocks
+// stride over its range (ranges overlap; nothing is read back); the latest times go into the output's own 64-bit bins.
+__global__ __launch_bounds__(EAS_BLOCK) void latest_dat_ranges_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges, int ns,
+                                                                      int H, int W, unsigned long long* __restrict__ bins,
+                                                                      uint32_t* __restrict__ oob) {
+    const int b = blockIdx.y;
+    const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
+    if (e <= a) return;
+    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, ns);
+    for (int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint2 v = rec[i];
+        latest_one(v.x, v.y & 16383u, (v.y >> 14) & 16383u, (v.y >> 28) & 1u, w, b, ns, H, W, bins, oob);
+    }
+}
+
+// in place: one thread per (sample, polarity, pixel), adjacent lanes on adjacent pixels, the micro slices 2 * H * W bins apart
+__global__ __launch_bounds__(EAS_BLOCK) void latest_dat_ranges_finish_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges,
+                                                                             int B, int ns, int H, int W, double tau,
+                                                                             unsigned long long* __restrict__ bins) {
+    const int64_t plane = (int64_t)2 * H * W, total = (int64_t)B * plane;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / plane);
+        const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
         SampleWin w{0u, 0u};
-        if (e > a) w = sample_window(t, offsets, b, ns);
-        uint32_t m = 0;
-        for (int k = 0; k < ns; ++k) {
-            const int64_t idx = ((int64_t)b * ns + k) * plane + q;
-            if (w.win == 0) {                       // no events, or a window of zero length (invalid input): zeros
-                out[idx] = 0.0;
-                continue;
-            }
-            const uint32_t l = latest[idx];
-            m = l > m ? l : m;
-            const uint32_t end = (uint32_t)(k + 1) * w.win + w.t0;       // uint32 arithmetic as numpy's
-            const int64_t diff = -((int64_t)end - (int64_t)m);
-            out[idx] = exp((double)diff / tau);
-        }
+        if (e > a) w = make_window(rec[a].x, rec[e - 1].x, ns);
+        surface_walk_in_place(bins + (int64_t)b * ns * plane + (i - (int64_t)b * plane), plane, w.t0, w.win, ns, tau);
     }
 }
 
@@ -729,6 +756,23 @@ int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, i
     if (!zero_counts(out, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), oob_count, st)) return EAS_ERR_LAUNCH;
     // the ranges live on the device (no host read): a fixed number of blocks per sample strides over whatever it holds
     EAS_LAUNCH(event_hist_dat_ranges_kernel, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, Tm, H, W, out, oob_count);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* ranges, int B, int num_slices, int H, int W, double tau, double* out,
+                                        uint32_t* oob_count, eas_stream_t stream) {
+    if (!records || !ranges || !out || B < 1 || num_slices < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7) || !(tau > 0.0))
+        return EAS_ERR_INVALID_ARG;                // !(tau > 0): also NaN
+    if (B > 65535) return EAS_ERR_UNSUPPORTED;     // the sample is a block's y index
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    if (!zero_counts((int32_t*)out, (size_t)B * num_slices * 2 * H * W * sizeof(double), oob_count, st)) return EAS_ERR_LAUNCH;
+    EAS_LAUNCH(latest_dat_ranges_kernel, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, num_slices, H, W, bins, oob_count);
+    EAS_CHECK_LAUNCH();
+    EAS_LAUNCH(latest_dat_ranges_finish_kernel, dim3(eas_grid_1d((int64_t)B * 2 * H * W)), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, B,
+               num_slices, H, W, tau, bins);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -18,6 +18,11 @@
 //                                   TimeSurfaceAcc adds llrint(w * 2^48), w = 1 - tanh((t_target - t) / tau) in fp64 with t_target =
 //                                   the time of the macro slice's last member event (a plan row), to a 64-bit bin
 //   5. atis_ts_finish_kernel        (time surface only) the 64-bit sums, in place, -> double * 2^-48
+//   aggregation 'timesurface' (eas_event_latest_surface_atis; agrregate('timesurface'), ncaltech.py:255-257 + to_timesurface_numpy,
+//   event_reps.py:141-160, tau = 10e3) is a third accumulate step and a finishing pass of its own: LatestAcc takes the integer atomic max
+//   of the event's time into the OUTPUT's 64-bit bin of its micro slice; atis_latest_finish_kernel, one thread per (recording, macro slice,
+//   polarity, pixel), walks the Tm bins with a running maximum m and overwrites each with exp(-((q + 1) * w + f - m) / tau), f and w read
+//   from the plan's row (latest_surface.h).  Plan flag bit 3: a macro slice that holds events has micro window 0 (the reference raises).
 // Time-surface sums are integers, so the frames do not depend on the order of the adds: bit-identical run to run, for any grid and any
 // neighbours in the buffer.  Each event is off by <= 2^-49 (the rounding of w * 2^48) + the error of tanh; a bin holds 65 535 events of
 // weight 1 (kTsCapacity): a macro slice of more records than that sets flag bit 2 (conservative: the records of ONE pixel would have to).
@@ -29,6 +34,7 @@
 #include <limits.h>
 
 #include "eas_common.h"
+#include "latest_surface.h"
 
 namespace {
 
@@ -150,8 +156,8 @@ __device__ __forceinline__ int64_t lower_bound_events(const AtisRec& R, int64_t 
 __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
                                                              const uint32_t* __restrict__ chunk_base, int64_t window_lo, int64_t window_hi,
                                                              int Tl, int Tm, AtisHead* __restrict__ heads, AtisSlice* __restrict__ slices,
-                                                             uint32_t* __restrict__ t_target, uint32_t* __restrict__ oob,
-                                                             uint32_t* __restrict__ flags) {
+                                                             uint32_t* __restrict__ t_target, uint32_t window0_flag,
+                                                             uint32_t* __restrict__ oob, uint32_t* __restrict__ flags) {
     const int b = blockIdx.x;
     const bool writer = threadIdx.x == 0;
     int64_t a, e;
@@ -197,6 +203,7 @@ __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __re
                 s.w = l > f ? (uint32_t)((l - f) / Tm) : 0u;
                 target = (uint32_t)l;
                 if (t_target && end - start > kTsCapacity) flag |= 4u;     // more records than one 64-bit bin holds at weight 1
+                if (s.w == 0u) flag |= window0_flag;                       // (the latest-time surface: 8, the reference raises; else 0)
             }
             start = end;
         }
@@ -294,6 +301,11 @@ __global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __rest
     }
 }
 
+struct LatestAcc {                      // aggregation 'timesurface': the latest time of the bin (latest_surface.h), finished by atis_latest_finish_kernel
+    typedef unsigned long long Bin;
+    __device__ __forceinline__ void operator()(Bin* bin, int64_t, uint32_t t) const { latest_time_max(bin, t); }
+};
+
 // the frames are zeroed by a kernel of the call's own (16-byte stores; torch hands out 16-byte aligned frames, a scalar loop otherwise)
 __global__ __launch_bounds__(EAS_BLOCK) void atis_zero_kernel(int32_t* __restrict__ out, int64_t n) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
@@ -311,6 +323,19 @@ __global__ __launch_bounds__(EAS_BLOCK) void atis_ts_finish_kernel(unsigned long
         bins[i] = __builtin_bit_cast(unsigned long long, (double)bins[i] * (1.0 / kTsOne));
 }
 
+// the latest-time surface's finishing pass, in place: one thread per (recording, macro slice, polarity, pixel), adjacent lanes on adjacent
+// pixels, the Tm micro slices 2 * H * W bins apart; f and w come from the plan's row (w == 0: an empty macro slice or a micro window of zero
+// length -- nothing was binned, the frames are zeros)
+__global__ __launch_bounds__(EAS_BLOCK) void atis_latest_finish_kernel(const AtisSlice* __restrict__ slices, int64_t nrows, int Tm, int H, int W,
+                                                                       double tau, unsigned long long* __restrict__ bins) {
+    const int64_t plane = (int64_t)2 * H * W, total = nrows * plane;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / plane;
+        const AtisSlice s = slices[row];
+        surface_walk_in_place(bins + row * Tm * plane + (i - row * plane), plane, s.f, s.w, Tm, tau);
+    }
+}
+
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t chunks_of(int64_t nrec) { return (nrec + kChunk - 1) / kChunk; }
 
@@ -326,11 +351,12 @@ struct AtisWorkspace {
     }
 };
 
-// The launches of both entry points (arguments checked by the caller).  t_target: NULL for the count measure.
+// The launches the entry points share (arguments checked by the caller).  t_target: NULL but for the time-surface measure; window0_flag:
+// the flag bits of a macro slice that holds events and has micro window 0 (8 for the latest-time surface, else 0).
 template <typename Acc>
 int atis_frames(const uint8_t* rec, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
-                int H, int W, typename Acc::Bin* out, uint32_t* oob_count, uint32_t* flags, void* workspace, uint32_t* t_target, const Acc& acc,
-                hipStream_t st) {
+                int H, int W, typename Acc::Bin* out, uint32_t* oob_count, uint32_t* flags, void* workspace, uint32_t* t_target, uint32_t window0_flag,
+                const Acc& acc, hipStream_t st) {
     const int64_t far = (int64_t)1 << 40;                  // decoded times fit 32 bits: a bound beyond +-2^40 selects what 2^40 selects
     window_lo = window_lo < -far ? -far : window_lo;
     window_hi = window_hi > far ? far : (window_hi < -far ? -far : window_hi);
@@ -350,7 +376,7 @@ int atis_frames(const uint8_t* rec, int64_t nrec, const int64_t* sample_offsets,
         EAS_CHECK_LAUNCH();
     }
     EAS_LAUNCH(atis_plan_kernel, dim3(B), dim3(EAS_WAVE), 0, st, rec, nrec, sample_offsets, chunk_base, window_lo, window_hi, Tl, Tm, heads, slices,
-               t_target, oob_count, flags);
+               t_target, window0_flag, oob_count, flags);
     EAS_CHECK_LAUNCH();
     if (nchunks > 0) {
         // the recordings' lengths live on the device: a fixed number of blocks per recording strides over whatever it holds
@@ -363,7 +389,7 @@ int atis_frames(const uint8_t* rec, int64_t nrec, const int64_t* sample_offsets,
     return EAS_OK;
 }
 
-// the argument rules the two entry points share
+// the argument rules the entry points share
 int atis_check_args(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int Tl, int Tm, int H, int W, const void* out,
                     const void* workspace) {
     if (!out || !sample_offsets || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
@@ -387,7 +413,7 @@ int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* s
     const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
     if (rc != EAS_OK) return rc;
     return atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace,
-                       nullptr, CountAcc{}, eas_s(stream));
+                       nullptr, 0u, CountAcc{}, eas_s(stream));
 }
 
 int64_t eas_event_timesurface_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
@@ -407,10 +433,28 @@ int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t*
     uint32_t* t_target = (uint32_t*)((char*)workspace + AtisWorkspace(nrec, B, Tl).t_target);
     unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
     const int launched = atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, bins, oob_count, flags,
-                                     workspace, t_target, TimeSurfaceAcc{t_target, tau}, st);
+                                     workspace, t_target, 0u, TimeSurfaceAcc{t_target, tau}, st);
     if (launched != EAS_OK) return launched;
     const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W;
     EAS_LAUNCH(atis_ts_finish_kernel, dim3(eas_grid_1d(nout)), dim3(EAS_BLOCK), 0, st, bins, nout);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+int eas_event_latest_surface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                                  int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                  eas_stream_t stream) {
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
+    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
+    if (rc != EAS_OK) return rc;
+    hipStream_t st = eas_s(stream);
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    const int launched = atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, bins, oob_count, flags,
+                                     workspace, nullptr, 8u, LatestAcc{}, st);
+    if (launched != EAS_OK) return launched;
+    const AtisSlice* slices = (const AtisSlice*)((char*)workspace + AtisWorkspace(nrec, B, Tl).slices);
+    const int64_t nrows = (int64_t)B * Tl;
+    EAS_LAUNCH(atis_latest_finish_kernel, dim3(eas_grid_1d(nrows * 2 * H * W)), dim3(EAS_BLOCK), 0, st, slices, nrows, Tm, H, W, tau, bins);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -26,9 +26,40 @@ def events_to_device(ev, device):
     return {k: torch.from_numpy(v).to(device, non_blocking=True) for k, v in ev.items()}
 
 
-def events_to_frames(ev_dev, Tm, sensor_hw, canvas_hw):
-    """Device events -> model input [B, Tl=1, Tm, 2, Hc, Wc] fp32 via the HIP histogram (K1)."""
+# the values of the reference's ``aggregation`` option (EventExp.aggregation -> slice_args) whose frames the sampler takes: two polarity
+# channels, one frame per micro slice
+FRAME_AGGREGATIONS = ('micro_sum', 'timesurface')
+_OTHER_AGGREGATIONS = ('voxel_grid', 'voxel_cube', 'sum', 'raw_frame')
+
+
+def check_aggregation(aggregation):
+    """``aggregation`` if a device front end has it; ValueError otherwise (nothing trains on another representation without a word)"""
+    if aggregation in FRAME_AGGREGATIONS:
+        return aggregation
+    have = ' and '.join(repr(a) for a in FRAME_AGGREGATIONS)
+    why = ''
+    if aggregation in _OTHER_AGGREGATIONS:
+        why = (f": the reference's {aggregation!r} frames do not have the sampler's two channels per micro slice "
+               "(voxel_grid: 1 channel, voxel_cube: 2 * tbins, sum: no micro slices, raw_frame: one frame per timestamp)")
+    raise ValueError(f'aggregation {aggregation!r}: the event front ends have {have}{why}')
+
+
+def unscaled_params(batch, sensor_hw, device):
+    """int32 [batch, 5] rows (W, H, 0, 0, 0) made on the device (fills, no copy from the host: graph-capturable): the sensor at scale 1 at
+    the top left of a zero canvas, where the count loaders place their frames"""
+    par = torch.zeros((batch, 5), dtype=torch.int32, device=device)
+    par[:, 0], par[:, 1] = int(sensor_hw[1]), int(sensor_hw[0])
+    return par
+
+
+def events_to_frames(ev_dev, Tm, sensor_hw, canvas_hw, aggregation='micro_sum', tau=50e3):
+    """Device events -> model input [B, Tl=1, Tm, 2, Hc, Wc] fp32 via the HIP histogram (K1).  ``aggregation='timesurface'``: Gen1's
+    exponential time surfaces instead (``ops.event_time_surface`` with ``tau`` in us, gen1.py:362-369), placed like the counts: scale 1,
+    top left, zero padding (``ops.frames_letterbox`` with ``unscaled_params``).  Any other value raises ValueError."""
     H, W = sensor_hw
+    if check_aggregation(aggregation) == 'timesurface':
+        surf = ops.event_time_surface(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, tau=tau)
+        return ops.frames_letterbox(surf, unscaled_params(surf.shape[0], sensor_hw, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
     frames = ops.event_frames(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, canvas_hw[0], canvas_hw[1])
     return frames.unsqueeze(1)
 
@@ -52,11 +83,18 @@ class SyntheticEventDataset:
         return self.length
 
 
+def exp_aggregation(exp):
+    """the experiment's ``aggregation`` field ('micro_sum' without one), checked"""
+    return check_aggregation(getattr(exp, 'aggregation', 'micro_sum'))
+
+
 class SyntheticEventLoader:
-    """Iterable of (frames [B,Tl,Tm,2,H,W] fp32 on the GPU, targets [B,50,5]); one 'epoch' = ``iters`` batches."""
+    """Iterable of (frames [B,Tl,Tm,2,H,W] fp32 on the GPU, targets [B,50,5]); one 'epoch' = ``iters`` batches.  The frames are those of
+    the experiment's ``aggregation`` (``events_to_frames``); a value no front end has raises ValueError, here and when iterating."""
 
     def __init__(self, exp, batch_size, iters=16, n_events=200_000, sensor_hw=(240, 304)):
         self.exp, self.batch_size, self.iters, self.n_events, self.sensor_hw = exp, batch_size, iters, n_events, sensor_hw
+        exp_aggregation(exp)
         self.dataset = SyntheticEventDataset(exp)
 
     def __len__(self):
@@ -69,7 +107,7 @@ class SyntheticEventLoader:
         dev = torch.device('cuda', torch.cuda.current_device())
         for i in range(self.iters):
             ev = events_to_device(synth_event_batch(self.batch_size, self.n_events, *self.sensor_hw, seed=i), dev)
-            frames = events_to_frames(ev, self.exp.Tm, self.sensor_hw, self.exp.input_size)
+            frames = events_to_frames(ev, self.exp.Tm, self.sensor_hw, self.exp.input_size, aggregation=exp_aggregation(self.exp))
             yield frames, synth_targets(self.batch_size, self.exp.input_size, dev)
 
 class SyntheticEvalDataset(SyntheticEventDataset):
@@ -91,10 +129,11 @@ class SyntheticEvalLoader:
     """Iterable of ``(frames [B,Tl,Tm,2,H,W] fp32 on the GPU, labels [B][n,5] rows (x, y, w, h, cls), (heights, widths), ids)`` -- the tuple
     the reference's evaluation loader yields (gen1_collact_func; event_evaluator.py:183).  Sample ``i`` is the seeded stream ``i`` on every
     rank; ``indices`` are this rank's samples (rank, rank + world, ... like DistributedSampler(shuffle=False), event_yolox_base.py:489-494);
-    the last batch may be short."""
+    the last batch may be short.  The frames are those of the experiment's ``aggregation``, as in ``SyntheticEventLoader``."""
 
     def __init__(self, exp, batch_size, indices, n_events=200_000, sensor_hw=(240, 304), dataset=None):
         self.exp, self.batch_size, self.indices, self.n_events, self.sensor_hw = exp, batch_size, list(indices), n_events, sensor_hw
+        exp_aggregation(exp)
         self.dataset = dataset if dataset is not None else SyntheticEvalDataset(exp, n_events=n_events)
 
     def __len__(self):
@@ -108,7 +147,8 @@ class SyntheticEvalLoader:
             parts = [synth_event_batch(1, self.n_events, H, W, seed=10_000 + i) for i in ids]
             ev = {k: np.concatenate([p[k] for p in parts]) for k in ('t', 'x', 'y', 'p')}
             ev['offsets'] = np.arange(len(ids) + 1, dtype=np.int64) * self.n_events
-            frames = events_to_frames(events_to_device(ev, dev), self.exp.Tm, self.sensor_hw, self.exp.test_size)
+            frames = events_to_frames(events_to_device(ev, dev), self.exp.Tm, self.sensor_hw, self.exp.test_size,
+                                      aggregation=exp_aggregation(self.exp))
             labels = [torch.tensor([[0.3 * W, 0.4 * H, 0.25 * W, 0.3 * H, float(i % self.exp.num_classes)]]) for i in ids]
             yield frames, labels, (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
 
@@ -220,9 +260,13 @@ def synth_atis_batch(batch, n_events, height=180, width=240, span_us=300_000, se
 ATIS_MEASURES = ('count', 'timesurface')
 
 
-def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic', measure=None, tau=500e3):
+def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic', measure=None, tau=500e3, aggregation=None, surface_tau=10e3):
     """Raw ATIS recordings in HBM -> model input [B, Tl, Tm, 2, Hc, Wc] fp32: ``ops.event_histogram_atis`` then ``ops.counts_letterbox``,
-    nothing read back in between (graph-capturable).  ``measure`` (None: the experiment's ``measure`` field, ``'count'`` without one):
+    nothing read back in between (graph-capturable).  ``aggregation`` (None: the experiment's ``aggregation`` field, ``'micro_sum'`` without
+    one): ``'micro_sum'``, or ``'timesurface'`` = ``ops.event_latest_surface_atis`` with ``surface_tau`` (us) then ``ops.frames_letterbox``,
+    the reference's ``aggregation timesurface`` (NCaltech.agrregate, ncaltech.py:255-257); anything else raises ValueError.  With
+    ``'timesurface'`` the measure is not consulted, as in the reference, which computes its measure function there and does not use it: the
+    rest of this paragraph is about ``'micro_sum'``.  ``measure`` (None: the experiment's ``measure`` field, ``'count'`` without one):
     ``'count'``, or ``'timesurface'`` = ``ops.event_timesurface_atis`` with ``tau`` (us) then ``ops.frames_letterbox``, the reference's
     ``measure timesurface`` (NCaltech.get_measure_func, ncaltech.py:218-225); anything else raises ValueError.  ``exp_or_dims``: an experiment (fields ``Tl``, ``Tm``, ``input_size``, optionally
     ``img_size`` -- the sensor, default (180, 240) -- and ``window`` in ms, as yolox/exp/event_yolox_base.py passes it: ``(window * 1000, 0)``) or a tuple
@@ -239,6 +283,11 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
         window = (e.window * 1000, 0) if getattr(e, 'window', None) is not None else None
         if measure is None:
             measure = getattr(e, 'measure', None)
+        if aggregation is None:
+            aggregation = getattr(e, 'aggregation', None)
+    if check_aggregation('micro_sum' if aggregation is None else aggregation) == 'timesurface':
+        frames = ops.event_latest_surface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=surface_tau)
+        return ops.frames_letterbox(frames, params_on(params, frames.device), Hc, Wc, interp=interp)
     measure = 'count' if measure is None else measure
     if measure not in ATIS_MEASURES:
         raise ValueError(f"measure {measure!r}: the N-Caltech101 front end has {' and '.join(repr(m) for m in ATIS_MEASURES)}")
@@ -377,9 +426,27 @@ class SyntheticStackedHistLoader:
             yield frames, torch.from_numpy(self.targets(idx, par)).to(dev)
 
 
-def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params):
+def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params, aggregation='micro_sum', tau=50e3):
     """events -> histogram (K1) -> resize / paste / flip on the device -> [B, 1, Tm, 2, Hc, Wc] fp32; ``params``: per-sample
-    (nw, nh, dx, dy, flip) rows."""
+    (nw, nh, dx, dy, flip) rows.  ``aggregation='timesurface'``: ``ops.event_time_surface`` with ``tau`` (us) in place of the histogram,
+    then ``ops.frames_letterbox`` (linear, as Gen1 resizes); any value but the two of ``FRAME_AGGREGATIONS`` raises ValueError."""
     H, W = sensor_hw
+    if check_aggregation(aggregation) == 'timesurface':
+        surf = ops.event_time_surface(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, tau=tau)
+        return ops.frames_letterbox(surf, params_on(params, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
     counts = ops.event_histogram(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W)
+    return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+
+
+def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggregation='micro_sum', tau=50e3):
+    """The Gen1 chain from record ranges: the .dat image ``records`` in HBM and the ranges int64 [B, 2] of ``ops.event_window_search`` ->
+    model input [B, 1, Tm, 2, Hc, Wc] fp32, nothing read back in between (graph-capturable).  ``'micro_sum'``:
+    ``ops.event_histogram_dat_ranges`` then ``ops.counts_letterbox``; ``'timesurface'``: ``ops.event_latest_surface_dat_ranges`` with ``tau``
+    (us; GEN1Dataset.agrregate, gen1.py:362-369) then ``ops.frames_letterbox``, both with the linear resize; any other value raises
+    ValueError.  ``params``: per-sample (nw, nh, dx, dy, flip) rows, a device int32 tensor or anything numpy reads."""
+    H, W = sensor_hw
+    if check_aggregation(aggregation) == 'timesurface':
+        surf = ops.event_latest_surface_dat_ranges(records, ranges, Tm, H, W, tau=tau)
+        return ops.frames_letterbox(surf, params_on(params, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+    counts = ops.event_histogram_dat_ranges(records, ranges, Tm, H, W)
     return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)

@@ -123,6 +123,48 @@ def event_timesurface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, t
     return res if len(res) > 1 else out
 
 
+def event_latest_surface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, tau=10e3, return_oob=False, return_flags=False):
+    """The reference's ``aggregation timesurface`` of raw ATIS recordings: float64 [B, Tl, Tm, 2, H, W], frame ``q`` of a macro slice =
+    ``exp(-((q + 1) * w + f - latest) / tau)`` on every pixel, ``latest`` the time of the pixel's last event in micro slices 0 .. q of the
+    macro slice (0 where none fell: a surface is > 0 everywhere), ``f`` / ``w`` the macro slice's first time and micro window, ``tau`` in us
+    (NCaltech.agrregate 'timesurface', ncaltech.py:255-257; to_timesurface_numpy, event_reps.py:141-160).  Decode, window, slicing and the
+    optional returns are ``event_histogram_atis``'s; flags bit 3 (value 8): a macro slice holds events and has micro window 0 (the reference
+    raises; its frames are zero).  Not ``event_timesurface_atis``, which is the *measure* of that name.  Bit-identical from run to run."""
+    _dev(records, sample_offsets)
+    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
+    rec = records if records.is_contiguous() else records.contiguous()
+    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    nrec = rec.numel() // 5
+    B = sample_offsets.numel() - 1
+    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
+    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.float64, device=rec.device)
+    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
+    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
+    ws = torch.empty(_lib.lib().eas_event_histogram_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
+    # bytes: the records twice, the 64-bit bins zeroed, then read and written once by the finishing pass
+    _call('eas_event_latest_surface_atis', 10 * nrec + 24 * out.numel(), _lib.lib().eas_event_latest_surface_atis, ptr(rec), nrec,
+          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, float(tau), ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
+    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return res if len(res) > 1 else out
+
+
+def event_latest_surface_dat_ranges(records, ranges, num_slices, H, W, tau=50e3, return_oob=False):
+    """``event_time_surface`` (Gen1's ``aggregation timesurface``) of the record ranges [B, 2] (``event_window_search``) of a .dat image in
+    HBM: float64 [B, num_slices, 2, H, W], bit-identical to ``event_time_surface`` on the decoded arrays of the same samples; an empty range
+    or a window of zero length gives zero frames.  Label timestamps in, surfaces out, nothing read back to the host in between.  Optional
+    return: the events outside the sensor that were dropped (int32 [1])."""
+    _dev(records, ranges)
+    rec = records.contiguous().view(torch.uint8)
+    assert rec.numel() % 8 == 0, '.dat event records are 8 bytes'
+    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
+    B = ranges.shape[0]
+    out = torch.empty((B, num_slices, 2, H, W), dtype=torch.float64, device=rec.device)
+    oob = torch.empty(1, dtype=torch.int32, device=rec.device) if return_oob else None
+    _call('eas_event_latest_surface_dat_ranges', 8 * (rec.numel() // 8) + 24 * out.numel(), _lib.lib().eas_event_latest_surface_dat_ranges,
+          ptr(rec), ptr(ranges.contiguous()), B, num_slices, H, W, float(tau), ptr(out), ptr(oob), stream())
+    return (out, oob) if return_oob else out
+
+
 def event_frames(t, x, y, p, sample_offsets, Tm, H, W, Hc, Wc):
     """raw events -> fp32 count frames on the zero-padded model canvas [B, Tm, 2, Hc, Wc] in one call (K1 + canvas)."""
     _dev(t, x, y, p, sample_offsets)

@@ -142,6 +142,23 @@ int64_t eas_event_timesurface_atis_capacity(void);
 int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
                                int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                                eas_stream_t stream);
+/* The same recordings with aggregation='timesurface' (additive, ABI 9; "latest surface": eas_event_timesurface_atis is the MEASURE of that
+ * name): frames float64 [B][Tl][Tm][2][H][W], frame q of macro slice k = exp(-((q + 1) w + f - latest) / tau) for every pixel, f / w the
+ * macro slice's first member time and micro window as above, latest[p][y][x] the time of the last event of micro slices 0 .. q on the
+ * pixel -- the memory is not cleared between the micro slices of a macro slice -- and 0 for a pixel no event touched (so a surface is > 0
+ * everywhere), tau in us (the reference: 10e3).  NCaltech.agrregate('timesurface') = generate_slices(events, Tm, overlap=0) +
+ * to_timesurface_numpy(dt = the micro window, start_t = f) per macro slice (ncaltech.py:178-183, 255-257, 368-379;
+ * yolox/utils/event_reps.py:141-160); the reference computes its measure there and does not use it.  Decode, overflow prefix, window,
+ * slicing, oob_count and flag bits 0 and 1 are those of eas_event_histogram_atis (the same device code, a third accumulate step: an integer
+ * atomic max of the decoded time).  The latest times are kept in the output's own 64-bit bins, zeroed by the call, until a finishing pass --
+ * one thread per (recording, macro slice, polarity, pixel), a running maximum over the Tm micro slices -- overwrites them with the
+ * exponentials: integer atomics and one fp64 exp per element, bit-identical from run to run, for every batch composition and alignment.
+ * flags[b] bit 3 (value 8): a macro slice of recording b holds events and has micro window 0 (the reference raises IndexError); that
+ * slice's frames are zero, and so are the frames of an empty macro slice (bit 1).  tau <= 0 or NaN: EAS_ERR_INVALID_ARG.
+ * workspace: the count entry's, eas_event_histogram_atis_workspace_bytes(nrec, B, Tl) bytes, 16-byte aligned. */
+int eas_event_latest_surface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
+                                  int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                  eas_stream_t stream);
 /* eas_counts_letterbox_ex on float64 frames [B][F][H][W] (those of eas_event_timesurface_atis): the same kernel body on a double source --
  * cv2.resize of the reference sees float64 images for both measures --, so frames that hold integers give the bits the counts give. */
 int eas_frames_letterbox_f64(const double* frames, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
@@ -182,6 +199,15 @@ int eas_event_window_search(const void* records, const int64_t* file_offsets, in
  * of neighbouring labels overlap): out int32 [B][Tm][2][H][W], zeroed by the call.  No host read of the ranges. */
 int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, int B, int Tm, int H, int W, int32_t* out,
                                    uint32_t* oob_count, eas_stream_t stream);
+/* eas_event_time_surface (Gen1's aggregation 'timesurface', tau: the reference's 50e3) for samples given as such record ranges (additive,
+ * ABI 9): out float64 [B][num_slices][2][H][W].  The records are decoded as eas_event_histogram_dat_ranges decodes them; the arithmetic is
+ * eas_event_time_surface's (the same device functions): uint32 window (t_last - t_first) / num_slices and slice ends as numpy's, latest = 0
+ * for a pixel no event touched, zero frames for an empty range or a window of zero length -- bit-identical to eas_event_time_surface on
+ * the decoded arrays of the same samples.  Events outside the sensor that would have been binned are dropped and counted in
+ * oob_count[0] (uint32, may be NULL).  The latest times are kept in the output's own 64-bit bins, zeroed by the call, and a finishing pass
+ * overwrites them in place: no workspace, no host read of the ranges.  tau <= 0 or NaN: EAS_ERR_INVALID_ARG. */
+int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* ranges, int B, int num_slices, int H, int W, double tau,
+                                        double* out, uint32_t* oob_count, eas_stream_t stream);
 
 /* Config-4 input (BASELINE configs[3]): RVT stacked histogram -> per-polarity counts on the model canvas.  Replaces
  * RVTGEN4Dataset.generate_slices(..., method='event_sum') (yolox/data/datasets/rvt_gen4.py:109-125: reshape
