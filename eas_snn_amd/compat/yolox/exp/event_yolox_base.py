@@ -178,10 +178,16 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'stacked_hist':       # opt-in: the 1 Mpx path (indices into a resident store -> augmented frames)
             from eas_snn_amd.data import SyntheticStackedHistLoader
             return SyntheticStackedHistLoader(self, batch_size)
+        if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
+            from eas_snn_amd.data import Gen1StoreLoader
+            return Gen1StoreLoader(self, batch_size)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):
         from eas_snn_amd.data import SyntheticEvalDataset
+        if getattr(self, 'train_input', None) == 'dat_store':
+            from eas_snn_amd.data import Gen1StoreDataset, gen1_store_for
+            return Gen1StoreDataset(self, gen1_store_for(self, 'test'))
         return SyntheticEvalDataset(self, length=int(getattr(self, 'eval_samples', 256)), n_events=int(getattr(self, 'eval_events', 200_000)))
 
     def get_eval_loader(self, batch_size, is_distributed, **kwargs):
@@ -198,6 +204,9 @@ class EventExp(BaseExp):
         n = len(valdataset)
         per_rank = (n + world - 1) // world                 # DistributedSampler pads with the first samples so every rank gets the same count
         idx = [(rank + k * world) % n for k in range(per_rank)]
+        if getattr(self, 'train_input', None) == 'dat_store':
+            from eas_snn_amd.data import Gen1StoreEvalLoader
+            return Gen1StoreEvalLoader(self, batch_size, idx, valdataset.store)
         # synthetic streams on the Gen1 sensor (or on the canvas itself when that is smaller); ``eval_sensor_hw`` / ``eval_events`` override
         sensor = getattr(self, 'eval_sensor_hw', None) or (min(240, self.test_size[0]), min(304, self.test_size[1]))
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)
@@ -205,8 +214,9 @@ class EventExp(BaseExp):
     def get_evaluator(self, batch_size, is_distributed, testdev=False, legacy=False):
         """reference: event_yolox_base.py:509-534.  ``eval_proph`` on a gen* dataset selects PSEEEvaluator (the Prophesee protocol,
         psee_evaluator.py) when the samples of the evaluation dataset carry their label time in their names (``<recording>a<time in us>``,
-        what the protocol matches on); the synthetic samples do not unless ``eval_label_period_us`` is set, and then EventEvaluator
-        answers, with a warning."""
+        what the protocol matches on): the samples of a ``train_input = 'dat_store'`` evaluation do (``<recording>_r<index>_a<time>``, the
+        reference's own names); the synthetic event samples do not unless ``eval_label_period_us`` is set, and then EventEvaluator answers,
+        with a warning."""
         from yolox.evaluators import EventEvaluator
         loader = self.get_eval_loader(batch_size, is_distributed, testdev=testdev, legacy=legacy)
         if 'gen' in str(self.data_name) and self.eval_proph not in (False, 'False', None, 0):

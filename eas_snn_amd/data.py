@@ -3,6 +3,9 @@
 Stream definition = BASELINE.md section 2 / SURVEY.md 8d: per sample ``n_events`` events over a 200 ms window
 on the 240x304 Gen1 sensor, ``t`` sorted uniform, ``x``,``y`` uniform, ``p`` Bernoulli(0.5), numpy default_rng.
 Raw events (9 B/event) are what crosses PCIe; binning (K1) and canvas padding run on the GPU.
+
+Further down: the augmentation draws, the N-Caltech101 and 1 Mpx chains, and Gen1 from recordings resident in HBM (``Gen1Store`` and its
+loaders: ``.dat`` / ``_bbox.npy`` pairs read once, or seeded synthetic recordings).
 """
 import numpy as np
 import torch
@@ -450,3 +453,283 @@ def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggr
         return ops.frames_letterbox(surf, params_on(params, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
     counts = ops.event_histogram_dat_ranges(records, ranges, Tm, H, W)
     return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+
+
+# ------------------------------------------------------------------------------------------------ Gen1 from recordings resident in HBM
+def parse_dat_header(buf):
+    """(offset of the first event record, event type, event size) of a Prophesee ``.dat`` file image (bytes or a uint8 array), as the
+    reference's reader finds them (psee_loader/io/dat_events_tools.py parse_header): text lines that begin with ``'% '`` form the header; if
+    there was at least one, two bytes follow it (event type, event size in bytes); a file without header lines holds type 0 / size 8
+    records from its first byte."""
+    raw = buf.tobytes() if isinstance(buf, np.ndarray) else bytes(buf)
+    pos, lines = 0, 0
+    while raw[pos:pos + 2] == b'% ':
+        end = raw.find(b'\n', pos)
+        lines += 1
+        if end < 0:                      # a header line without an end: nothing follows it
+            pos = len(raw)
+            break
+        pos = end + 1
+    if lines == 0:
+        return pos, 0, 8
+    return pos + 2, int(raw[pos]), int(raw[pos + 1])
+
+
+def encode_dat(t, x, y, p, height=240, width=304):
+    """Events -> the byte image of a ``.dat`` recording (uint8 array): the text header, the type / size bytes (0, 8) and one 8-byte record
+    per event (uint32 time in us, then x in bits 0..13, y in bits 14..27 and the polarity in bit 28 of a second uint32)."""
+    head = ('% Data file containing Event2D events.\n% Version 2\n% Date 2024-1-1 0:0:0\n'
+            f'% Height {height}\n% Width {width}\n').encode('latin-1') + bytes([0, 8])
+    rec = np.empty((len(t), 2), dtype='<u4')
+    rec[:, 0] = t
+    rec[:, 1] = (np.asarray(x, np.uint32) & 16383) | ((np.asarray(y, np.uint32) & 16383) << 14) | ((np.asarray(p, np.uint32) & 1) << 28)
+    return np.concatenate([np.frombuffer(head, dtype=np.uint8), rec.reshape(-1).view(np.uint8)])
+
+
+GEN1_BBOX_DTYPE = np.dtype([('t', '<u8'), ('x', '<f4'), ('y', '<f4'), ('w', '<f4'), ('h', '<f4'), ('class_id', 'u1'),
+                            ('class_confidence', '<f4'), ('track_id', '<u4')])
+
+
+def synth_gen1_recordings(n_files, labels_per_file, n_events=50_000, sensor_hw=(240, 304), label_period_us=50_000, num_classes=2, seed=0):
+    """``n_files`` seeded recordings ``(name, dat_bytes uint8, bbox_rows)`` as ``Gen1Store`` takes them, so that the store and its loaders
+    run without a dataset.  Events: ``t`` sorted uniform over the recording, ``x``, ``y`` uniform on the sensor, ``p`` Bernoulli(0.5).
+    Labels: ``labels_per_file`` distinct ascending times, ``label_period_us`` apart, the first one period after the first event; label k
+    carries 3, 0 surviving, 1, 2 boxes for k % 4 = 0, 1, 2, 3 -- the label without a survivor holds a box without area and one that lies
+    off the sensor, which no resize brings back."""
+    H, W = sensor_hw
+    out = []
+    for f in range(n_files):
+        rng = np.random.default_rng([seed, f])
+        t0 = 1_000_000 + 10_000 * f
+        span = (labels_per_file + 1) * label_period_us
+        t = np.sort(rng.integers(t0, t0 + span, size=n_events, dtype=np.int64))
+        x, y = rng.integers(0, W, size=n_events), rng.integers(0, H, size=n_events)
+        p = (rng.random(n_events) < 0.5).astype(np.int64)
+        rows = []
+        for k in range(labels_per_file):
+            lt = t0 + (k + 1) * label_period_us
+            if k % 4 == 1:
+                rows += [(lt, 0.4 * W, 0.5 * H, 0.0, 0.0, 0, 1.0, 0), (lt, -0.5 * W, 0.2 * H, 0.2 * W, 0.3 * H, 1 % num_classes, 1.0, 1)]
+                continue
+            for i in range((3, 0, 1, 2)[k % 4]):
+                bw, bh = rng.uniform(0.15, 0.4) * W, rng.uniform(0.15, 0.4) * H
+                bx, by = rng.uniform(-0.05, 0.9) * W, rng.uniform(-0.05, 0.9) * H
+                rows.append((lt, bx, by, bw, bh, int(rng.integers(0, num_classes)), 1.0, i))
+        out.append((f'synthetic_{seed}_{f:03d}', encode_dat(t, x, y, p, H, W), np.array(rows, dtype=GEN1_BBOX_DTYPE)))
+    return out
+
+
+class Gen1Store:
+    """Gen1 recordings and their labels resident on the device: what GEN1Dataset keeps on disk and in host lists (gen1.py:43-85), as tables
+    that the kernels index.  ``recordings``: a list of ``(name, dat_bytes, bbox_rows)`` -- the byte image of ``<name>_td.dat`` and the
+    structured array of ``<name>_bbox.npy`` (fields ``t`` or ``ts``, ``x``, ``y``, ``w``, ``h``, ``class_id``); names in ``ignore`` are left
+    out.  ``Tl``: macro slices per sample (the reference's ``num_slice``); ``window`` = (lo, hi) in us relative to the label time
+    (``EventExp.get_slice_args``: ``(window * 1000, 0)``).
+
+    Built once on the host and uploaded once: ``records`` uint8 (the record areas back to back), ``file_offsets`` int64 [F + 1] (record index
+    of every recording's first event), ``boxes`` float32 [L, 5] rows (x1, y1, x2, y2, class) (``raw_bboxes``, gen1.py:169-170),
+    ``group_start`` int64 [G + 1], ``group_t`` int64 [G] and ``group_file`` int32 [G]: a label group is the rows of one recording that share
+    a time, in ascending time (extract_labels, gen1.py:282-298; a descending time raises ValueError).  On the host: ``sample_names``
+    ``<name>_r<index>_a<t>`` (get_sample_resp, gen1.py:213-215), ``max_group_rows`` and numpy copies of the tables (``host``).  The flat
+    sample index is the group index: recordings in the order given, groups in time order (resolve_index, gen1.py:263-267, with
+    ``continuous=True`` as EventExp builds the dataset: no leading groups are dropped).
+
+    A store holds the recordings it is given; cutting a dataset that exceeds HBM into shards is the caller's business."""
+
+    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304)):
+        self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
+        self.names, self.sample_names = [], []
+        areas, file_offsets, boxes, group_start, group_t, group_file = [], [0], [], [0], [], []
+        for name, dat, rows in recordings:
+            if name in ignore:
+                continue
+            buf = np.frombuffer(dat, dtype=np.uint8) if isinstance(dat, (bytes, bytearray, memoryview)) else np.asarray(dat, dtype=np.uint8)
+            start, _, ev_size = parse_dat_header(buf)
+            if ev_size != 8 or (len(buf) - start) % 8 != 0:
+                raise ValueError(f'{name}: not a .dat recording of 8-byte event records (event size {ev_size}, {len(buf) - start} bytes)')
+            f = len(self.names)
+            self.names.append(name)
+            areas.append(buf[start:])
+            file_offsets.append(file_offsets[-1] + (len(buf) - start) // 8)
+            t = np.asarray(rows['t' if 't' in rows.dtype.names else 'ts']).astype(np.int64)
+            if (np.diff(t) < 0).any():
+                raise ValueError(f'{name}: the label times are not ascending')
+            boxes.append(np.stack([rows['x'], rows['y'], rows['x'] + rows['w'], rows['y'] + rows['h'], rows['class_id']], axis=-1)
+                         .astype(np.float32).reshape(-1, 5))
+            first = np.flatnonzero(np.r_[True, np.diff(t) > 0]) if len(t) else np.zeros(0, dtype=np.int64)
+            for k, a in enumerate(first):
+                self.sample_names.append(f'{name}_r{k}_a{int(t[a])}')
+            group_t += [int(t[a]) for a in first]
+            group_file += [f] * len(first)
+            base = group_start[-1]                              # rows of the recordings in front
+            group_start += [base + int(e) for e in np.r_[first[1:], len(t)]] if len(first) else []
+        self.host = dict(file_offsets=np.asarray(file_offsets, dtype=np.int64),
+                         boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
+                         group_start=np.asarray(group_start, dtype=np.int64), group_t=np.asarray(group_t, dtype=np.int64),
+                         group_file=np.asarray(group_file, dtype=np.int32))
+        self.group_rows = np.diff(self.host['group_start'])
+        self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
+        self.device = torch.device(device)
+        self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
+        for k, v in self.host.items():
+            setattr(self, k, torch.from_numpy(v).to(self.device))
+
+    @classmethod
+    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304)):
+        """the ``<name>_td.dat`` / ``<name>_bbox.npy`` pairs of the directories ``paths``, every directory in sorted order (the reference
+        takes them as ``os.listdir`` gives them), read with ``numpy.fromfile`` / ``numpy.load``"""
+        import os
+        recs = []
+        for path in ([paths] if isinstance(paths, str) else paths):
+            for fn in sorted(os.listdir(path)):
+                if fn.endswith('_bbox.npy'):
+                    name = fn[:-len('_bbox.npy')]
+                    if name not in ignore:
+                        recs.append((name, np.fromfile(os.path.join(path, name + '_td.dat'), dtype=np.uint8), np.load(os.path.join(path, fn))))
+        return cls(recs, Tl, window, device, sensor_hw=sensor_hw)
+
+    def __len__(self):
+        return len(self.sample_names)
+
+    def raw_labels(self, index):
+        """float32 [n, 5] rows (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands them out (``map_val``,
+        ``format='xywh'``, gen1.py:191-197: ``xyxy2xywh`` of the raw boxes -- not truncated, not transformed)"""
+        a, b = self.host['group_start'][index], self.host['group_start'][index + 1]
+        box = self.host['boxes'][a:b].copy()
+        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        return box
+
+    def frames(self, sample_idx, params, exp, canvas_hw=None):
+        """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): label time and recording gathered
+        on the device, ``ops.event_window_search`` for the ``Tl`` windows that end at the label (generate_slices with ``continuous``,
+        gen1.py:117-125), then ``dat_ranges_to_frames`` with the experiment's ``aggregation``; ``params``: (nw, nh, dx, dy, flip) per
+        sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back (graph-capturable)."""
+        B, Tl = sample_idx.numel(), self.Tl
+        step = self.window[1] - self.window[0]
+        shift = torch.arange(-Tl + 1, 1, dtype=torch.int64, device=self.device) * step
+        t = (self.group_t[sample_idx][:, None] + shift[None, :]).reshape(-1)
+        f = self.group_file[sample_idx][:, None].expand(B, Tl).reshape(-1)
+        ranges = ops.event_window_search(self.records, t, self.window, Tl, self.file_offsets, f)
+        par = params_on(params, self.device)[:, None, :].expand(B, Tl, 5).reshape(-1, 5)
+        Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
+        out = dat_ranges_to_frames(self.records, ranges, exp.Tm, self.sensor_hw, (Hc, Wc), par, aggregation=exp_aggregation(exp))
+        return out.reshape(B, Tl, exp.Tm, 2, Hc, Wc)
+
+    def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
+        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
+        box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
+        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
+                                 canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
+
+
+def gen1_store_for(exp, split='train', device=None):
+    """The store of an experiment with ``train_input = 'dat_store'``: ``Gen1Store.from_directories`` over ``exp.data_dir``/train + /val
+    (``split='test'``: /test) when that directory exists, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files, labels
+    per file, events per file), default (4, 16, 50000); the sensor is Gen1's, or the canvas where that is smaller).  Kept on the
+    experiment: one store per split."""
+    import os
+    cache = exp.__dict__.setdefault('_dat_stores', {})
+    if split not in cache:
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+        window = (exp.window * 1000, 0)
+        root = str(getattr(exp, 'data_dir', '') or '')
+        dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
+        if root and all(os.path.isdir(d) for d in dirs):
+            cache[split] = Gen1Store.from_directories(dirs, exp.Tl, window, device)
+        else:
+            n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
+            size = exp.test_size if split == 'test' else exp.input_size
+            sensor = (min(240, size[0]), min(304, size[1]))
+            recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
+            cache[split] = Gen1Store(recs, exp.Tl, window, device, sensor_hw=sensor)
+    return cache[split]
+
+
+class Gen1StoreDataset:
+    """what the trainer and the evaluators ask of a dataset, over a ``Gen1Store``: length, ``sample_names`` (they carry the label time the
+    Prophesee protocol reads), ``class_names``, ``map_val`` without random augmentation"""
+    map_val, random_aug = True, False
+
+    def __init__(self, exp, store):
+        self.exp, self.store, self.sample_names = exp, store, store.sample_names
+        self.class_names = [str(i) for i in range(exp.num_classes)]
+
+    def __len__(self):
+        return len(self.store)
+
+
+class Gen1StoreLoader:
+    """Training loader of Gen1 from a ``Gen1Store``: iterable of (frames [B, Tl, Tm, 2, Hc, Wc] fp32 on the GPU, targets [B, 50, 5] rows
+    (cls, cx, cy, w, h), zero padded).  An epoch is a permutation of the samples; per sample the draws come in the reference's order
+    (get_random_data, gen1.py:485-511): ``jitter_params(..., jitter=.3)``, then the permutation of its boxes, ``rng.permutation(n)`` -- the
+    order ``np.random.shuffle`` gives the rows under the same state.  ``batches(epoch)`` returns the draws of an epoch, a function of (seed,
+    epoch) alone; a step uploads them -- sample indices, params, box permutations -- and everything else happens on the device
+    (``store.frames``, ``store.targets``): no host read, no per-sample work.  ``store=None``: ``gen1_store_for(exp)``."""
+
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
+        exp_aggregation(exp)
+        self.store = store if store is not None else gen1_store_for(exp)
+        self.iters = len(self.store) // batch_size
+        assert self.iters >= 1, 'fewer labels than one batch'
+        self.dataset = Gen1StoreDataset(exp, self.store)
+        self.epoch = 0
+
+    def __len__(self):
+        return self.iters
+
+    def close_mosaic(self):
+        pass
+
+    def batches(self, epoch):
+        """[(sample indices int64 [B], params int32 [B, 5], box permutations int32 [B, P])] of an epoch; P = the store's largest group (at
+        least 1), a row of a smaller group is filled up with the identity"""
+        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
+        order = rs.permutation(len(self.store))
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
+        P = max(self.store.max_group_rows, 1)
+        out = []
+        for i in range(self.iters):
+            idx = order[i * self.batch_size:(i + 1) * self.batch_size].astype(np.int64)
+            par = np.empty((len(idx), 5), dtype=np.int32)
+            perm = np.tile(np.arange(P, dtype=np.int32), (len(idx), 1))
+            for b, s in enumerate(idx):
+                par[b] = jitter_params(H, W, Hc, Wc, jitter=.3, rng=rs)
+                n = int(self.store.group_rows[s])
+                perm[b, :n] = rs.permutation(n)
+            out.append((idx, par, perm))
+        return out
+
+    def __iter__(self):
+        dev = self.store.device
+        draws = self.batches(self.epoch)
+        self.epoch += 1
+        for idx, par, perm in draws:
+            idx, par, perm = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev), torch.from_numpy(perm).to(dev)
+            yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, perm, self.exp.input_size, self.max_labels)
+
+
+class Gen1StoreEvalLoader:
+    """Evaluation loader over a ``Gen1Store``: iterable of the tuple ``SyntheticEvalLoader`` yields -- ``(frames [B, Tl, Tm, 2, H, W] fp32
+    on the GPU, labels [B][n, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
+    get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``); the labels are the raw float32 rows of the store
+    (``Gen1Store.raw_labels``), prepared on the host once.  ``indices`` are this rank's samples; the last batch may be short."""
+
+    def __init__(self, exp, batch_size, indices, store):
+        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+        exp_aggregation(exp)
+        self.dataset = Gen1StoreDataset(exp, store)
+        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
+
+    def __len__(self):
+        return (len(self.indices) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
+        row = letterbox_params(H, W, Hc, Wc)
+        for b in range(len(self)):
+            ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
+            idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
+            frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
+            yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)

@@ -221,6 +221,36 @@ def stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=10, lo=None, params=None
     return (out, flags) if return_flags else out
 
 
+def label_targets(boxes, group_start, group, params, ih, iw, h, w, perm=None, max_labels=50, return_info=False):
+    """The label side of a training batch from a box table in HBM: ``targets`` fp32 [B, max_labels, 5] rows (cls, cx, cy, w, h), zero padded --
+    the box half of get_random_data (gen1.py:437, 459-468, 510-521), ``reformat('cxcywh')`` and EventTrainTransform for every sample in one
+    launch (``data.transform_boxes`` + centre form + padding).  ``boxes`` fp32 [L, 5] rows (x1, y1, x2, y2, class) on the ``ih`` x ``iw``
+    sensor; ``group_start`` int64 [G + 1]: rows group_start[g] .. group_start[g + 1] are label group g; ``group`` int64 [B]; ``params`` int32
+    [B, 5] = (nw, nh, dx, dy, flip) on the ``h`` x ``w`` canvas; ``perm`` int32 [B, P] (None: identity): row j of a sample's shuffled list is
+    row perm[b, j] of its group.  ``return_info``: also ``count`` int32 [B] (survivors before the cut at ``max_labels``) and ``flags`` int32
+    [B] (bit 0: a perm entry outside the group, row dropped; bit 1: more rows than P, the rest dropped; bit 2: group outside [0, G), no
+    rows).  Nothing is read back (graph-capturable)."""
+    _dev(boxes, group_start, group, params, perm)
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 5
+    assert group_start.dtype == torch.int64 and group_start.dim() == 1 and group_start.numel() >= 1
+    assert group.dtype == torch.int64 and group.dim() == 1
+    B = group.numel()
+    assert params.dtype == torch.int32 and params.shape == (B, 5)
+    boxes, group_start, group, params = boxes.contiguous(), group_start.contiguous(), group.contiguous(), params.contiguous()
+    P = 0
+    if perm is not None:
+        assert perm.dtype == torch.int32 and perm.dim() == 2 and perm.shape[0] == B
+        perm, P = perm.contiguous(), perm.shape[1]
+    targets = torch.empty((B, max_labels, 5), dtype=torch.float32, device=group.device)
+    count = torch.empty(B, dtype=torch.int32, device=group.device) if return_info else None
+    flags = torch.empty(B, dtype=torch.int32, device=group.device) if return_info else None
+    # bytes: at most P (or every) row of each group once + the targets
+    _call('eas_label_targets', 4 * targets.numel() + 24 * B * max(P, 1), _lib.lib().eas_label_targets, ptr(boxes), boxes.shape[0], ptr(group_start),
+          group_start.numel() - 1, ptr(group), ptr(params), ptr(perm), P, B, int(ih), int(iw), int(h), int(w), int(max_labels), ptr(targets),
+          ptr(count), ptr(flags), stream())
+    return (targets, count, flags) if return_info else targets
+
+
 def counts_to_canvas(counts, Hc, Wc):
     """int32 [..., H, W] -> float32 [..., Hc, Wc], zero padded bottom/right."""
     _dev(counts)

@@ -236,6 +236,27 @@ int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int 
 int eas_stacked_hist_frames(const uint8_t* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B,
                             int Tm, int nbins, int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream);
 
+/* The LABEL side of a training batch from a box table that stays in HBM (additive, ABI 9; csrc/labels.hip): the box half of
+ * GEN1Dataset.get_random_data (gen1.py:437, 459-468, 510-521; rvt_gen4.py:510-598 and ncaltech.py:272-366 are the same arithmetic), then
+ * reformat('cxcywh') (yolox/utils/boxes.py:131-136) and EventTrainTransform.__call__ (yolox/data/event_data_augment.py:19-65).
+ * boxes: f32 [L][5] rows (x1, y1, x2, y2, class) on the sensor (NULL only with L == 0); group_start: int64 [G + 1], rows group_start[g] ..
+ * group_start[g + 1] are the boxes of label group g (clamped into [0, L]); group: int64 [B], the group of every sample; params: int32 [B][5]
+ * rows (nw, nh, dx, dy, flip) as for eas_counts_letterbox; perm (int32 [B][P], nullable = identity): row j of sample b's shuffled list is
+ * row perm[b][j] of its group; ih, iw: the sensor; h, w: the canvas.  Per row: the five floats truncated toward zero to int64;
+ * x = (int64)((double)(x * nw) / (double)iw + (double)dx) for both corners (product in integers, one IEEE division, one addition, truncation
+ * toward zero), y likewise with nh, ih, dy; flipped: (x1, x2) = (w - x2, w - x1); x1, y1 clipped up to 0, x2 down to w, y2 down to h; rows
+ * with x2 - x1 > 1 and y2 - y1 > 1 survive, in the order of the list.
+ * targets: f32 [B][max_labels][5] rows (class, cx, cy, w, h) of the first max_labels survivors, cx = x1 + (x2 - x1) * 0.5 in float32, zero
+ * rows behind them: every element is written by the call.  count (int32 [B], nullable): survivors before the cut at max_labels.
+ * flags (int32 [B], nullable, every element written): bit 0 a perm entry outside [0, rows of the group) -- that row is dropped; bit 1 the
+ * group has more than P rows and perm is given -- the rows beyond P are dropped; bit 2 group[b] outside [0, G) -- the sample has no rows.
+ * EAS_ERR_INVALID_ARG without a launch: a NULL boxes (with L > 0), group_start, group, params or targets, a misaligned pointer,
+ * max_labels < 1, iw < 1, ih < 1, negative L, G, B or P.  B == 0 with sizes and alignments in order returns EAS_OK without a launch
+ * (the pointers of an empty batch may be NULL).  Bit-exact. */
+int eas_label_targets(const float* boxes, int64_t L, const int64_t* group_start, int G, const int64_t* group, const int32_t* params,
+                      const int32_t* perm, int P, int B, int ih, int iw, int h, int w, int max_labels, float* targets, int32_t* count,
+                      int32_t* flags, eas_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2  multi-step (P)LIF neuron.  Replaces spikingjelly ParametricLIFNode / LIFNode
  *     multi_step_forward (call site yolox/utils/utils_snn.py:44-53): per step
