@@ -396,8 +396,8 @@ class _DetLossFn(torch.autograd.Function):
         grads = ctx.grads
         if g_total is None:
             return (None,) * (4 + len(grads))
-        torch._foreach_mul_(grads, g_total * ctx.scale)
-        return (None, None, None, None) + tuple(grads)
+        # out of place: ctx.grads keep d(total * num_fg)/d(raw), so a second backward through a retained graph scales the same maps again
+        return (None, None, None, None) + tuple(torch._foreach_mul(grads, g_total * ctx.scale))
 
 
 def det_decode_eval_supported(raws):
