@@ -108,6 +108,7 @@ class EasAdamHyper(C.Structure):
 # name -> (restype, argtypes) ; one line per prototype of include/eas_hip.h
 ABI_VERSION = 9
 
+_ATIS_HEAD = [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4      # the ATIS entries up to Tl, Tm, H, W (then tau, or the frames)
 PROTOTYPES = {
     'eas_abi_version': (C.c_int, []),
     'eas_kernel_trace_begin': (None, []),
@@ -129,12 +130,12 @@ PROTOTYPES = {
     'eas_counts_letterbox': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     'eas_counts_letterbox_ex': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
     'eas_event_histogram_atis_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
-    'eas_event_histogram_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [_P] * 5),
+    'eas_event_histogram_atis': (C.c_int, _ATIS_HEAD + [_P] * 5),
     'eas_event_timesurface_atis_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     'eas_event_timesurface_atis_capacity': (C.c_int64, []),
-    'eas_event_timesurface_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_double] + [_P] * 5),
+    'eas_event_timesurface_atis': (C.c_int, _ATIS_HEAD + [C.c_double] + [_P] * 5),
     'eas_frames_letterbox_f64': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
-    'eas_event_latest_surface_atis': (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_double] + [_P] * 5),
+    'eas_event_latest_surface_atis': (C.c_int, _ATIS_HEAD + [C.c_double] + [_P] * 5),
     'eas_event_latest_surface_dat_ranges': (C.c_int, [_P, _P] + [C.c_int] * 4 + [C.c_double, _P, _P, _P]),
     'eas_postprocess_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'eas_postprocess': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P]),

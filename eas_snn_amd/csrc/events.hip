@@ -3,12 +3,15 @@
 // (u32 t + u16 x + u16 y + u8 p) + 4*Tm*2*H*W B for the frames (zero-fill + result).
 // One thread handles 4 consecutive events (16-B / 8-B / 8-B / 4-B vector loads); the atomics are
 // int32 `global_atomic_add` without return, so results are bit-exact and order independent.
+// Every source (decoded arrays, .dat records with offsets, .dat record ranges) sends an event to its bin, a count or a latest time, by one route:
+// bin_event<Acc> (event_bin.h).  Record ranges: one walk, dat_ranges_kernel<Acc>, behind one host template, dat_ranges_frames<Acc>.
 #include <stdlib.h>
 
 #include <string.h>
 
 #include "eas_common.h"
 #include "count_resize.h"
+#include "event_bin.h"
 #include "latest_surface.h"
 
 namespace {
@@ -23,36 +26,15 @@ __device__ __forceinline__ int find_sample(const int64_t* __restrict__ offsets, 
     return lo;
 }
 
-struct SampleWin {
-    uint32_t t0;
-    uint32_t win;  // 0 -> nothing is binned
-};
-
-// the one micro-slice window rule (gen1.py:313-328): t0 = first timestamp of the range, win = (last - first) / Tm, integer floor
-__device__ __forceinline__ SampleWin make_window(uint32_t t_first, uint32_t t_last, int Tm) {
-    SampleWin w;
-    w.t0 = t_first;
-    w.win = (t_last - t_first) / (uint32_t)Tm;
-    return w;
-}
-
 __device__ __forceinline__ SampleWin sample_window(const uint32_t* __restrict__ t, const int64_t* __restrict__ offsets,
                                                    int b, int Tm) {
     return make_window(t[offsets[b]], t[offsets[b + 1] - 1], Tm);
 }
 
+// the count's reading of the polarity byte: p != 0 is channel 1
 __device__ __forceinline__ void bin_one(uint32_t tt, uint32_t xx, uint32_t yy, uint32_t pp, const SampleWin& w, int b,
                                         int Tm, int H, int W, int32_t* __restrict__ out, uint32_t* __restrict__ oob) {
-    if (w.win == 0) return;
-    const uint32_t k = (tt - w.t0) / w.win;
-    if (k >= (uint32_t)Tm) return;  // tail beyond t0 + Tm*win is dropped (gen1.py:321-326)
-    if (xx >= (uint32_t)W || yy >= (uint32_t)H) {
-        if (oob) atomicAdd(oob, 1u);
-        return;
-    }
-    const int c = pp != 0 ? 1 : 0;
-    const int64_t idx = ((((int64_t)b * Tm + k) * 2 + c) * H + yy) * W + xx;
-    atomicAdd(out + idx, 1);
+    bin_event(tt, xx, yy, pp != 0 ? 1u : 0u, w, b, Tm, H, W, out, oob, CountAcc{});
 }
 
 template <bool VEC4>
@@ -205,19 +187,33 @@ __global__ __launch_bounds__(EAS_WAVE) void event_window_search_kernel(const uin
     ranges[2 * b + 1] = base + e;
 }
 
-// micro-slice count frames of arbitrary (possibly overlapping) record ranges: blockIdx.y = sample, blocks stride over its range
-__global__ __launch_bounds__(EAS_BLOCK) void event_hist_dat_ranges_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges,
-                                                                          int Tm, int H, int W, int32_t* __restrict__ out,
-                                                                          uint32_t* __restrict__ oob) {
+// Samples given as arbitrary (possibly overlapping) record ranges of a .dat image: blockIdx.y = sample, blocks stride over its range; nothing
+// is read back.  ``Acc`` (event_bin.h) is the only difference between the entries: CountAcc -> micro-slice count frames, LatestAcc -> the
+// latest times in the output's own 64-bit bins (eas_event_latest_surface_dat_ranges, finished by latest_finish_kernel).
+template <typename Acc>
+__global__ __launch_bounds__(EAS_BLOCK) void dat_ranges_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges, int ns, int H,
+                                                               int W, typename Acc::Bin* __restrict__ out, uint32_t* __restrict__ oob,
+                                                               const Acc acc) {
     const int b = blockIdx.y;
     const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
     if (e <= a) return;
-    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, Tm);
+    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, ns);
     for (int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
         const uint2 v = rec[i];
-        bin_dat(v.x, v.y, w, b, Tm, H, W, out, oob);
+        bin_event(v.x, v.y & 16383u, (v.y >> 14) & 16383u, (v.y >> 28) & 1u, w, b, ns, H, W, out, oob, acc);
     }
 }
+
+// the window of sample b of such ranges, for the finishing pass (latest_surface.h latest_finish_kernel)
+struct DatRangesWin {
+    const uint2* rec; const int64_t* ranges; int ns;
+    __device__ __forceinline__ void operator()(int b, uint32_t& t0, uint32_t& win) const {
+        const uint2* r = rec;
+        const SampleWin w = sample_window_of(ranges[2 * b], ranges[2 * b + 1], [r](int64_t i) { return r[i].x; }, ns);
+        t0 = w.t0;
+        win = w.win;
+    }
+};
 
 // LDS-privatised form of the histogram for streams with many events per frame: one block owns one (sample, micro-slice,
 // band of rows) and keeps that band's two polarity planes in LDS (<= 150 KB).  The events of a micro-slice are a
@@ -533,28 +529,16 @@ __global__ __launch_bounds__(EAS_BLOCK) void voxel_cube_kernel(const uint32_t* _
 // Pass 1: latest timestamp per (sample, slice, polarity, pixel) by integer atomic max (timestamps ascend, so the
 // maximum is the reference's "last write wins").  Pass 2: running maximum over the slices, then
 // exp(-((i + 1) * window + t0 - latest) / tau) in float64; untouched pixels keep latest = 0 exactly like the reference.
-// Both steps live in latest_surface.h; ``latest_one`` is the event's way to its bin, for decoded arrays and for .dat records.
-template <typename Bin>
-__device__ __forceinline__ void latest_one(uint32_t tt, uint32_t xx, uint32_t yy, uint32_t pp, const SampleWin& w, int b, int ns, int H, int W,
-                                           Bin* __restrict__ latest, uint32_t* __restrict__ oob) {
-    if (w.win == 0) return;
-    const uint32_t k = (tt - w.t0) / w.win;
-    if (k >= (uint32_t)ns) return;
-    if (xx >= (uint32_t)W || yy >= (uint32_t)H) {
-        if (oob) atomicAdd(oob, 1u);
-        return;
-    }
-    if (pp > 1u) return;
-    latest_time_max(latest + ((((int64_t)b * ns + k) * 2 + pp) * H + yy) * W + xx, tt);
-}
-
+// Both steps live in latest_surface.h; the event goes to its bin by the route of the counts (event_bin.h bin_event).
 __global__ __launch_bounds__(EAS_BLOCK) void time_surface_scatter_kernel(const uint32_t* __restrict__ t, const uint16_t* __restrict__ x,
                                                                          const uint16_t* __restrict__ y, const uint8_t* __restrict__ p,
                                                                          int64_t nev, const int64_t* __restrict__ offsets, int B,
                                                                          int ns, int H, int W, uint32_t* __restrict__ latest) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nev; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = find_sample(offsets, B, i);
-        latest_one(t[i], x[i], y[i], p[i], sample_window(t, offsets, b, ns), b, ns, H, W, latest, nullptr);
+        const uint32_t pp = p[i];
+        if (pp > 1u) continue;  // to_timesurface_numpy indexes its two planes by p: a polarity byte above 1 has no plane (the count: p != 0 is channel 1)
+        bin_event(t[i], x[i], y[i], pp, sample_window(t, offsets, b, ns), b, ns, H, W, latest, nullptr, LatestAccT<uint32_t>{});
     }
 }
 
@@ -565,39 +549,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void time_surface_exp_kernel(const uint3
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)(i / plane);
         const int64_t first = (int64_t)b * ns * plane + (i - (int64_t)b * plane);
-        SampleWin w{0u, 0u};                        // no events, or a window of zero length (invalid input): zeros
-        if (offsets[b + 1] > offsets[b]) w = sample_window(t, offsets, b, ns);
+        const SampleWin w = sample_window_of(offsets[b], offsets[b + 1], [t](int64_t j) { return t[j]; }, ns);   // (0, 0) or win == 0: zeros
         surface_walk(w.t0, w.win, ns, tau, [latest, first, plane](int k) { return latest[first + k * plane]; },
                      [out, first, plane](int k, double v) { out[first + k * plane] = v; });
-    }
-}
-
-// The same surfaces for samples given as record ranges of a .dat image (eas_event_latest_surface_dat_ranges): blockIdx.y = sample, blocks
-// stride over its range (ranges overlap; nothing is read back); the latest times go into the output's own 64-bit bins.
-__global__ __launch_bounds__(EAS_BLOCK) void latest_dat_ranges_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges, int ns,
-                                                                      int H, int W, unsigned long long* __restrict__ bins,
-                                                                      uint32_t* __restrict__ oob) {
-    const int b = blockIdx.y;
-    const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
-    if (e <= a) return;
-    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, ns);
-    for (int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint2 v = rec[i];
-        latest_one(v.x, v.y & 16383u, (v.y >> 14) & 16383u, (v.y >> 28) & 1u, w, b, ns, H, W, bins, oob);
-    }
-}
-
-// in place: one thread per (sample, polarity, pixel), adjacent lanes on adjacent pixels, the micro slices 2 * H * W bins apart
-__global__ __launch_bounds__(EAS_BLOCK) void latest_dat_ranges_finish_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges,
-                                                                             int B, int ns, int H, int W, double tau,
-                                                                             unsigned long long* __restrict__ bins) {
-    const int64_t plane = (int64_t)2 * H * W, total = (int64_t)B * plane;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)(i / plane);
-        const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
-        SampleWin w{0u, 0u};
-        if (e > a) w = make_window(rec[a].x, rec[e - 1].x, ns);
-        surface_walk_in_place(bins + (int64_t)b * ns * plane + (i - (int64_t)b * plane), plane, w.t0, w.win, ns, tau);
     }
 }
 
@@ -717,6 +671,20 @@ int histogram_impl(const uint32_t* t, const uint16_t* x, const uint16_t* y, cons
     return EAS_OK;
 }
 
+// The two entries for record ranges: one argument rule, the bins zeroed, one launch.  The ranges live on the device (no host read): a fixed
+// number of blocks per sample strides over whatever it holds; the sample is a block's y index, hence the bound on B.
+template <typename Acc>
+int dat_ranges_frames(const void* records, const int64_t* ranges, int B, int ns, int H, int W, typename Acc::Bin* out, uint32_t* oob_count,
+                      const Acc& acc, hipStream_t st) {
+    if (!records || !ranges || !out || B < 1 || ns < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7)) return EAS_ERR_INVALID_ARG;
+    if (B > 65535) return EAS_ERR_UNSUPPORTED;
+    EAS_CLEAR_ERR();
+    if (!zero_counts((int32_t*)out, (size_t)B * ns * 2 * H * W * sizeof(typename Acc::Bin), oob_count, st)) return EAS_ERR_LAUNCH;
+    EAS_LAUNCH(dat_ranges_kernel<Acc>, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, ns, H, W, out, oob_count, acc);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -750,29 +718,18 @@ int eas_event_window_search(const void* records, const int64_t* file_offsets, in
 
 int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, int B, int Tm, int H, int W, int32_t* out, uint32_t* oob_count,
                                    eas_stream_t stream) {
-    if (!records || !ranges || !out || B < 1 || Tm < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7)) return EAS_ERR_INVALID_ARG;
-    hipStream_t st = eas_s(stream);
-    EAS_CLEAR_ERR();
-    if (!zero_counts(out, (size_t)B * Tm * 2 * H * W * sizeof(int32_t), oob_count, st)) return EAS_ERR_LAUNCH;
-    // the ranges live on the device (no host read): a fixed number of blocks per sample strides over whatever it holds
-    EAS_LAUNCH(event_hist_dat_ranges_kernel, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, Tm, H, W, out, oob_count);
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
+    return dat_ranges_frames(records, ranges, B, Tm, H, W, out, oob_count, CountAcc{}, eas_s(stream));
 }
 
 int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* ranges, int B, int num_slices, int H, int W, double tau, double* out,
                                         uint32_t* oob_count, eas_stream_t stream) {
-    if (!records || !ranges || !out || B < 1 || num_slices < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7) || !(tau > 0.0))
-        return EAS_ERR_INVALID_ARG;                // !(tau > 0): also NaN
-    if (B > 65535) return EAS_ERR_UNSUPPORTED;     // the sample is a block's y index
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;  // also NaN
     hipStream_t st = eas_s(stream);
-    EAS_CLEAR_ERR();
     unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
-    if (!zero_counts((int32_t*)out, (size_t)B * num_slices * 2 * H * W * sizeof(double), oob_count, st)) return EAS_ERR_LAUNCH;
-    EAS_LAUNCH(latest_dat_ranges_kernel, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, num_slices, H, W, bins, oob_count);
-    EAS_CHECK_LAUNCH();
-    EAS_LAUNCH(latest_dat_ranges_finish_kernel, dim3(eas_grid_1d((int64_t)B * 2 * H * W)), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, B,
-               num_slices, H, W, tau, bins);
+    const int launched = dat_ranges_frames(records, ranges, B, num_slices, H, W, bins, oob_count, LatestAcc{}, st);
+    if (launched != EAS_OK) return launched;
+    EAS_LAUNCH(latest_finish_kernel<DatRangesWin>, dim3(eas_grid_1d((int64_t)B * 2 * H * W)), dim3(EAS_BLOCK), 0, st, (int64_t)B, num_slices, H, W,
+               tau, bins, DatRangesWin{(const uint2*)records, ranges, num_slices});
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -12,15 +12,15 @@
 //                                   event (binary searches over decoded records; a probe's time = raw + 8192 * (chunk base + in-chunk
 //                                   count - the recording's own base)) -> one AtisHead per recording, one AtisSlice per macro slice
 //   4. atis_hist_kernel             blocks stride over the chunks of a recording: decode in registers, block scan of the overflow
-//                                   records of the chunk, window / macro slice / micro slice (the SampleWin rule of events.hip bin_one),
+//                                   records of the chunk, window / macro slice / micro slice (the SampleWin rule of event_bin.h bin_event),
 //                                   integer atomics -- bit-exact in any order.  The accumulate step is the kernel's template
-//                                   parameter, the only difference between the two measures: CountAcc adds 1 to an int32 bin,
+//                                   parameter, the only difference between the two measures: CountAcc (event_bin.h) adds 1 to an int32 bin,
 //                                   TimeSurfaceAcc adds llrint(w * 2^48), w = 1 - tanh((t_target - t) / tau) in fp64 with t_target =
 //                                   the time of the macro slice's last member event (a plan row), to a 64-bit bin
 //   5. atis_ts_finish_kernel        (time surface only) the 64-bit sums, in place, -> double * 2^-48
 //   aggregation 'timesurface' (eas_event_latest_surface_atis; agrregate('timesurface'), ncaltech.py:255-257 + to_timesurface_numpy,
 //   event_reps.py:141-160, tau = 10e3) is a third accumulate step and a finishing pass of its own: LatestAcc takes the integer atomic max
-//   of the event's time into the OUTPUT's 64-bit bin of its micro slice; atis_latest_finish_kernel, one thread per (recording, macro slice,
+//   of the event's time into the OUTPUT's 64-bit bin of its micro slice; latest_finish_kernel<AtisSliceWin>, one thread per (recording, macro slice,
 //   polarity, pixel), walks the Tm bins with a running maximum m and overwrites each with exp(-((q + 1) * w + f - m) / tau), f and w read
 //   from the plan's row (latest_surface.h).  Plan flag bit 3: a macro slice that holds events has micro window 0 (the reference raises).
 // Time-surface sums are integers, so the frames do not depend on the order of the adds: bit-identical run to run, for any grid and any
@@ -34,6 +34,7 @@
 #include <limits.h>
 
 #include "eas_common.h"
+#include "event_bin.h"
 #include "latest_surface.h"
 
 namespace {
@@ -233,11 +234,8 @@ __device__ __forceinline__ uint64_t load_record(const uint8_t* __restrict__ rec,
     return (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24) | ((uint64_t)p[4] << 32);
 }
 
-// ---- the accumulate step of the histogram: what an event of time t in macro slice `row` (= b * Tl + k) adds to its bin
-struct CountAcc {                       // measure 'count': 1
-    typedef int32_t Bin;
-    __device__ __forceinline__ void operator()(Bin* bin, int64_t, uint32_t) const { atomicAdd(bin, 1); }
-};
+// ---- the accumulate step of the histogram: what an event of time t in macro slice `row` (= b * Tl + k) adds to its bin.  CountAcc (measure
+// 'count') and LatestAcc (aggregation 'timesurface') are event_bin.h's, shared with the Gen1 sources; the time-surface measure is ATIS-only
 struct TimeSurfaceAcc {                 // measure 'timesurface' (decay 'tanh'): 1 - tanh((t_target - t) / tau) in units of 2^-48
     typedef unsigned long long Bin;
     const uint32_t* t_target;           // [B * Tl], written by the plan
@@ -301,11 +299,6 @@ __global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __rest
     }
 }
 
-struct LatestAcc {                      // aggregation 'timesurface': the latest time of the bin (latest_surface.h), finished by atis_latest_finish_kernel
-    typedef unsigned long long Bin;
-    __device__ __forceinline__ void operator()(Bin* bin, int64_t, uint32_t t) const { latest_time_max(bin, t); }
-};
-
 // the frames are zeroed by a kernel of the call's own (16-byte stores; torch hands out 16-byte aligned frames, a scalar loop otherwise)
 __global__ __launch_bounds__(EAS_BLOCK) void atis_zero_kernel(int32_t* __restrict__ out, int64_t n) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
@@ -323,18 +316,15 @@ __global__ __launch_bounds__(EAS_BLOCK) void atis_ts_finish_kernel(unsigned long
         bins[i] = __builtin_bit_cast(unsigned long long, (double)bins[i] * (1.0 / kTsOne));
 }
 
-// the latest-time surface's finishing pass, in place: one thread per (recording, macro slice, polarity, pixel), adjacent lanes on adjacent
-// pixels, the Tm micro slices 2 * H * W bins apart; f and w come from the plan's row (w == 0: an empty macro slice or a micro window of zero
-// length -- nothing was binned, the frames are zeros)
-__global__ __launch_bounds__(EAS_BLOCK) void atis_latest_finish_kernel(const AtisSlice* __restrict__ slices, int64_t nrows, int Tm, int H, int W,
-                                                                       double tau, unsigned long long* __restrict__ bins) {
-    const int64_t plane = (int64_t)2 * H * W, total = nrows * plane;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / plane;
+// the latest-time surface's finishing pass (latest_surface.h) takes f and w of a row from the plan (w == 0: nothing was binned, zero frames)
+struct AtisSliceWin {
+    const AtisSlice* slices;
+    __device__ __forceinline__ void operator()(int row, uint32_t& t0, uint32_t& win) const {
         const AtisSlice s = slices[row];
-        surface_walk_in_place(bins + row * Tm * plane + (i - row * plane), plane, s.f, s.w, Tm, tau);
+        t0 = s.f;
+        win = s.w;
     }
-}
+};
 
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t chunks_of(int64_t nrec) { return (nrec + kChunk - 1) / kChunk; }
@@ -454,7 +444,8 @@ int eas_event_latest_surface_atis(const void* records, int64_t nrec, const int64
     if (launched != EAS_OK) return launched;
     const AtisSlice* slices = (const AtisSlice*)((char*)workspace + AtisWorkspace(nrec, B, Tl).slices);
     const int64_t nrows = (int64_t)B * Tl;
-    EAS_LAUNCH(atis_latest_finish_kernel, dim3(eas_grid_1d(nrows * 2 * H * W)), dim3(EAS_BLOCK), 0, st, slices, nrows, Tm, H, W, tau, bins);
+    EAS_LAUNCH(latest_finish_kernel<AtisSliceWin>, dim3(eas_grid_1d(nrows * 2 * H * W)), dim3(EAS_BLOCK), 0, st, nrows, Tm, H, W, tau, bins,
+               AtisSliceWin{slices});
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -7,7 +7,8 @@
 //                     (the reference does not clear its memory between micro slices), and per slice
 //                     exp(-((k + 1) * win + t0 - m) / tau) in float64; an untouched pixel keeps m = 0 exactly like the reference.
 // The two record entries keep the latest times in the OUTPUT's own 64-bit bins (zeroed by the call) and the walk overwrites every bin, after it
-// has read it, with the double it becomes: no workspace the size of the frames, and a bin is read and written by the same thread only.
+// has read it, with the double it becomes: no workspace the size of the frames, and a bin is read and written by the same thread only.  Their
+// finishing pass is latest_finish_kernel<RowWin> (below).
 #pragma once
 #include "eas_common.h"
 
@@ -40,4 +41,19 @@ __device__ __forceinline__ void surface_walk(uint32_t t0, uint32_t win, int ns, 
 __device__ __forceinline__ void surface_walk_in_place(unsigned long long* bins, int64_t stride, uint32_t t0, uint32_t win, int ns, double tau) {
     surface_walk(t0, win, ns, tau, [bins, stride](int k) { return (uint32_t)bins[k * stride]; },
                  [bins, stride](int k, double v) { bins[k * stride] = __builtin_bit_cast(unsigned long long, v); });
+}
+
+// The finishing pass of the record entries, in place over bins [rows][ns][2][H][W]: one thread per (row, polarity, pixel), adjacent lanes on
+// adjacent pixels, the ns micro slices 2 * H * W bins apart.  ``win(row, t0, w)`` gives a row's first time and micro window: DatRangesWin
+// (events.hip; row = sample: its range's two record times, (0, 0) when empty) or AtisSliceWin (events_atis.hip; row = the plan's AtisSlice).
+template <typename RowWin>
+__global__ __launch_bounds__(EAS_BLOCK) void latest_finish_kernel(int64_t nrows, int ns, int H, int W, double tau, unsigned long long* __restrict__ bins,
+                                                                  const RowWin win) {
+    const int64_t plane = (int64_t)2 * H * W, total = nrows * plane;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int row = (int)(i / plane);          // (the entries bound their rows far below 2^31)
+        uint32_t t0, w;
+        win(row, t0, w);
+        surface_walk_in_place(bins + (int64_t)row * ns * plane + (i - (int64_t)row * plane), plane, t0, w, ns, tau);
+    }
 }

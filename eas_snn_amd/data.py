@@ -55,16 +55,17 @@ def unscaled_params(batch, sensor_hw, device):
     return par
 
 
+def _letterboxed(frames, params, canvas_hw, interp='linear'):
+    """int32 counts or float64 frames [B, ..., H, W] -> fp32 canvas frames: ``ops.counts_letterbox`` / ``ops.frames_letterbox`` by dtype"""
+    op = ops.counts_letterbox if frames.dtype == torch.int32 else ops.frames_letterbox
+    return op(frames, params_on(params, frames.device), canvas_hw[0], canvas_hw[1], interp=interp)
+
+
 def events_to_frames(ev_dev, Tm, sensor_hw, canvas_hw, aggregation='micro_sum', tau=50e3):
     """Device events -> model input [B, Tl=1, Tm, 2, Hc, Wc] fp32 via the HIP histogram (K1).  ``aggregation='timesurface'``: Gen1's
     exponential time surfaces instead (``ops.event_time_surface`` with ``tau`` in us, gen1.py:362-369), placed like the counts: scale 1,
     top left, zero padding (``ops.frames_letterbox`` with ``unscaled_params``).  Any other value raises ValueError."""
-    H, W = sensor_hw
-    if check_aggregation(aggregation) == 'timesurface':
-        surf = ops.event_time_surface(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, tau=tau)
-        return ops.frames_letterbox(surf, unscaled_params(surf.shape[0], sensor_hw, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
-    frames = ops.event_frames(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, canvas_hw[0], canvas_hw[1])
-    return frames.unsqueeze(1)
+    return events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, None, aggregation=aggregation, tau=tau)
 
 
 def synth_targets(batch, canvas_hw, device, n_boxes=2, max_labels=50):
@@ -290,15 +291,15 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
             aggregation = getattr(e, 'aggregation', None)
     if check_aggregation('micro_sum' if aggregation is None else aggregation) == 'timesurface':
         frames = ops.event_latest_surface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=surface_tau)
-        return ops.frames_letterbox(frames, params_on(params, frames.device), Hc, Wc, interp=interp)
+        return _letterboxed(frames, params, (Hc, Wc), interp)
     measure = 'count' if measure is None else measure
     if measure not in ATIS_MEASURES:
         raise ValueError(f"measure {measure!r}: the N-Caltech101 front end has {' and '.join(repr(m) for m in ATIS_MEASURES)}")
     if measure == 'timesurface':
         frames = ops.event_timesurface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=tau)
-        return ops.frames_letterbox(frames, params_on(params, frames.device), Hc, Wc, interp=interp)
-    counts = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
-    return ops.counts_letterbox(counts, params_on(params, counts.device), Hc, Wc, interp=interp)
+    else:
+        frames = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
+    return _letterboxed(frames, params, (Hc, Wc), interp)
 
 
 # ------------------------------------------------------------------------------------------------ 1 Mpx (RVT stacked histograms)
@@ -434,11 +435,14 @@ def events_to_frames_augmented(ev_dev, Tm, sensor_hw, canvas_hw, params, aggrega
     (nw, nh, dx, dy, flip) rows.  ``aggregation='timesurface'``: ``ops.event_time_surface`` with ``tau`` (us) in place of the histogram,
     then ``ops.frames_letterbox`` (linear, as Gen1 resizes); any value but the two of ``FRAME_AGGREGATIONS`` raises ValueError."""
     H, W = sensor_hw
+    ev = ev_dev and (ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'])
     if check_aggregation(aggregation) == 'timesurface':
-        surf = ops.event_time_surface(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W, tau=tau)
-        return ops.frames_letterbox(surf, params_on(params, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
-    counts = ops.event_histogram(ev_dev['t'], ev_dev['x'], ev_dev['y'], ev_dev['p'], ev_dev['offsets'], Tm, H, W)
-    return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+        frames = ops.event_time_surface(*ev, Tm, H, W, tau=tau)
+    elif params is None:                     # the counts at scale 1, top left: histogram and canvas in one call
+        return ops.event_frames(*ev, Tm, H, W, canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+    else:
+        frames = ops.event_histogram(*ev, Tm, H, W)
+    return _letterboxed(frames, unscaled_params(frames.shape[0], sensor_hw, frames.device) if params is None else params, canvas_hw).unsqueeze(1)
 
 
 def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggregation='micro_sum', tau=50e3):
@@ -449,10 +453,10 @@ def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggr
     ValueError.  ``params``: per-sample (nw, nh, dx, dy, flip) rows, a device int32 tensor or anything numpy reads."""
     H, W = sensor_hw
     if check_aggregation(aggregation) == 'timesurface':
-        surf = ops.event_latest_surface_dat_ranges(records, ranges, Tm, H, W, tau=tau)
-        return ops.frames_letterbox(surf, params_on(params, surf.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
-    counts = ops.event_histogram_dat_ranges(records, ranges, Tm, H, W)
-    return ops.counts_letterbox(counts, params_on(params, counts.device), canvas_hw[0], canvas_hw[1]).unsqueeze(1)
+        frames = ops.event_latest_surface_dat_ranges(records, ranges, Tm, H, W, tau=tau)
+    else:
+        frames = ops.event_histogram_dat_ranges(records, ranges, Tm, H, W)
+    return _letterboxed(frames, params, canvas_hw).unsqueeze(1)
 
 
 # ------------------------------------------------------------------------------------------------ Gen1 from recordings resident in HBM

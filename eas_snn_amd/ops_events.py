@@ -62,18 +62,44 @@ def event_window_search(records, label_t, window, num_slice, file_offsets=None, 
     return ranges
 
 
+def _dat_ranges_frames(timer, entry, dtype, out_bytes, records, ranges, ns, H, W, tau, return_oob):
+    """the two .dat-range wrappers: checks, allocations, the call (``tau``: a tuple, empty for the counts) and the return tuple"""
+    _dev(records, ranges)
+    rec = records.contiguous().view(torch.uint8)
+    assert rec.numel() % 8 == 0, '.dat event records are 8 bytes'
+    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
+    B = ranges.shape[0]
+    out = torch.empty((B, ns, 2, H, W), dtype=dtype, device=rec.device)
+    oob = torch.empty(1, dtype=torch.int32, device=rec.device) if return_oob else None
+    _call(timer, 8 * (rec.numel() // 8) + out_bytes * out.numel(), getattr(_lib.lib(), entry), ptr(rec), ptr(ranges.contiguous()), B, ns, H, W,
+          *tau, ptr(out), ptr(oob), stream())
+    return (out, oob) if return_oob else out
+
+
 def event_histogram_dat_ranges(records, ranges, Tm, H, W, return_oob=False):
     """Count frames int32 [B, Tm, 2, H, W] of the record ranges [B, 2] (``event_window_search``) of a .dat image in HBM: label
     timestamps in, frames out, nothing read back to the host in between."""
-    _dev(records, ranges)
-    rec = records.contiguous().view(torch.uint8)
-    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
-    B = ranges.shape[0]
-    out = torch.empty((B, Tm, 2, H, W), dtype=torch.int32, device=rec.device)
-    oob = torch.empty(1, dtype=torch.int32, device=rec.device) if return_oob else None
-    _call('eas_event_histogram_dat', 8 * (rec.numel() // 8) + 4 * out.numel(), _lib.lib().eas_event_histogram_dat_ranges, ptr(rec),
-          ptr(ranges.contiguous()), B, Tm, H, W, ptr(out), ptr(oob), stream())
-    return (out, oob) if return_oob else out
+    return _dat_ranges_frames('eas_event_histogram_dat', 'eas_event_histogram_dat_ranges', torch.int32, 4, records, ranges, Tm, H, W, (), return_oob)
+
+
+def _atis_frames(entry, dtype, workspace_query, out_bytes, records, sample_offsets, Tl, Tm, H, W, window, tau, return_oob, return_flags):
+    """the three ATIS wrappers: checks, the window rule, allocations, the call (``tau``: a tuple, empty for the counts) and the return tuple.
+    bytes: the records twice + ``out_bytes`` per element of the frames"""
+    _dev(records, sample_offsets)
+    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
+    rec = records if records.is_contiguous() else records.contiguous()
+    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    nrec = rec.numel() // 5
+    B = sample_offsets.numel() - 1
+    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
+    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=dtype, device=rec.device)
+    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
+    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
+    ws = torch.empty(getattr(_lib.lib(), workspace_query)(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
+    _call(entry, 10 * nrec + out_bytes * out.numel(), getattr(_lib.lib(), entry), ptr(rec), nrec, ptr(sample_offsets.contiguous()), B, lo, hi,
+          Tl, Tm, H, W, *tau, ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
+    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return res if len(res) > 1 else out
 
 
 def event_histogram_atis(records, sample_offsets, Tl, Tm, H, W, window=None, return_oob=False, return_flags=False):
@@ -82,21 +108,8 @@ def event_histogram_atis(records, sample_offsets, Tl, Tm, H, W, window=None, ret
     micro slicing and the count histogram on the device (NCaltech.read_ATIS / generate_slices / agrregate 'micro_sum').  ``records``: any
     uint8 view, at any alignment; ``sample_offsets`` int64 [B+1] record indices.  Optional returns: out-of-sensor events per recording
     (int32 [B]) and flags (int32 [B]; bit 0 event times decrease, bit 1 no event remains / a macro slice is empty)."""
-    _dev(records, sample_offsets)
-    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
-    rec = records if records.is_contiguous() else records.contiguous()
-    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
-    nrec = rec.numel() // 5
-    B = sample_offsets.numel() - 1
-    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
-    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.int32, device=rec.device)
-    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
-    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
-    ws = torch.empty(_lib.lib().eas_event_histogram_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
-    _call('eas_event_histogram_atis', 10 * nrec + 4 * out.numel(), _lib.lib().eas_event_histogram_atis, ptr(rec), nrec,
-          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
-    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
-    return res if len(res) > 1 else out
+    return _atis_frames('eas_event_histogram_atis', torch.int32, 'eas_event_histogram_atis_workspace_bytes', 4, records, sample_offsets, Tl, Tm, H, W,
+                        window, (), return_oob, return_flags)
 
 
 def event_timesurface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, tau=500e3, return_oob=False, return_flags=False):
@@ -105,22 +118,9 @@ def event_timesurface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, t
     (NCaltech.get_measure_func, ncaltech.py:218-225; event_reps.py:13-19).  Same decode, window, slicing and optional returns; flags bit 2:
     a macro slice spans more records than one bin can hold at weight 1 (``eas_event_timesurface_atis_capacity()``).  Bit-identical from run
     to run (64-bit integer sums of the weights in units of 2^-48)."""
-    _dev(records, sample_offsets)
-    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
-    rec = records if records.is_contiguous() else records.contiguous()
-    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
-    nrec = rec.numel() // 5
-    B = sample_offsets.numel() - 1
-    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
-    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.float64, device=rec.device)
-    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
-    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
-    ws = torch.empty(_lib.lib().eas_event_timesurface_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
-    # bytes: the records twice, the 64-bit bins written, then read and written once more by the finishing pass
-    _call('eas_event_timesurface_atis', 10 * nrec + 24 * out.numel(), _lib.lib().eas_event_timesurface_atis, ptr(rec), nrec,
-          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, float(tau), ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
-    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
-    return res if len(res) > 1 else out
+    # bytes: the 64-bit bins written, then read and written once more by the finishing pass
+    return _atis_frames('eas_event_timesurface_atis', torch.float64, 'eas_event_timesurface_atis_workspace_bytes', 24, records, sample_offsets, Tl, Tm,
+                        H, W, window, (float(tau),), return_oob, return_flags)
 
 
 def event_latest_surface_atis(records, sample_offsets, Tl, Tm, H, W, window=None, tau=10e3, return_oob=False, return_flags=False):
@@ -130,22 +130,9 @@ def event_latest_surface_atis(records, sample_offsets, Tl, Tm, H, W, window=None
     (NCaltech.agrregate 'timesurface', ncaltech.py:255-257; to_timesurface_numpy, event_reps.py:141-160).  Decode, window, slicing and the
     optional returns are ``event_histogram_atis``'s; flags bit 3 (value 8): a macro slice holds events and has micro window 0 (the reference
     raises; its frames are zero).  Not ``event_timesurface_atis``, which is the *measure* of that name.  Bit-identical from run to run."""
-    _dev(records, sample_offsets)
-    assert records.dtype == torch.uint8 and sample_offsets.dtype == torch.int64
-    rec = records if records.is_contiguous() else records.contiguous()
-    assert rec.numel() % 5 == 0, 'ATIS records are 5 bytes'
-    nrec = rec.numel() // 5
-    B = sample_offsets.numel() - 1
-    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
-    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=torch.float64, device=rec.device)
-    oob = torch.empty(B, dtype=torch.int32, device=rec.device) if return_oob else None
-    flags = torch.empty(B, dtype=torch.int32, device=rec.device) if return_flags else None
-    ws = torch.empty(_lib.lib().eas_event_histogram_atis_workspace_bytes(nrec, B, Tl), dtype=torch.uint8, device=rec.device)
-    # bytes: the records twice, the 64-bit bins zeroed, then read and written once by the finishing pass
-    _call('eas_event_latest_surface_atis', 10 * nrec + 24 * out.numel(), _lib.lib().eas_event_latest_surface_atis, ptr(rec), nrec,
-          ptr(sample_offsets.contiguous()), B, lo, hi, Tl, Tm, H, W, float(tau), ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
-    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
-    return res if len(res) > 1 else out
+    # bytes: the 64-bit bins zeroed, then read and written once by the finishing pass
+    return _atis_frames('eas_event_latest_surface_atis', torch.float64, 'eas_event_histogram_atis_workspace_bytes', 24, records, sample_offsets, Tl, Tm,
+                        H, W, window, (float(tau),), return_oob, return_flags)
 
 
 def event_latest_surface_dat_ranges(records, ranges, num_slices, H, W, tau=50e3, return_oob=False):
@@ -153,16 +140,8 @@ def event_latest_surface_dat_ranges(records, ranges, num_slices, H, W, tau=50e3,
     HBM: float64 [B, num_slices, 2, H, W], bit-identical to ``event_time_surface`` on the decoded arrays of the same samples; an empty range
     or a window of zero length gives zero frames.  Label timestamps in, surfaces out, nothing read back to the host in between.  Optional
     return: the events outside the sensor that were dropped (int32 [1])."""
-    _dev(records, ranges)
-    rec = records.contiguous().view(torch.uint8)
-    assert rec.numel() % 8 == 0, '.dat event records are 8 bytes'
-    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
-    B = ranges.shape[0]
-    out = torch.empty((B, num_slices, 2, H, W), dtype=torch.float64, device=rec.device)
-    oob = torch.empty(1, dtype=torch.int32, device=rec.device) if return_oob else None
-    _call('eas_event_latest_surface_dat_ranges', 8 * (rec.numel() // 8) + 24 * out.numel(), _lib.lib().eas_event_latest_surface_dat_ranges,
-          ptr(rec), ptr(ranges.contiguous()), B, num_slices, H, W, float(tau), ptr(out), ptr(oob), stream())
-    return (out, oob) if return_oob else out
+    return _dat_ranges_frames('eas_event_latest_surface_dat_ranges', 'eas_event_latest_surface_dat_ranges', torch.float64, 24, records, ranges,
+                              num_slices, H, W, (float(tau),), return_oob)
 
 
 def event_frames(t, x, y, p, sample_offsets, Tm, H, W, Hc, Wc):

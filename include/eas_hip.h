@@ -196,7 +196,9 @@ int eas_event_time_surface(const uint32_t* t, const uint16_t* x, const uint16_t*
 int eas_event_window_search(const void* records, const int64_t* file_offsets, int F, const int32_t* file_id, const int64_t* label_t, int B,
                             int64_t window_lo, int64_t window_hi, int num_slice, int64_t* ranges, eas_stream_t stream);
 /* eas_event_histogram_dat for samples given as device-resident record ranges (the output of eas_event_window_search; the ranges
- * of neighbouring labels overlap): out int32 [B][Tm][2][H][W], zeroed by the call.  No host read of the ranges. */
+ * of neighbouring labels overlap): out int32 [B][Tm][2][H][W], zeroed by the call.  No host read of the ranges.  The sample is a
+ * block's y index: B > 65535 is EAS_ERR_UNSUPPORTED, answered before any HIP call, as eas_event_latest_surface_dat_ranges answers it
+ * (until the two entries got one argument rule this one went on to a launch that failed). */
 int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, int B, int Tm, int H, int W, int32_t* out,
                                    uint32_t* oob_count, eas_stream_t stream);
 /* eas_event_time_surface (Gen1's aggregation 'timesurface', tau: the reference's 50e3) for samples given as such record ranges (additive,

@@ -18,7 +18,7 @@ import eas_snn_amd
 from eas_snn_amd import data, ops
 
 NEW_ABI = ['eas_event_latest_surface_atis', 'eas_event_latest_surface_dat_ranges']
-INVALID_ARG = -1
+INVALID_ARG, UNSUPPORTED = -1, -2
 P = 0x1000                                                           # a 16-byte aligned address nobody dereferences
 
 
@@ -66,6 +66,28 @@ def test_bad_arguments_are_refused_before_any_launch():
             assert atis(**{dim: v}) == INVALID_ARG, (dim, v)
     assert dat(ns=0) == INVALID_ARG and dat(ns=-1) == INVALID_ARG and dat(ranges=None) == INVALID_ARG and dat(rec=P + 4) == INVALID_ARG
     assert atis(off=None) == INVALID_ARG and atis(ws=None) == INVALID_ARG and atis(ws=P + 8) == INVALID_ARG and atis(nrec=-1) == INVALID_ARG
+
+
+def test_both_dat_range_entries_share_one_argument_rule():
+    """The count entry and the latest-surface entry of .dat record ranges refuse the same arguments the same way, without a GPU: the sample
+    is a block's y index in both, so a batch above 65535 is EAS_ERR_UNSUPPORTED.  That assertion on eas_event_histogram_dat_ranges is new
+    with the shared host template: before it the entry went on to a launch that failed (here, without a GPU, with another error code)."""
+    lib = eas_snn_amd.hip_library()
+
+    def count(rec=P, ranges=P, out=P, B=1, ns=4, H=24, W=32):
+        return lib.eas_event_histogram_dat_ranges(rec, ranges, B, ns, H, W, out, None, None)
+
+    def latest(rec=P, ranges=P, out=P, B=1, ns=4, H=24, W=32):
+        return lib.eas_event_latest_surface_dat_ranges(rec, ranges, B, ns, H, W, 50e3, out, None, None)
+
+    for call in (count, latest):
+        assert call(B=65536) == UNSUPPORTED, call.__name__
+        for dim in ('B', 'ns', 'H', 'W'):
+            for v in (0, -3):
+                assert call(**{dim: v}) == INVALID_ARG, (call.__name__, dim, v)
+        for bad in (dict(out=None), dict(rec=None), dict(ranges=None), dict(rec=P + 4)):
+            assert call(**bad) == INVALID_ARG, (call.__name__, bad)
+        assert call(B=65536, H=0) == INVALID_ARG, call.__name__            # a bad argument is reported before an unsupported size
 
 
 @pytest.mark.parametrize('name', ref.CASES)
