@@ -109,6 +109,8 @@ class EasAdamHyper(C.Structure):
 ABI_VERSION = 9
 
 _ATIS_HEAD = [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4      # the ATIS entries up to Tl, Tm, H, W (then tau, or the frames)
+# the store entries up to Tl, Tm, H, W: records, nrec, file_offsets, F, sample_file, B, chunk_base, max_file_records, window_lo, window_hi
+_ATIS_STORE_HEAD = [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64] + [C.c_int] * 4
 PROTOTYPES = {
     'eas_abi_version': (C.c_int, []),
     'eas_kernel_trace_begin': (None, []),
@@ -136,6 +138,13 @@ PROTOTYPES = {
     'eas_event_timesurface_atis': (C.c_int, _ATIS_HEAD + [C.c_double] + [_P] * 5),
     'eas_frames_letterbox_f64': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
     'eas_event_latest_surface_atis': (C.c_int, _ATIS_HEAD + [C.c_double] + [_P] * 5),
+    'eas_atis_store_index_bytes': (C.c_int64, [C.c_int64]),
+    'eas_atis_store_index': (C.c_int, [_P, C.c_int64, _P, _P]),
+    'eas_atis_store_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'eas_atis_store_timesurface_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'eas_event_histogram_atis_store': (C.c_int, _ATIS_STORE_HEAD + [_P] * 5),
+    'eas_event_timesurface_atis_store': (C.c_int, _ATIS_STORE_HEAD + [C.c_double] + [_P] * 5),
+    'eas_event_latest_surface_atis_store': (C.c_int, _ATIS_STORE_HEAD + [C.c_double] + [_P] * 5),
     'eas_event_latest_surface_dat_ranges': (C.c_int, [_P, _P] + [C.c_int] * 4 + [C.c_double, _P, _P, _P]),
     'eas_postprocess_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'eas_postprocess': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P]),

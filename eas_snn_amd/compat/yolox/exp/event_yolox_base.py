@@ -181,6 +181,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
             from eas_snn_amd.data import Gen1StoreLoader
             return Gen1StoreLoader(self, batch_size)
+        if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)
+            from eas_snn_amd.data import NCaltechStoreLoader
+            return NCaltechStoreLoader(self, batch_size)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):
@@ -188,6 +191,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'dat_store':
             from eas_snn_amd.data import Gen1StoreDataset, gen1_store_for
             return Gen1StoreDataset(self, gen1_store_for(self, 'test'))
+        if getattr(self, 'train_input', None) == 'atis_store':
+            from eas_snn_amd.data import NCaltechStoreDataset, ncaltech_store_for
+            return NCaltechStoreDataset(self, ncaltech_store_for(self, 'test' if kwargs.get('testdev', False) else 'val'))
         return SyntheticEvalDataset(self, length=int(getattr(self, 'eval_samples', 256)), n_events=int(getattr(self, 'eval_events', 200_000)))
 
     def get_eval_loader(self, batch_size, is_distributed, **kwargs):
@@ -207,6 +213,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'dat_store':
             from eas_snn_amd.data import Gen1StoreEvalLoader
             return Gen1StoreEvalLoader(self, batch_size, idx, valdataset.store)
+        if getattr(self, 'train_input', None) == 'atis_store':
+            from eas_snn_amd.data import NCaltechStoreEvalLoader
+            return NCaltechStoreEvalLoader(self, batch_size, idx, valdataset.store)
         # synthetic streams on the Gen1 sensor (or on the canvas itself when that is smaller); ``eval_sensor_hw`` / ``eval_events`` override
         sensor = getattr(self, 'eval_sensor_hw', None) or (min(240, self.test_size[0]), min(304, self.test_size[1]))
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)

@@ -4,7 +4,8 @@
 // (yolox/data/datasets/ncaltech.py:63-96, 179-183, 218-237, 264-269, 368-379; yolox/utils/event_reps.py:9-19).
 //   record b0..b4: x = b0, y = b1, p = b2 >> 7, raw = (b2 & 127) << 16 | b3 << 8 | b4;  y == 240 is an overflow record: no event, it adds
 //   8192 to the time of every later record of its recording, so t = raw + 8192 * (overflow records at or before the record).
-// Five launches (six for the time surface), no allocation, no host read (graph-capturable):
+// Five launches (six for the time surface; 1 and 2, the index of the buffer, run in front of 0), no allocation, no host read
+// (graph-capturable):
 //   0. atis_zero_kernel             the frames
 //   1. atis_overflow_count_kernel  overflow records per chunk of kChunk records of the whole buffer (reads the y byte of every record)
 //   2. atis_overflow_scan_kernel    exclusive scan of the chunk counts, in place (one block)
@@ -31,6 +32,10 @@
 // re-read O(Tl * log nrec) chunks.
 // The chunks are chunks of the BUFFER (record index / kChunk), not of a recording: the overflow count of a record inside recording
 // [a, e) is prefix(i) - prefix(a - 1), so recordings need no chunk tables of their own.
+// A store (a dataset resident in HBM) runs launches 1 and 2 ONCE (eas_atis_store_index -> uint32 [chunks + 1], caller-owned); a step then is
+// launches 0, 3, 4 (5) of the *_store entries on the B recordings that sample_file picks out of file_offsets: 5 * sum n_b record bytes, not
+// 10 * nrec.  Where recording b lies is the only difference between the two families: a range source (PackedRanges / StoreRanges), a
+// template parameter of the plan and the histogram kernel.
 #include <limits.h>
 
 #include "eas_common.h"
@@ -54,13 +59,32 @@ struct AtisHead {                       // per recording
 };
 struct AtisSlice { uint32_t f, w; };    // per (recording, macro slice): time of its first member event, micro window (0: nothing is binned)
 
-__device__ __forceinline__ void clamp_range(const int64_t* __restrict__ offsets, int b, int64_t nrec, int64_t& a, int64_t& e) {
-    a = offsets[b];
-    e = offsets[b + 1];
-    if (a < 0) a = 0;
-    if (e > nrec) e = nrec;
+__device__ __forceinline__ void clamp_range(int64_t lo, int64_t hi, int64_t nrec, int64_t& a, int64_t& e) {
+    a = lo < 0 ? 0 : lo;
+    e = hi > nrec ? nrec : hi;
     if (e < a) e = a;                   // offsets that do not describe a range: an empty recording (flag bit 1), nothing past nrec is read
 }
+
+// ---- range sources: recording b of a call -> its records [a, e) of the buffer; false: b names no recording (an empty range, flag bit 4)
+struct PackedRanges {                   // the batch back to back: offsets [B + 1]
+    const int64_t* offsets;
+    __device__ __forceinline__ bool operator()(int b, int64_t nrec, int64_t& a, int64_t& e) const {
+        clamp_range(offsets[b], offsets[b + 1], nrec, a, e);
+        return true;
+    }
+};
+struct StoreRanges {                    // a resident store: recording b is file sample_file[b] of file_offsets [F + 1]
+    const int64_t* file_offsets;
+    int64_t F;
+    const int64_t* sample_file;
+    __device__ __forceinline__ bool operator()(int b, int64_t nrec, int64_t& a, int64_t& e) const {
+        const int64_t f = sample_file[b];
+        a = e = 0;
+        if (f < 0 || f >= F) return false;                     // nothing is read through the index
+        clamp_range(file_offsets[f], file_offsets[f + 1], nrec, a, e);
+        return true;
+    }
+};
 
 __device__ __forceinline__ uint32_t rec_y(const uint8_t* __restrict__ rec, int64_t i) { return rec[5 * i + 1]; }
 __device__ __forceinline__ uint32_t rec_raw(const uint8_t* __restrict__ rec, int64_t i) {
@@ -154,7 +178,8 @@ __device__ __forceinline__ int64_t lower_bound_events(const AtisRec& R, int64_t 
     return lo;
 }
 
-__global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
+template <typename Src>
+__global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const Src src,
                                                              const uint32_t* __restrict__ chunk_base, int64_t window_lo, int64_t window_hi,
                                                              int Tl, int Tm, AtisHead* __restrict__ heads, AtisSlice* __restrict__ slices,
                                                              uint32_t* __restrict__ t_target, uint32_t window0_flag,
@@ -162,12 +187,11 @@ __global__ __launch_bounds__(EAS_WAVE) void atis_plan_kernel(const uint8_t* __re
     const int b = blockIdx.x;
     const bool writer = threadIdx.x == 0;
     int64_t a, e;
-    clamp_range(offsets, b, nrec, a, e);
+    uint32_t flag = src(b, nrec, a, e) ? 0u : 16u;
     AtisRec R = {rec, chunk_base, 0u};
     if (a > 0 && a < e) R.ovf_base = overflow_prefix(rec, chunk_base, a - 1);
     AtisHead h = {LLONG_MIN, LLONG_MAX, 0, 0, R.ovf_base, 0u};
     AtisSlice* rows = slices + (int64_t)b * Tl;
-    uint32_t flag = 0;
     int64_t ia = a, ib = e;
     const int64_t last = prev_event(rec, e - 1, a);
     bool any = last >= a;
@@ -247,8 +271,8 @@ struct TimeSurfaceAcc {                 // measure 'timesurface' (decay 'tanh'):
     }
 };
 
-template <typename Acc>
-__global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const int64_t* __restrict__ offsets,
+template <typename Acc, typename Src>
+__global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __restrict__ rec, int64_t nrec, const Src src,
                                                            const uint32_t* __restrict__ chunk_base, const AtisHead* __restrict__ heads,
                                                            const AtisSlice* __restrict__ slices, int Tl, int Tm, int H, int W,
                                                            typename Acc::Bin* __restrict__ out, uint32_t* __restrict__ oob,
@@ -256,7 +280,7 @@ __global__ __launch_bounds__(kChunk) void atis_hist_kernel(const uint8_t* __rest
     __shared__ uint32_t wave_total[kChunk / EAS_WAVE];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & (EAS_WAVE - 1), wid = tid / EAS_WAVE;
     int64_t a, e;
-    clamp_range(offsets, b, nrec, a, e);
+    src(b, nrec, a, e);
     if (e <= a) return;
     const AtisHead h = heads[b];
     const AtisSlice* rows = slices + (int64_t)b * Tl;
@@ -328,64 +352,139 @@ struct AtisSliceWin {
 
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t chunks_of(int64_t nrec) { return (nrec + kChunk - 1) / kChunk; }
+inline int64_t index_bytes(int64_t nrec) { return (chunks_of(nrec) + 1) * (int64_t)sizeof(uint32_t); }
 
-// the workspace of a call: chunk counts / bases, one head per recording, one row per (recording, macro slice), and -- behind what the
-// count entry uses -- the time surface's t_target rows
+// the workspace of a step: one head per recording, one row per (recording, macro slice), and -- behind what the count entry uses -- the
+// time surface's t_target rows.  The packed entries keep their overflow index in front of it (align16(index_bytes(nrec)) bytes)
 struct AtisWorkspace {
-    int64_t heads, slices, t_target, count_bytes, ts_bytes;          // byte offsets and the two totals
-    AtisWorkspace(int64_t nrec, int B, int Tl) {
-        heads = align16((chunks_of(nrec) + 1) * (int64_t)sizeof(uint32_t));
-        slices = heads + align16((int64_t)B * sizeof(AtisHead));
+    int64_t slices, t_target, count_bytes, ts_bytes;                 // byte offsets behind the heads and the two totals
+    AtisWorkspace(int B, int Tl) {
+        slices = align16((int64_t)B * sizeof(AtisHead));
         t_target = count_bytes = slices + align16((int64_t)B * Tl * sizeof(AtisSlice));
         ts_bytes = t_target + align16((int64_t)B * Tl * sizeof(uint32_t));
     }
 };
 
-// The launches the entry points share (arguments checked by the caller).  t_target: NULL but for the time-surface measure; window0_flag:
-// the flag bits of a macro slice that holds events and has micro window 0 (8 for the latest-time surface, else 0).
-template <typename Acc>
-int atis_frames(const uint8_t* rec, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
-                int H, int W, typename Acc::Bin* out, uint32_t* oob_count, uint32_t* flags, void* workspace, uint32_t* t_target, uint32_t window0_flag,
-                const Acc& acc, hipStream_t st) {
-    const int64_t far = (int64_t)1 << 40;                  // decoded times fit 32 bits: a bound beyond +-2^40 selects what 2^40 selects
-    window_lo = window_lo < -far ? -far : window_lo;
-    window_hi = window_hi > far ? far : (window_hi < -far ? -far : window_hi);
+// launches 1 and 2: overflow records in front of every chunk of the buffer -> chunk_base [chunks + 1] (the last word: all of them)
+int atis_index(const uint8_t* rec, int64_t nrec, uint32_t* chunk_base, hipStream_t st) {
     EAS_CLEAR_ERR();
-    const int64_t nchunks = chunks_of(nrec);
-    const AtisWorkspace ws(nrec, B, Tl);
-    uint32_t* chunk_base = (uint32_t*)workspace;
-    AtisHead* heads = (AtisHead*)((char*)workspace + ws.heads);
-    AtisSlice* slices = (AtisSlice*)((char*)workspace + ws.slices);
-    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W, nwords = nout * (int64_t)(sizeof(typename Acc::Bin) / sizeof(int32_t));
-    EAS_LAUNCH(atis_zero_kernel, dim3(eas_grid_1d((nwords + 3) / 4)), dim3(EAS_BLOCK), 0, st, (int32_t*)out, nwords);
+    const int64_t n = chunks_of(nrec) + 1;                 // the chunk behind the last one holds no record: it counts 0
+    EAS_LAUNCH(atis_overflow_count_kernel, dim3(eas_grid_1d(n, 1)), dim3(kChunk), 0, st, rec, nrec, n, chunk_base);
     EAS_CHECK_LAUNCH();
-    if (nchunks > 0) {
-        EAS_LAUNCH(atis_overflow_count_kernel, dim3(eas_grid_1d(nchunks, 1)), dim3(kChunk), 0, st, rec, nrec, nchunks, chunk_base);
-        EAS_CHECK_LAUNCH();
-        EAS_LAUNCH(atis_overflow_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, chunk_base, nchunks);
-        EAS_CHECK_LAUNCH();
-    }
-    EAS_LAUNCH(atis_plan_kernel, dim3(B), dim3(EAS_WAVE), 0, st, rec, nrec, sample_offsets, chunk_base, window_lo, window_hi, Tl, Tm, heads, slices,
-               t_target, window0_flag, oob_count, flags);
+    EAS_LAUNCH(atis_overflow_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, chunk_base, n);
     EAS_CHECK_LAUNCH();
-    if (nchunks > 0) {
+    return EAS_OK;
+}
+
+// what the entry points of both families hand to the launches they share (arguments checked by the caller)
+struct AtisCall {
+    const uint8_t* rec;
+    int64_t nrec;
+    int B;
+    int64_t window_lo, window_hi;
+    int Tl, Tm, H, W;
+    uint32_t *oob_count, *flags;
+    const uint32_t* chunk_base;         // the overflow index of the buffer
+    void* workspace;                    // AtisWorkspace(B, Tl)
+    int64_t per;                        // histogram blocks per recording
+    hipStream_t st;
+    AtisSlice* slices() const { return (AtisSlice*)((char*)workspace + AtisWorkspace(B, Tl).slices); }
+    uint32_t* t_target() const { return (uint32_t*)((char*)workspace + AtisWorkspace(B, Tl).t_target); }
+    int64_t nout() const { return (int64_t)B * Tl * Tm * 2 * H * W; }
+};
+
+// Launches 0, 3 and 4.  t_target: NULL but for the time-surface measure; window0_flag: the flag bits of a macro slice that holds events
+// and has micro window 0 (8 for the latest-time surface, else 0).
+template <typename Acc, typename Src>
+int atis_frames(const AtisCall& c, const Src& src, typename Acc::Bin* out, uint32_t* t_target, uint32_t window0_flag, const Acc& acc) {
+    const int64_t far = (int64_t)1 << 40;                  // decoded times fit 32 bits: a bound beyond +-2^40 selects what 2^40 selects
+    const int64_t window_lo = c.window_lo < -far ? -far : c.window_lo;
+    const int64_t window_hi = c.window_hi > far ? far : (c.window_hi < -far ? -far : c.window_hi);
+    EAS_CLEAR_ERR();
+    AtisHead* heads = (AtisHead*)c.workspace;
+    AtisSlice* slices = c.slices();
+    const int64_t nwords = c.nout() * (int64_t)(sizeof(typename Acc::Bin) / sizeof(int32_t));
+    EAS_LAUNCH(atis_zero_kernel, dim3(eas_grid_1d((nwords + 3) / 4)), dim3(EAS_BLOCK), 0, c.st, (int32_t*)out, nwords);
+    EAS_CHECK_LAUNCH();
+    EAS_LAUNCH(atis_plan_kernel<Src>, dim3(c.B), dim3(EAS_WAVE), 0, c.st, c.rec, c.nrec, src, c.chunk_base, window_lo, window_hi, c.Tl, c.Tm, heads,
+               slices, t_target, window0_flag, c.oob_count, c.flags);
+    EAS_CHECK_LAUNCH();
+    if (c.nrec > 0) {
         // the recordings' lengths live on the device: a fixed number of blocks per recording strides over whatever it holds
-        int64_t per = nchunks / B + 1;
-        if (per > 64) per = 64;
-        EAS_LAUNCH(atis_hist_kernel<Acc>, dim3((unsigned)per, B), dim3(kChunk), 0, st, rec, nrec, sample_offsets, chunk_base, heads, slices, Tl, Tm,
-                   H, W, out, oob_count, flags, acc);
+        EAS_LAUNCH((atis_hist_kernel<Acc, Src>), dim3((unsigned)c.per, c.B), dim3(kChunk), 0, c.st, c.rec, c.nrec, src, c.chunk_base, heads, slices,
+                   c.Tl, c.Tm, c.H, c.W, out, c.oob_count, c.flags, acc);
         EAS_CHECK_LAUNCH();
     }
     return EAS_OK;
 }
 
+// ---- the three representations, for either range source
+template <typename Src>
+int atis_counts(const AtisCall& c, const Src& src, int32_t* out) {
+    return atis_frames(c, src, out, nullptr, 0u, CountAcc{});
+}
+
+template <typename Src>
+int atis_timesurface(const AtisCall& c, const Src& src, double tau, double* out) {
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    uint32_t* t_target = c.t_target();
+    const int launched = atis_frames(c, src, bins, t_target, 0u, TimeSurfaceAcc{t_target, tau});
+    if (launched != EAS_OK) return launched;
+    EAS_LAUNCH(atis_ts_finish_kernel, dim3(eas_grid_1d(c.nout())), dim3(EAS_BLOCK), 0, c.st, bins, c.nout());
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+template <typename Src>
+int atis_latest_surface(const AtisCall& c, const Src& src, double tau, double* out) {
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    const int launched = atis_frames(c, src, bins, nullptr, 8u, LatestAcc{});
+    if (launched != EAS_OK) return launched;
+    const int64_t nrows = (int64_t)c.B * c.Tl;
+    EAS_LAUNCH(latest_finish_kernel<AtisSliceWin>, dim3(eas_grid_1d(nrows * 2 * c.H * c.W)), dim3(EAS_BLOCK), 0, c.st, nrows, c.Tm, c.H, c.W, tau, bins,
+               AtisSliceWin{c.slices()});
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+inline int64_t hist_blocks(int64_t chunks) { return chunks + 1 > 64 ? 64 : chunks + 1; }
+
 // the argument rules the entry points share
-int atis_check_args(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int Tl, int Tm, int H, int W, const void* out,
+int atis_check_args(const void* records, int64_t nrec, const void* ranges, int B, int Tl, int Tm, int H, int W, const void* out,
                     const void* workspace) {
-    if (!out || !sample_offsets || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
+    if (!out || !ranges || !workspace || B < 1 || Tl < 1 || Tm < 1 || H < 1 || W < 1 || nrec < 0) return EAS_ERR_INVALID_ARG;
     if ((nrec > 0 && !records) || ((uintptr_t)workspace & 15) || nrec > (INT64_MAX >> 3)) return EAS_ERR_INVALID_ARG;
     if ((int64_t)B * Tl >= (1 << 24) || B > 65535) return EAS_ERR_UNSUPPORTED;
     return EAS_OK;
+}
+
+// a packed entry: checks, then index and frames on its own workspace (the index in front, the step's workspace behind it)
+template <typename Frames>
+int atis_packed(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi, int Tl, int Tm, int H,
+                int W, const void* out, uint32_t* oob_count, uint32_t* flags, void* workspace, eas_stream_t stream, const Frames& frames) {
+    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
+    if (rc != EAS_OK) return rc;
+    uint32_t* chunk_base = (uint32_t*)workspace;
+    const AtisCall c = {(const uint8_t*)records, nrec, B, window_lo, window_hi, Tl, Tm, H, W, oob_count, flags, chunk_base,
+                        (char*)workspace + align16(index_bytes(nrec)), hist_blocks(chunks_of(nrec) / B), eas_s(stream)};
+    if (nrec > 0) {
+        const int indexed = atis_index(c.rec, nrec, chunk_base, c.st);
+        if (indexed != EAS_OK) return indexed;
+    }
+    return frames(c, PackedRanges{sample_offsets});
+}
+
+// a store entry: checks, then the frames of the B recordings sample_file picks, on the store's index
+template <typename Frames>
+int atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+               const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl, int Tm, int H, int W,
+               const void* out, uint32_t* oob_count, uint32_t* flags, void* workspace, eas_stream_t stream, const Frames& frames) {
+    const int rc = atis_check_args(records, nrec, sample_file, B, Tl, Tm, H, W, out, workspace);
+    if (rc != EAS_OK) return rc;
+    if (!file_offsets || !chunk_base || F < 0 || max_file_records < 0) return EAS_ERR_INVALID_ARG;
+    const AtisCall c = {(const uint8_t*)records, nrec, B, window_lo, window_hi, Tl, Tm, H, W, oob_count, flags, chunk_base, workspace,
+                        hist_blocks(chunks_of(max_file_records)), eas_s(stream)};
+    return frames(c, StoreRanges{file_offsets, F, sample_file});
 }
 
 }  // namespace
@@ -394,21 +493,19 @@ extern "C" {
 
 int64_t eas_event_histogram_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
     if (nrec < 0 || B < 1 || Tl < 1) return 0;
-    return AtisWorkspace(nrec, B, Tl).count_bytes;
+    return align16(index_bytes(nrec)) + AtisWorkspace(B, Tl).count_bytes;
 }
 
 int eas_event_histogram_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
                              int Tl, int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                              eas_stream_t stream) {
-    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
-    if (rc != EAS_OK) return rc;
-    return atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace,
-                       nullptr, 0u, CountAcc{}, eas_s(stream));
+    return atis_packed(records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace, stream,
+                       [=](const AtisCall& c, const PackedRanges& src) { return atis_counts(c, src, out); });
 }
 
 int64_t eas_event_timesurface_atis_workspace_bytes(int64_t nrec, int B, int Tl) {
     if (nrec < 0 || B < 1 || Tl < 1) return 0;
-    return AtisWorkspace(nrec, B, Tl).ts_bytes;
+    return align16(index_bytes(nrec)) + AtisWorkspace(B, Tl).ts_bytes;
 }
 
 int64_t eas_event_timesurface_atis_capacity(void) { return kTsCapacity; }
@@ -417,37 +514,54 @@ int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t*
                                int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                                eas_stream_t stream) {
     if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
-    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
-    if (rc != EAS_OK) return rc;
-    hipStream_t st = eas_s(stream);
-    uint32_t* t_target = (uint32_t*)((char*)workspace + AtisWorkspace(nrec, B, Tl).t_target);
-    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
-    const int launched = atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, bins, oob_count, flags,
-                                     workspace, t_target, 0u, TimeSurfaceAcc{t_target, tau}, st);
-    if (launched != EAS_OK) return launched;
-    const int64_t nout = (int64_t)B * Tl * Tm * 2 * H * W;
-    EAS_LAUNCH(atis_ts_finish_kernel, dim3(eas_grid_1d(nout)), dim3(EAS_BLOCK), 0, st, bins, nout);
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
+    return atis_packed(records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace, stream,
+                       [=](const AtisCall& c, const PackedRanges& src) { return atis_timesurface(c, src, tau, out); });
 }
 
 int eas_event_latest_surface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
                                   int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                                   eas_stream_t stream) {
     if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
-    const int rc = atis_check_args(records, nrec, sample_offsets, B, Tl, Tm, H, W, out, workspace);
-    if (rc != EAS_OK) return rc;
-    hipStream_t st = eas_s(stream);
-    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
-    const int launched = atis_frames((const uint8_t*)records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, bins, oob_count, flags,
-                                     workspace, nullptr, 8u, LatestAcc{}, st);
-    if (launched != EAS_OK) return launched;
-    const AtisSlice* slices = (const AtisSlice*)((char*)workspace + AtisWorkspace(nrec, B, Tl).slices);
-    const int64_t nrows = (int64_t)B * Tl;
-    EAS_LAUNCH(latest_finish_kernel<AtisSliceWin>, dim3(eas_grid_1d(nrows * 2 * H * W)), dim3(EAS_BLOCK), 0, st, nrows, Tm, H, W, tau, bins,
-               AtisSliceWin{slices});
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
+    return atis_packed(records, nrec, sample_offsets, B, window_lo, window_hi, Tl, Tm, H, W, out, oob_count, flags, workspace, stream,
+                       [=](const AtisCall& c, const PackedRanges& src) { return atis_latest_surface(c, src, tau, out); });
+}
+
+// ---- a store: the index once, then steps whose work is the batch's
+int64_t eas_atis_store_index_bytes(int64_t nrec) { return nrec < 0 ? 0 : index_bytes(nrec); }
+
+int eas_atis_store_index(const void* records, int64_t nrec, uint32_t* chunk_base, eas_stream_t stream) {
+    if (!chunk_base || nrec < 0 || (nrec > 0 && !records) || nrec > (INT64_MAX >> 3)) return EAS_ERR_INVALID_ARG;
+    return atis_index((const uint8_t*)records, nrec, chunk_base, eas_s(stream));
+}
+
+int64_t eas_atis_store_workspace_bytes(int B, int Tl) { return B < 1 || Tl < 1 ? 0 : AtisWorkspace(B, Tl).count_bytes; }
+int64_t eas_atis_store_timesurface_workspace_bytes(int B, int Tl) { return B < 1 || Tl < 1 ? 0 : AtisWorkspace(B, Tl).ts_bytes; }
+
+int eas_event_histogram_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                   const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
+                                   int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace, eas_stream_t stream) {
+    return atis_store(records, nrec, file_offsets, F, sample_file, B, chunk_base, max_file_records, window_lo, window_hi, Tl, Tm, H, W, out,
+                      oob_count, flags, workspace, stream, [=](const AtisCall& c, const StoreRanges& src) { return atis_counts(c, src, out); });
+}
+
+int eas_event_timesurface_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                     const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
+                                     int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                     eas_stream_t stream) {
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
+    return atis_store(records, nrec, file_offsets, F, sample_file, B, chunk_base, max_file_records, window_lo, window_hi, Tl, Tm, H, W, out,
+                      oob_count, flags, workspace, stream,
+                      [=](const AtisCall& c, const StoreRanges& src) { return atis_timesurface(c, src, tau, out); });
+}
+
+int eas_event_latest_surface_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                        const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl,
+                                        int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                        eas_stream_t stream) {
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;          // also NaN
+    return atis_store(records, nrec, file_offsets, F, sample_file, B, chunk_base, max_file_records, window_lo, window_hi, Tl, Tm, H, W, out,
+                      oob_count, flags, workspace, stream,
+                      [=](const AtisCall& c, const StoreRanges& src) { return atis_latest_surface(c, src, tau, out); });
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@ on the 240x304 Gen1 sensor, ``t`` sorted uniform, ``x``,``y`` uniform, ``p`` Ber
 Raw events (9 B/event) are what crosses PCIe; binning (K1) and canvas padding run on the GPU.
 
 Further down: the augmentation draws, the N-Caltech101 and 1 Mpx chains, and Gen1 from recordings resident in HBM (``Gen1Store`` and its
-loaders: ``.dat`` / ``_bbox.npy`` pairs read once, or seeded synthetic recordings).
+loaders: ``.dat`` / ``_bbox.npy`` pairs read once, or seeded synthetic recordings) and N-Caltech101 likewise (``NCaltechStore`` and its
+loaders: the split file's recordings and annotation files read once, or seeded synthetic recordings).
 """
 import numpy as np
 import torch
@@ -278,6 +279,20 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
     (nw, nh, dx, dy, flip) rows, a device int32 tensor or anything numpy reads.  N-Caltech101 resizes every sample, in evaluation too:
     ``letterbox_params(180, 240, 192, 256)`` = (256, 192, 0, 0, 0).  Its random branch (NCaltech.get_random_data, ncaltech.py:330-350)
     is ``jitter_params(..., jitter=.1)``, and the boxes go through ``transform_boxes`` as they are."""
+    Tl, Tm, (H, W), canvas_hw, window, kind = _atis_choice(exp_or_dims, measure, aggregation)
+    if kind == 'latest':
+        frames = ops.event_latest_surface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=surface_tau)
+    elif kind == 'timesurface':
+        frames = ops.event_timesurface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=tau)
+    else:
+        frames = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
+    return _letterboxed(frames, params, canvas_hw, interp)
+
+
+def _atis_choice(exp_or_dims, measure=None, aggregation=None):
+    """``(Tl, Tm, (H, W), (Hc, Wc), window, kind)`` of ``atis_to_frames``' ``exp_or_dims``, ``kind`` the representation that ``aggregation`` /
+    ``measure`` select: ``'latest'`` (aggregation 'timesurface'), ``'timesurface'`` (the measure) or ``'count'``; ValueError for a value no
+    front end has, the aggregation first"""
     if isinstance(exp_or_dims, (tuple, list)):
         Tl, Tm, (H, W), (Hc, Wc) = exp_or_dims[:4]
         window = exp_or_dims[4] if len(exp_or_dims) > 4 else None
@@ -290,16 +305,11 @@ def atis_to_frames(records_dev, offsets_dev, exp_or_dims, params, interp='cubic'
         if aggregation is None:
             aggregation = getattr(e, 'aggregation', None)
     if check_aggregation('micro_sum' if aggregation is None else aggregation) == 'timesurface':
-        frames = ops.event_latest_surface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=surface_tau)
-        return _letterboxed(frames, params, (Hc, Wc), interp)
+        return Tl, Tm, (H, W), (Hc, Wc), window, 'latest'
     measure = 'count' if measure is None else measure
     if measure not in ATIS_MEASURES:
         raise ValueError(f"measure {measure!r}: the N-Caltech101 front end has {' and '.join(repr(m) for m in ATIS_MEASURES)}")
-    if measure == 'timesurface':
-        frames = ops.event_timesurface_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window, tau=tau)
-    else:
-        frames = ops.event_histogram_atis(records_dev, offsets_dev, Tl, Tm, H, W, window=window)
-    return _letterboxed(frames, params, (Hc, Wc), interp)
+    return Tl, Tm, (H, W), (Hc, Wc), window, measure
 
 
 # ------------------------------------------------------------------------------------------------ 1 Mpx (RVT stacked histograms)
@@ -724,6 +734,242 @@ class Gen1StoreEvalLoader:
         self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
         exp_aggregation(exp)
         self.dataset = Gen1StoreDataset(exp, store)
+        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
+
+    def __len__(self):
+        return (len(self.indices) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
+        row = letterbox_params(H, W, Hc, Wc)
+        for b in range(len(self)):
+            ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
+            idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
+            frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
+            yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
+
+
+# ------------------------------------------------------------------------------------------------ N-Caltech101 from recordings resident in HBM
+NCALTECH_BACKGROUND = 'BACKGROUND_Google'          # the class the reference leaves out (ncaltech.py:48-51, 129-134)
+
+
+def parse_ncaltech_annotation(buf):
+    """``(x1, y1, x2, y2)`` of an N-Caltech101 ``annotation_*.bin`` image (bytes or a uint8 array), as NCaltech.read_annotation finds them
+    (ncaltech.py:107-127): two int16 (rows, cols), the box contour as rows * cols int16 in column-major order, and the minimum / maximum of
+    its rows 0 (x) and 1 (y).  The object contour behind it is not looked at."""
+    raw = buf.tobytes() if isinstance(buf, np.ndarray) else bytes(buf)
+    rows, cols = (int(v) for v in np.frombuffer(raw, dtype='<i2', count=2))
+    contour = np.frombuffer(raw, dtype='<i2', count=rows * cols, offset=4).reshape((rows, cols), order='F')
+    return int(contour[0].min()), int(contour[1].min()), int(contour[0].max()), int(contour[1].max())
+
+
+def encode_ncaltech_annotation(x1, y1, x2, y2, contour=((0, 0),)):
+    """The inverse of ``parse_ncaltech_annotation``, numpy uint8: a 2 x 5 box contour -- the rectangle's corners, closed, as the dataset's
+    files hold it -- and the object contour ``contour`` (points (x, y)) behind it."""
+    box = np.array([[x1, x2, x2, x1, x1], [y1, y1, y2, y2, y1]], dtype='<i2')
+    obj = np.asarray(contour, dtype='<i2').reshape(-1, 2).T
+    parts = [np.array(a.shape, dtype='<i2').view(np.uint8) for a in (box, obj)]
+    return np.concatenate([parts[0], box.reshape(-1, order='F').view(np.uint8), parts[1], obj.reshape(-1, order='F').view(np.uint8)])
+
+
+def synth_ncaltech_recordings(n_files, n_events, sensor_hw=(180, 240), n_classes=3, span_us=300_000, seed=0):
+    """``n_files`` seeded recordings ``(class_name, stem, atis_bytes uint8, annotation_bytes uint8)`` as ``NCaltechStore`` takes them, so that
+    the store and its loaders run without a dataset.  Recording f holds between ``n_events`` / 2 and ``n_events`` events -- ``t`` sorted uniform
+    over ``span_us``, ``x``, ``y`` uniform on the sensor, ``p`` Bernoulli(0.5) --, an overflow record in front of the first event of every further
+    65536 us (``encode_atis``), class ``f % n_classes`` and one box: inside the sensor, or (every fourth) across its right and lower border."""
+    H, W = sensor_hw
+    out = []
+    for f in range(n_files):
+        rng = np.random.default_rng([seed, f])
+        n = int(rng.integers(n_events // 2, n_events + 1))
+        t = np.sort(rng.integers(0, span_us, size=n, dtype=np.int64))
+        x, y = rng.integers(0, W, size=n), rng.integers(0, H, size=n)
+        p = (rng.random(n) < 0.5).astype(np.int64)
+        marks = np.arange(1, span_us // 65536 + 1) * 65536
+        bw, bh = int(rng.uniform(0.3, 0.6) * W), int(rng.uniform(0.3, 0.6) * H)
+        bx, by = (W - bw // 2, H - bh // 2) if f % 4 == 3 else (int(rng.integers(0, W - bw)), int(rng.integers(0, H - bh)))
+        out.append((f'class_{f % n_classes:03d}', f'image_{f:04d}', encode_atis(t, x, y, p, overflow_before=np.searchsorted(t, marks)),
+                    encode_ncaltech_annotation(bx, by, bx + bw, by + bh)))
+    return out
+
+
+class NCaltechStore:
+    """N-Caltech101 recordings and their boxes resident on the device: what NCaltech keeps on disk (ncaltech.py:43-61, 172-178), as tables that
+    the kernels index.  ``recordings``: a list of ``(class_name, stem, atis_bytes, annotation_bytes)`` -- the byte images of
+    ``Caltech101/<class>/<stem>.bin`` and its ``annotation`` file; recordings of ``BACKGROUND_Google`` are left out.  ``Tl``: macro slices per
+    sample (the reference's ``num_slice``); ``window`` = (lo, hi) in us relative to the recording's last event, or None.
+
+    Built once on the host and uploaded once: ``records`` uint8 (the recordings back to back), ``file_offsets`` int64 [F + 1] (record
+    indices), ``index`` (``ops.atis_store_index(records)``, the buffer's overflow prefix: two launches over the store, never again), ``boxes``
+    float32 [F, 5] rows (x1, y1, x2, y2, class) (``raw_bboxes``, ncaltech.py:176-177) and ``group_start`` = arange(F + 1): one box per
+    sample.  On the host: ``sample_names`` ``<class>-<stem>`` (ncaltech.py:59, 194), ``class_names`` (given, else the sorted names of the
+    recordings' classes), ``max_file_records`` and numpy copies of the tables (``host``).  The flat sample index is the recording's."""
+
+    def __init__(self, recordings, Tl, window, device, class_names=None, sensor_hw=(180, 240)):
+        self.Tl, self.sensor_hw = int(Tl), (int(sensor_hw[0]), int(sensor_hw[1]))
+        self.window = None if window is None else (int(window[0]), int(window[1]))
+        recordings = [r for r in recordings if r[0] != NCALTECH_BACKGROUND]
+        if class_names is None:
+            class_names = sorted({r[0] for r in recordings})
+        self.class_names = list(class_names)
+        name_to_idx = {name: i for i, name in enumerate(self.class_names)}
+        self.sample_names = []
+        areas, file_offsets, boxes = [], [0], []
+        for cls, stem, rec, ann in recordings:
+            buf = np.frombuffer(rec, dtype=np.uint8) if isinstance(rec, (bytes, bytearray, memoryview)) else np.asarray(rec, dtype=np.uint8)
+            if len(buf) % 5 != 0:
+                raise ValueError(f'{cls}/{stem}: not an ATIS recording of 5-byte records ({len(buf)} bytes)')
+            self.sample_names.append(f'{cls}-{stem}')
+            areas.append(buf)
+            file_offsets.append(file_offsets[-1] + len(buf) // 5)
+            boxes.append(parse_ncaltech_annotation(ann) + (name_to_idx[cls],))
+        F = len(self.sample_names)
+        self.host = dict(file_offsets=np.asarray(file_offsets, dtype=np.int64), boxes=np.asarray(boxes, dtype=np.float32).reshape(F, 5),
+                         group_start=np.arange(F + 1, dtype=np.int64))
+        self.max_file_records = int(np.diff(self.host['file_offsets']).max()) if F else 0
+        self.device = torch.device(device)
+        self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
+        for k, v in self.host.items():
+            setattr(self, k, torch.from_numpy(v).to(self.device))
+        # a store kept on the host is its tables only (names, boxes, offsets: what needs no GPU); the operators refuse its tensors
+        self.index = ops.atis_store_index(self.records) if self.device.type == 'cuda' else None
+
+    @classmethod
+    def from_directory(cls, root, split, Tl, window, device, class_names=None, sensor_hw=(180, 240)):
+        """the recordings of ``<root>/<split>.txt`` -- ``data_path label_path`` per line, relative to ``root``; lines that name
+        ``BACKGROUND_Google`` are dropped (ncaltech.py:48-51) --, read with ``numpy.fromfile``.  The class of a sample is the directory of its
+        label file, its stem the data file's name up to the first dot.  ``class_names=None``: the sorted directory names of
+        ``<root>/Caltech101`` without ``BACKGROUND_Google`` (ncaltech.py:129-134)."""
+        import os
+        with open(os.path.join(root, split + '.txt')) as f:
+            lines = [ln for ln in f.readlines() if NCALTECH_BACKGROUND not in ln]
+        if class_names is None:
+            class_names = [n.strip() for n in sorted(os.listdir(os.path.join(root, 'Caltech101'))) if NCALTECH_BACKGROUND not in n]
+        recs = []
+        for ln in lines:
+            data_path, label_path = ln.strip().split(' ')
+            recs.append((label_path.split('/')[-2], data_path.split('/')[-1].split('.')[0],
+                         np.fromfile(os.path.join(root, data_path), dtype=np.uint8), np.fromfile(os.path.join(root, label_path), dtype=np.uint8)))
+        return cls(recs, Tl, window, device, class_names=class_names, sensor_hw=sensor_hw)
+
+    def __len__(self):
+        return len(self.sample_names)
+
+    def raw_labels(self, index):
+        """float32 [1, 5] row (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands it out (``map_val``,
+        ``format='xywh'``, ncaltech.py:199-202: ``xyxy2xywh`` of the raw box -- not transformed)"""
+        box = self.host['boxes'][index:index + 1].copy()
+        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        return box
+
+    def frames(self, sample_idx, params, exp, canvas_hw=None):
+        """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): the store operator that
+        ``exp.aggregation`` / ``exp.measure`` select, as ``atis_to_frames`` selects its own, on the B recordings alone, then the cubic
+        letterbox; ``params``: (nw, nh, dx, dy, flip) per sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back
+        (graph-capturable)."""
+        kind = _atis_choice((self.Tl, exp.Tm, self.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))[-1]
+        op = {'latest': ops.event_latest_surface_atis_store, 'timesurface': ops.event_timesurface_atis_store,
+              'count': ops.event_histogram_atis_store}[kind]
+        frames = op(self.records, self.file_offsets, self.index, sample_idx, self.Tl, exp.Tm, *self.sensor_hw, window=self.window,
+                    max_file_records=self.max_file_records)
+        return _letterboxed(frames, params, canvas_hw if canvas_hw is not None else exp.input_size, 'cubic')
+
+    def targets(self, sample_idx, params, canvas_hw, max_labels=50, return_info=False):
+        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params``:
+        ``ops.label_targets`` on the store's box table (one box per sample: no permutation), one launch, nothing read back"""
+        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
+                                 canvas_hw[0], canvas_hw[1], max_labels=max_labels, return_info=return_info)
+
+
+def ncaltech_store_for(exp, split='train', device=None):
+    """The store of an experiment with ``train_input = 'atis_store'``: ``NCaltechStore.from_directory`` over ``exp.data_dir`` when it holds
+    ``<split>.txt``, seeded synthetic recordings otherwise (``exp.atis_store_recordings`` = (files, events per file), default (16, 20000);
+    the sensor is N-Caltech101's, or the canvas where that is smaller).  Kept on the experiment: one store per split."""
+    import os
+    cache = exp.__dict__.setdefault('_atis_stores', {})
+    if split not in cache:
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+        window = (exp.window * 1000, 0) if getattr(exp, 'window', None) is not None else None
+        root = str(getattr(exp, 'data_dir', '') or '')
+        if root and os.path.isfile(os.path.join(root, split + '.txt')):
+            cache[split] = NCaltechStore.from_directory(root, split, exp.Tl, window, device)
+        else:
+            n_files, n_events = getattr(exp, 'atis_store_recordings', (16, 20_000))
+            size = exp.input_size if split == 'train' else exp.test_size
+            sensor = (min(180, size[0]), min(240, size[1]))
+            n_classes = max(int(exp.num_classes), 1)
+            recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(split != 'train'))
+            cache[split] = NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor)
+    return cache[split]
+
+
+class NCaltechStoreDataset:
+    """what the trainer and the evaluators ask of a dataset, over an ``NCaltechStore``: length, ``sample_names``, ``class_names``, ``map_val``
+    without random augmentation"""
+    map_val, random_aug = True, False
+
+    def __init__(self, exp, store):
+        self.exp, self.store, self.sample_names, self.class_names = exp, store, store.sample_names, store.class_names
+
+    def __len__(self):
+        return len(self.store)
+
+
+class NCaltechStoreLoader:
+    """Training loader of N-Caltech101 from an ``NCaltechStore``: iterable of (frames [B, Tl, Tm, 2, Hc, Wc] fp32 on the GPU, targets
+    [B, 50, 5] rows (cls, cx, cy, w, h), zero padded).  An epoch is a permutation of the samples; per sample the draws come in the reference's
+    order (NCaltech.get_random_data, ncaltech.py:330-350): ``jitter_params(..., jitter=.1)`` and nothing else -- ``np.random.shuffle`` of the
+    sample's single box consumes no random state.  ``batches(epoch)`` returns the draws of an epoch, a function of (seed, epoch) alone; a
+    step uploads them -- sample indices and params -- and everything else happens on the device (``store.frames``, ``store.targets``): no
+    host read, no per-sample work.  ``store=None``: ``ncaltech_store_for(exp)``."""
+
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
+        self.store = store if store is not None else ncaltech_store_for(exp)
+        _atis_choice((self.store.Tl, exp.Tm, self.store.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))
+        self.iters = len(self.store) // batch_size
+        assert self.iters >= 1, 'fewer recordings than one batch'
+        self.dataset = NCaltechStoreDataset(exp, self.store)
+        self.epoch = 0
+
+    def __len__(self):
+        return self.iters
+
+    def close_mosaic(self):
+        pass
+
+    def batches(self, epoch):
+        """[(sample indices int64 [B], params int32 [B, 5])] of an epoch"""
+        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
+        order = rs.permutation(len(self.store))
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
+        out = []
+        for i in range(self.iters):
+            idx = order[i * self.batch_size:(i + 1) * self.batch_size].astype(np.int64)
+            par = np.array([jitter_params(H, W, Hc, Wc, jitter=.1, rng=rs) for _ in idx], dtype=np.int32).reshape(len(idx), 5)
+            out.append((idx, par))
+        return out
+
+    def __iter__(self):
+        dev = self.store.device
+        draws = self.batches(self.epoch)
+        self.epoch += 1
+        for idx, par in draws:
+            idx, par = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev)
+            yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, self.exp.input_size, self.max_labels)
+
+
+class NCaltechStoreEvalLoader:
+    """Evaluation loader over an ``NCaltechStore``: iterable of the tuple ``Gen1StoreEvalLoader`` yields -- ``(frames [B, Tl, Tm, 2, H, W]
+    fp32 on the GPU, labels [B][1, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
+    get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``, the cubic resize: N-Caltech101 resizes in evaluation too); the
+    labels are the raw float32 rows of the store (``NCaltechStore.raw_labels``), prepared on the host once; the sizes are the sensor's and
+    the ids index ``sample_names``.  ``indices`` are this rank's samples; the last batch may be short."""
+
+    def __init__(self, exp, batch_size, indices, store):
+        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+        self.dataset = NCaltechStoreDataset(exp, store)
         self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
 
     def __len__(self):

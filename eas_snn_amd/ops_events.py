@@ -135,6 +135,67 @@ def event_latest_surface_atis(records, sample_offsets, Tl, Tm, H, W, window=None
                         H, W, window, (float(tau),), return_oob, return_flags)
 
 
+def atis_store_index(records):
+    """The overflow index of a buffer of ATIS recordings resident in HBM: uint32 [chunks + 1] (as an int32 tensor), entry c = overflow
+    records in front of record 256 * c, the last entry all of them.  Two launches over the buffer, once per store; the ``*_atis_store``
+    operators take it with the ``records`` it was made from (the same view: chunks are counted from its first byte)."""
+    _dev(records)
+    assert records.dtype == torch.uint8 and records.is_contiguous() and records.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    nrec = records.numel() // 5
+    index = torch.empty(_lib.lib().eas_atis_store_index_bytes(nrec) // 4, dtype=torch.int32, device=records.device)
+    _call('eas_atis_store_index', 5 * nrec + 8 * index.numel(), _lib.lib().eas_atis_store_index, ptr(records), nrec, ptr(index), stream())
+    return index
+
+
+def _atis_store_frames(entry, dtype, workspace_query, out_bytes, records, file_offsets, index, sample_file, Tl, Tm, H, W, window, tau, return_oob,
+                       return_flags, max_file_records):
+    """the three store wrappers: ``_atis_frames`` for recordings picked out of a resident store.  bytes: at most ``max_file_records`` records
+    per sample, once, + ``out_bytes`` per element of the frames -- not the store"""
+    _dev(records, file_offsets, index, sample_file)
+    assert records.dtype == torch.uint8 and records.is_contiguous() and records.numel() % 5 == 0, 'ATIS records are 5 bytes'
+    assert file_offsets.dtype == torch.int64 and file_offsets.dim() == 1 and file_offsets.numel() >= 1 and file_offsets.is_contiguous()
+    assert sample_file.dtype == torch.int64 and sample_file.dim() == 1
+    nrec, F, B = records.numel() // 5, file_offsets.numel() - 1, sample_file.numel()
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == _lib.lib().eas_atis_store_index_bytes(nrec) // 4, \
+        'the index is not atis_store_index(records)'
+    max_file_records = nrec if max_file_records is None else int(max_file_records)
+    lo, hi = (0, 0) if window is None or window[0] >= 0 else (int(window[0]), int(window[1]))
+    out = torch.empty((B, Tl, Tm, 2, H, W), dtype=dtype, device=records.device)
+    oob = torch.empty(B, dtype=torch.int32, device=records.device) if return_oob else None
+    flags = torch.empty(B, dtype=torch.int32, device=records.device) if return_flags else None
+    ws = torch.empty(getattr(_lib.lib(), workspace_query)(B, Tl), dtype=torch.uint8, device=records.device)
+    _call(entry, 5 * max_file_records * B + out_bytes * out.numel(), getattr(_lib.lib(), entry), ptr(records), nrec, ptr(file_offsets), F,
+          ptr(sample_file.contiguous()), B, ptr(index), max_file_records, lo, hi, Tl, Tm, H, W, *tau, ptr(out), ptr(oob), ptr(flags), ptr(ws), stream())
+    res = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return res if len(res) > 1 else out
+
+
+def event_histogram_atis_store(records, file_offsets, index, sample_file, Tl, Tm, H, W, window=None, return_oob=False, return_flags=False,
+                               max_file_records=None):
+    """``event_histogram_atis`` of recordings picked out of a store resident in HBM: ``records`` uint8 (every recording back to back),
+    ``file_offsets`` int64 [F + 1] record indices, ``index`` = ``atis_store_index(records)``, ``sample_file`` int64 [B] (recording b of the
+    batch is file ``sample_file[b]``; an index may repeat) -> int32 [B, Tl, Tm, 2, H, W], bit for bit what the packed operator gives on those
+    recordings.  The work is the batch's: nothing outside the B recordings is counted or scanned.  ``max_file_records``: the store's longest
+    recording (None: the whole buffer); it sizes the grid only.  An entry outside [0, F) gives zero frames and flags bit 4 (value 16) besides
+    bit 1.  Nothing is read back (graph-capturable)."""
+    return _atis_store_frames('eas_event_histogram_atis_store', torch.int32, 'eas_atis_store_workspace_bytes', 4, records, file_offsets, index,
+                              sample_file, Tl, Tm, H, W, window, (), return_oob, return_flags, max_file_records)
+
+
+def event_timesurface_atis_store(records, file_offsets, index, sample_file, Tl, Tm, H, W, window=None, tau=500e3, return_oob=False,
+                                 return_flags=False, max_file_records=None):
+    """``event_timesurface_atis`` (measure 'timesurface') on a store: the arguments of ``event_histogram_atis_store``, float64 frames"""
+    return _atis_store_frames('eas_event_timesurface_atis_store', torch.float64, 'eas_atis_store_timesurface_workspace_bytes', 24, records,
+                              file_offsets, index, sample_file, Tl, Tm, H, W, window, (float(tau),), return_oob, return_flags, max_file_records)
+
+
+def event_latest_surface_atis_store(records, file_offsets, index, sample_file, Tl, Tm, H, W, window=None, tau=10e3, return_oob=False,
+                                    return_flags=False, max_file_records=None):
+    """``event_latest_surface_atis`` (aggregation 'timesurface') on a store: the arguments of ``event_histogram_atis_store``, float64 frames"""
+    return _atis_store_frames('eas_event_latest_surface_atis_store', torch.float64, 'eas_atis_store_workspace_bytes', 24, records, file_offsets,
+                              index, sample_file, Tl, Tm, H, W, window, (float(tau),), return_oob, return_flags, max_file_records)
+
+
 def event_latest_surface_dat_ranges(records, ranges, num_slices, H, W, tau=50e3, return_oob=False):
     """``event_time_surface`` (Gen1's ``aggregation timesurface``) of the record ranges [B, 2] (``event_window_search``) of a .dat image in
     HBM: float64 [B, num_slices, 2, H, W], bit-identical to ``event_time_surface`` on the decoded arrays of the same samples; an empty range

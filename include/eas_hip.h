@@ -159,6 +159,37 @@ int eas_event_timesurface_atis(const void* records, int64_t nrec, const int64_t*
 int eas_event_latest_surface_atis(const void* records, int64_t nrec, const int64_t* sample_offsets, int B, int64_t window_lo, int64_t window_hi,
                                   int Tl, int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
                                   eas_stream_t stream);
+/* N-Caltech101 from a store (additive, ABI 9): a whole dataset of ATIS recordings resident in HBM, `records` / nrec as above, recording f =
+ * records [file_offsets[f], file_offsets[f+1]) (file_offsets int64 [F + 1], device).  The overflow prefix of the buffer is computed ONCE:
+ * eas_atis_store_index writes chunk_base, uint32 [chunks + 1] = eas_atis_store_index_bytes(nrec) bytes, chunks = ceil(nrec / 256):
+ * chunk_base[c] = overflow records in front of record 256 c (the exclusive scan of the per-chunk counts; the last word counts all of
+ * them).  Two launches over the buffer, the ones every eas_event_*_atis call runs on its own workspace.  The index belongs to the
+ * `records` pointer it was made from: chunks are counted from that address. */
+int64_t eas_atis_store_index_bytes(int64_t nrec);
+int eas_atis_store_index(const void* records, int64_t nrec, uint32_t* chunk_base, eas_stream_t stream);
+/* A step on the store: the three entries above for the B recordings sample_file picks (int64 [B], device; recording b of the call is file
+ * sample_file[b]; an index may repeat), through the same device code: outputs, window rule, slicing, accumulate steps, oob_count and flag
+ * bits 0 .. 3 are those of the namesake, bit for bit what it gives on the same recordings packed back to back.  No count and no scan is
+ * launched and no record outside the B recordings' chunks and the plan's probes is read: 5 * (records of the batch) bytes + the frames.
+ * File offsets are clamped to [0, nrec] as sample_offsets are.  A sample_file entry outside [0, F) is an empty recording: zero frames,
+ * flags[b] bit 4 (value 16) besides bit 1, and nothing is read through it.  max_file_records: an upper bound of the longest recording
+ * (host); it sizes the grid only (blocks per recording = min(ceil(max_file_records / 256) + 1, 64)), a wrong value costs time, not
+ * correctness.  workspace: eas_atis_store_workspace_bytes(B, Tl) bytes (the time-surface measure:
+ * eas_atis_store_timesurface_workspace_bytes(B, Tl)), 16-byte aligned; it does not grow with the store.  Nothing is allocated or read
+ * back (graph-capturable). */
+int64_t eas_atis_store_workspace_bytes(int B, int Tl);
+int64_t eas_atis_store_timesurface_workspace_bytes(int B, int Tl);
+int eas_event_histogram_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                   const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
+                                   int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, void* workspace, eas_stream_t stream);
+int eas_event_timesurface_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                     const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl, int Tm,
+                                     int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                     eas_stream_t stream);
+int eas_event_latest_surface_atis_store(const void* records, int64_t nrec, const int64_t* file_offsets, int64_t F, const int64_t* sample_file, int B,
+                                        const uint32_t* chunk_base, int64_t max_file_records, int64_t window_lo, int64_t window_hi, int Tl,
+                                        int Tm, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags, void* workspace,
+                                        eas_stream_t stream);
 /* eas_counts_letterbox_ex on float64 frames [B][F][H][W] (those of eas_event_timesurface_atis): the same kernel body on a double source --
  * cv2.resize of the reference sees float64 images for both measures --, so frames that hold integers give the bits the counts give. */
 int eas_frames_letterbox_f64(const double* frames, const int32_t* params, int interp, int B, int F, int H, int W, int Hc, int Wc, float* out,
