@@ -184,6 +184,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)
             from eas_snn_amd.data import NCaltechStoreLoader
             return NCaltechStoreLoader(self, batch_size)
+        if getattr(self, 'train_input', None) == 'hist_store':         # opt-in: 1 Mpx from recordings in HBM (sample indices -> frames and targets)
+            from eas_snn_amd.data import Gen4StoreLoader
+            return Gen4StoreLoader(self, batch_size)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):
@@ -194,6 +197,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'atis_store':
             from eas_snn_amd.data import NCaltechStoreDataset, ncaltech_store_for
             return NCaltechStoreDataset(self, ncaltech_store_for(self, 'test' if kwargs.get('testdev', False) else 'val'))
+        if getattr(self, 'train_input', None) == 'hist_store':
+            from eas_snn_amd.data import Gen4StoreDataset, hist_store_for
+            return Gen4StoreDataset(self, hist_store_for(self, 'test'))
         return SyntheticEvalDataset(self, length=int(getattr(self, 'eval_samples', 256)), n_events=int(getattr(self, 'eval_events', 200_000)))
 
     def get_eval_loader(self, batch_size, is_distributed, **kwargs):
@@ -216,6 +222,9 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'atis_store':
             from eas_snn_amd.data import NCaltechStoreEvalLoader
             return NCaltechStoreEvalLoader(self, batch_size, idx, valdataset.store)
+        if getattr(self, 'train_input', None) == 'hist_store':
+            from eas_snn_amd.data import Gen4StoreEvalLoader
+            return Gen4StoreEvalLoader(self, batch_size, idx, valdataset.store)
         # synthetic streams on the Gen1 sensor (or on the canvas itself when that is smaller); ``eval_sensor_hw`` / ``eval_events`` override
         sensor = getattr(self, 'eval_sensor_hw', None) or (min(240, self.test_size[0]), min(304, self.test_size[1]))
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)
@@ -224,7 +233,7 @@ class EventExp(BaseExp):
         """reference: event_yolox_base.py:509-534.  ``eval_proph`` on a gen* dataset selects PSEEEvaluator (the Prophesee protocol,
         psee_evaluator.py) when the samples of the evaluation dataset carry their label time in their names (``<recording>a<time in us>``,
         what the protocol matches on): the samples of a ``train_input = 'dat_store'`` evaluation do (``<recording>_r<index>_a<time>``, the
-        reference's own names); the synthetic event samples do not unless ``eval_label_period_us`` is set, and then EventEvaluator answers,
+        reference's own names), and so do those of ``'hist_store'`` (``<stream>_n<num_slice>_a<time>``; gen4: ``downsample_by_2``); the synthetic event samples do not unless ``eval_label_period_us`` is set, and then EventEvaluator answers,
         with a warning."""
         from yolox.evaluators import EventEvaluator
         loader = self.get_eval_loader(batch_size, is_distributed, testdev=testdev, legacy=legacy)

@@ -1,5 +1,6 @@
-// RVT "stacked histogram" representations -> per-polarity event counts on the model canvas: two kernels over shared pieces (SliceRule:
-// which representation feeds a slice; bin_sums16: the bin sum of 16 pixels; the paste and resize rule of count_resize.h).
+// RVT "stacked histogram" representations -> per-polarity event counts on the model canvas: three kernels over shared pieces (SliceRule:
+// which representation feeds a slice; bin_sums16: the bin sum of 16 pixels; the paste and resize rule of count_resize.h; the row sources
+// BinPlanes / SumPlanes: what the band kernel stages, from the representations as they are or from their bin sums).
 //
 // eas_stacked_hist_event_sum, the config-4 input: replaces RVTGEN4Dataset.generate_slices(..., method='event_sum') + the zero padding of the
 // validation letterbox (yolox/data/datasets/rvt_gen4.py:109-125 and :516-533 with scale 1).
@@ -121,6 +122,81 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_sum_kernel(const uint8
     }
 }
 
+// eas_stacked_hist_bin_sums, the builder of the summed store: one thread owns 16 consecutive pixels of one (representation, polarity, row)
+// -- nbins 16-byte loads, two 16-byte stores; bytes and 16-bit elements one by one where rows are not 16-byte aligned (W % 16 != 0)
+template <int NB>
+__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_bin_sums_kernel(const uint8_t* __restrict__ hist, int nbins_rt, int H, int W,
+                                                                          uint16_t* __restrict__ sums, int64_t total_groups) {
+    const int nbins = NB > 0 ? NB : nbins_rt;
+    const int wg = (W + 15) / 16;                        // 16-pixel groups per row, the last one ragged
+    const int64_t plane = (int64_t)H * W;
+    const bool vec = (W & 15) == 0;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total_groups; g += (int64_t)gridDim.x * blockDim.x) {
+        const int x0 = (int)(g % wg) * 16;
+        int64_t r = g / wg;
+        const int y = (int)(r % H);
+        r /= H;                                          // representation * 2 + polarity
+        uint32_t sum[8];
+        bin_sums16<NB>(hist + r * nbins * plane + (int64_t)y * W + x0, plane, nbins, vec, W - x0, sum);
+        uint16_t* d = sums + r * plane + (int64_t)y * W + x0;
+        if (vec) {
+            reinterpret_cast<uint4*>(d)[0] = make_uint4(sum[0], sum[1], sum[2], sum[3]);
+            reinterpret_cast<uint4*>(d)[1] = make_uint4(sum[4], sum[5], sum[6], sum[7]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                if (e < W - x0) d[e] = (uint16_t)(sum[e >> 1] >> (16 * (e & 1)));
+        }
+    }
+}
+
+// ---- row sources of the band kernel ----------------------------------------------------------------------------------------------------
+// A source is one polarity of one representation; sums16 hands out the bin sums of pixels x0 .. x0 + 15 of one of its rows as eight words
+// of two 16-bit sums, pixel order (pixels at and behind W: zero).
+// the representations as they are, u8 [R][2 * nbins][H][W]: nbins byte-plane loads and adds
+template <int NB>
+struct BinPlanes {
+    using elem = uint8_t;
+    const uint8_t* src0;
+    int64_t plane;
+    int nbins, W;
+    bool aligned;
+    __device__ __forceinline__ BinPlanes(const uint8_t* __restrict__ store, int64_t rep, int p, int nbins_rt, int H, int W_)
+        : plane((int64_t)H * W_), nbins(NB > 0 ? NB : nbins_rt), W(W_), aligned((W_ & 15) == 0) {
+        src0 = store + ((rep * 2 + p) * nbins) * plane;
+    }
+    __device__ __forceinline__ void sums16(int row, int x0, uint32_t (&sum)[8]) const {
+        bin_sums16<NB>(src0 + (int64_t)row * W + x0, plane, nbins, aligned, W - x0, sum);
+    }
+};
+// their bin sums, u16 [R][2][H][W] (eas_stacked_hist_bin_sums): a copy of 16-bit rows, 16-byte loads where rows are 16-byte aligned
+// (W % 8 == 0: a row then ends on a 16-byte boundary, so a group holds 8 or 16 pixels), element by element otherwise
+struct SumPlanes {
+    using elem = uint16_t;
+    const uint16_t* src0;
+    int W;
+    bool aligned;
+    __device__ __forceinline__ SumPlanes(const uint16_t* __restrict__ store, int64_t rep, int p, int, int H, int W_) : W(W_), aligned((W_ & 7) == 0) {
+        src0 = store + (rep * 2 + p) * ((int64_t)H * W_);
+    }
+    __device__ __forceinline__ void sums16(int row, int x0, uint32_t (&sum)[8]) const {
+        const uint16_t* src = src0 + (int64_t)row * W + x0;
+        const int n_left = W - x0;
+        if (aligned) {
+            const uint4 a = reinterpret_cast<const uint4*>(src)[0];
+            const uint4 b = n_left >= 16 ? reinterpret_cast<const uint4*>(src)[1] : make_uint4(0u, 0u, 0u, 0u);
+            sum[0] = a.x; sum[1] = a.y; sum[2] = a.z; sum[3] = a.w;
+            sum[4] = b.x; sum[5] = b.y; sum[6] = b.z; sum[7] = b.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) sum[q] = 0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                if (e < n_left) sum[e >> 1] |= (uint32_t)src[e] << (16 * (e & 1));
+        }
+    }
+};
+
 // ---- training input: indices into a resident store -> augmented frames (eas_stacked_hist_frames) --------------------------------------
 // RVTGEN4Dataset.__getitem__ for a training sample (rvt_gen4.py:190-235): the last Tm representations up to the label's
 // (generate_slices, :109-125, zero slices in front of a young sequence), the bin sum, then get_random_data's resize / paste / flip with cv2.INTER_LINEAR (:510-598) -- the arithmetic of
@@ -132,22 +208,24 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_sum_kernel(const uint8
 // every output pixel is a gather from LDS with the horizontal taps of the band (one table per block) and the stores are float4.  Zero
 // slices and bands outside the paste rectangle are stores only.  Everything read from device memory is clamped: a slice index by
 // SliceRule, the paste row by Paste (count_resize.h), and a source row or column index comes out of linear_tap, which clamps to the sensor.
+// The staging step reads through a row source (above): BinPlanes for eas_stacked_hist_frames, SumPlanes -- the same rows already summed,
+// 2 bytes per pixel in place of nbins -- for eas_count_store_frames; everything else is one body.
 constexpr int kFrameBandRows = 8;             // output rows per block at most (fewer on wide sensors: frames_band_rows)
 constexpr int kFrameLdsBytes = 48 * 1024;     // staged rows + tap tables
 
 struct XTap { uint32_t s01; float w1; };      // s0 | s1 << 16; w1 < 0: outside the paste rectangle
 
-template <int NB>
-__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const uint8_t* __restrict__ store, int64_t R, const int64_t* __restrict__ first,
-                                                                        const int64_t* __restrict__ lo, const int32_t* __restrict__ params,
-                                                                        int Tm, int nbins_rt, int H, int W, int Hc, int Wc, int band_rows,
-                                                                        int nbands, float* __restrict__ out, uint32_t* __restrict__ flags) {
+template <typename Src>
+__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const typename Src::elem* __restrict__ store, int64_t R,
+                                                                        const int64_t* __restrict__ first, const int64_t* __restrict__ lo,
+                                                                        const int32_t* __restrict__ params, int Tm, int nbins_rt, int H, int W,
+                                                                        int Hc, int Wc, int band_rows, int nbands, float* __restrict__ out,
+                                                                        uint32_t* __restrict__ flags) {
     extern __shared__ __attribute__((aligned(16))) unsigned char frames_lds[];
     __shared__ int y_s0[kFrameBandRows], y_s1[kFrameBandRows], y_slot0[kFrameBandRows], y_slot1[kFrameBandRows];
     __shared__ float y_w1[kFrameBandRows];
     __shared__ int slot_row[2 * kFrameBandRows];
     __shared__ int n_slots;
-    const int nbins = NB > 0 ? NB : nbins_rt;
     const int wp = (W + 15) & ~15;                        // staged row pitch in pixels
     uint16_t* stage = reinterpret_cast<uint16_t*>(frames_lds);                                             // [2 * band_rows][wp]
     XTap* xtab = reinterpret_cast<XTap*>(frames_lds + (size_t)2 * band_rows * wp * sizeof(uint16_t));      // [Wc]
@@ -206,13 +284,11 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const ui
 
     // stage the bin sums of the named rows
     const int wg = wp / 16, n_groups = n_slots * wg;
-    const int64_t plane = (int64_t)H * W;
-    const uint8_t* src0 = store + ((slice.index(j) * 2 + p) * nbins) * plane;
-    const bool aligned = (W & 15) == 0;
+    const Src src(store, slice.index(j), p, nbins_rt, H, W);
     for (int g = tid; g < n_groups; g += EAS_BLOCK) {
         const int slot = g / wg, x0 = (g - slot * wg) * 16;
         uint32_t sum[8];
-        bin_sums16<NB>(src0 + (int64_t)slot_row[slot] * W + x0, plane, nbins, aligned, W - x0, sum);
+        src.sums16(slot_row[slot], x0, sum);
         uint4* d = reinterpret_cast<uint4*>(stage + (size_t)slot * wp + x0);
         d[0] = make_uint4(sum[0], sum[1], sum[2], sum[3]);
         d[1] = make_uint4(sum[4], sum[5], sum[6], sum[7]);
@@ -249,6 +325,28 @@ int frames_band_rows(int W, int Wc) {
     return rows;
 }
 
+// the two frame entries: the argument checks, the band plan and the launch of the band kernel on the entry's row source
+template <typename Src>
+int frames_call(const typename Src::elem* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm, int nbins,
+                int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream) {
+    if (!store || !first || !out || R < 1 || B < 1 || Tm < 1 || nbins < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
+    if ((((uintptr_t)store | (uintptr_t)out) & 15) || (((uintptr_t)first | (uintptr_t)lo) & 7) || (((uintptr_t)params | (uintptr_t)flags) & 3))
+        return EAS_ERR_INVALID_ARG;
+    if (Wc % 16 != 0 || nbins > 255 || W > 65536) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32; taps are 16 bits
+    const int band_rows = frames_band_rows(W, Wc);
+    if (band_rows < 1) return EAS_ERR_UNSUPPORTED;
+    const int nbands = (Hc + band_rows - 1) / band_rows;
+    const int64_t blocks = (int64_t)B * Tm * 2 * nbands;
+    if (blocks > INT32_MAX) return EAS_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)2 * band_rows * ((W + 15) & ~15) * sizeof(uint16_t) + (size_t)Wc * sizeof(XTap);
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH((stacked_hist_frames_kernel<Src>), dim3((unsigned)blocks), dim3(EAS_BLOCK), lds, st, store, R, first, lo, params, Tm, nbins, H, W, Hc,
+               Wc, band_rows, nbands, out, flags);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
 }  // namespace
 
 extern "C" int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int B, int Tm, int nbins, int H, int W, int Hc,
@@ -271,24 +369,29 @@ extern "C" int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_
 
 extern "C" int eas_stacked_hist_frames(const uint8_t* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B,
                                        int Tm, int nbins, int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream) {
-    if (!store || !first || !out || R < 1 || B < 1 || Tm < 1 || nbins < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
-    if ((((uintptr_t)store | (uintptr_t)out) & 15) || (((uintptr_t)first | (uintptr_t)lo) & 7) || (((uintptr_t)params | (uintptr_t)flags) & 3))
-        return EAS_ERR_INVALID_ARG;
-    if (Wc % 16 != 0 || nbins > 255 || W > 65536) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32; taps are 16 bits
-    const int band_rows = frames_band_rows(W, Wc);
-    if (band_rows < 1) return EAS_ERR_UNSUPPORTED;
-    const int nbands = (Hc + band_rows - 1) / band_rows;
-    const int64_t blocks = (int64_t)B * Tm * 2 * nbands;
-    if (blocks > INT32_MAX) return EAS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)2 * band_rows * ((W + 15) & ~15) * sizeof(uint16_t) + (size_t)Wc * sizeof(XTap);
+    if (nbins == 10) return frames_call<BinPlanes<10>>(store, R, first, lo, params, B, Tm, nbins, H, W, Hc, Wc, out, flags, stream);
+    return frames_call<BinPlanes<0>>(store, R, first, lo, params, B, Tm, nbins, H, W, Hc, Wc, out, flags, stream);
+}
+
+extern "C" int eas_count_store_frames(const uint16_t* sums, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm,
+                                      int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream) {
+    return frames_call<SumPlanes>(sums, R, first, lo, params, B, Tm, 1, H, W, Hc, Wc, out, flags, stream);
+}
+
+extern "C" int eas_stacked_hist_bin_sums(const uint8_t* hist, int64_t n, int nbins, int H, int W, uint16_t* sums, eas_stream_t stream) {
+    if (!hist || !sums || n < 0 || nbins < 1 || H < 1 || W < 1) return EAS_ERR_INVALID_ARG;
+    if (nbins > 255) return EAS_ERR_UNSUPPORTED;                                    // a bin sum is held in 16 bits
+    // rows of 16-byte loads and stores (W % 16 == 0: every chunk offset of such a store keeps the alignment); else bytes and 16-bit elements
+    if (((uintptr_t)sums & 1) || ((W & 15) == 0 && (((uintptr_t)hist | (uintptr_t)sums) & 15))) return EAS_ERR_INVALID_ARG;
+    if (n == 0) return EAS_OK;
+    const int64_t groups = n * 2 * H * ((W + 15) / 16);
+    const int grid = eas_grid_1d(groups, EAS_BLOCK, 1 << 20);
     hipStream_t st = eas_s(stream);
     EAS_CLEAR_ERR();
     if (nbins == 10)
-        EAS_LAUNCH((stacked_hist_frames_kernel<10>), dim3((unsigned)blocks), dim3(EAS_BLOCK), lds, st, store, R, first, lo, params, Tm, nbins, H, W,
-                   Hc, Wc, band_rows, nbands, out, flags);
+        EAS_LAUNCH((stacked_hist_bin_sums_kernel<10>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, nbins, H, W, sums, groups);
     else
-        EAS_LAUNCH((stacked_hist_frames_kernel<0>), dim3((unsigned)blocks), dim3(EAS_BLOCK), lds, st, store, R, first, lo, params, Tm, nbins, H, W,
-                   Hc, Wc, band_rows, nbands, out, flags);
+        EAS_LAUNCH((stacked_hist_bin_sums_kernel<0>), dim3(grid), dim3(EAS_BLOCK), 0, st, hist, nbins, H, W, sums, groups);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
 }

@@ -749,6 +749,227 @@ class Gen1StoreEvalLoader:
             yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
 
 
+# ------------------------------------------------------------------------------------------------ 1 Mpx from recordings resident in HBM
+GEN4_REP_NAME = 'stacked_histogram_dt=50_nbins=10'        # RVTGEN4Dataset's default ``rep_name``
+GEN4_LABEL_FIELDS = ('t', 'x', 'y', 'w', 'h', 'class_id', 'class_confidence')        # _str2idx, rvt_gen4.py:34-42
+GEN4_BBOX_DTYPE = np.dtype([('t', '<u8'), ('x', '<f4'), ('y', '<f4'), ('w', '<f4'), ('h', '<f4'), ('class_id', 'u1'), ('class_confidence', '<f4')])
+
+
+def synth_gen4_recordings(n_files, representations, sensor_hw=(360, 640), nbins=10, num_classes=3, seed=0):
+    """``n_files`` seeded recordings ``(name, representations, objframe_idx_2_repr_idx, label_rows, objframe_idx_2_label_idx, label_times)``
+    as ``Gen4Store`` takes them, so that the store and its loaders run without a dataset.  Representations: u8 [representations, 2 * nbins,
+    H, W], Poisson(0.03) clamped to 255 (the histograms of ``SyntheticStackedHistLoader.store``), 50 ms apart.  Object frames: at
+    representations 1, 3, 4, 6, 7, 9, ... (two of every three; the first is younger than a sample of three slices), label time = the end of
+    the representation, the first one at 450 ms.  Object frame k carries 3, 0, 1, 2 boxes for k % 4 = 0, 1, 2, 3, some of them across the
+    borders; the rows (``GEN4_BBOX_DTYPE``) are in the coordinates of the stored labels, twice the sensor's (``down_sample_factor`` 2)."""
+    H, W = sensor_hw
+    out = []
+    for f in range(n_files):
+        rng = np.random.default_rng([seed, f])
+        reps = np.minimum(rng.poisson(0.03, size=(representations, 2 * nbins, H, W)), 255).astype(np.uint8)
+        obj2repr = np.array([i for i in range(1, representations) if i % 3 != 2], dtype=np.int64)
+        times = 400_000 + 50_000 * (obj2repr + 1)
+        rows, first = [], []
+        for k, t in enumerate(times):
+            first.append(len(rows))
+            for _ in range((3, 0, 1, 2)[k % 4]):
+                bw, bh = rng.uniform(0.15, 0.4) * 2 * W, rng.uniform(0.15, 0.4) * 2 * H
+                bx, by = rng.uniform(-0.1, 0.9) * 2 * W, rng.uniform(-0.1, 0.9) * 2 * H
+                rows.append((int(t), bx, by, bw, bh, int(rng.integers(0, max(num_classes, 1))), 1.0))
+        out.append((f'synthetic_{seed}_{f:03d}', reps, obj2repr, np.array(rows, dtype=GEN4_BBOX_DTYPE), np.asarray(first, dtype=np.int64),
+                    times.astype(np.int64)))
+    return out
+
+
+def _h5_representations(rep_dir):
+    """``data`` of ``<rep_dir>/event_representations_ds2_nearest.h5``, left open: the file RVTGEN4Dataset.generate_slices reads
+    (rvt_gen4.py:118-119)"""
+    import os
+    try:
+        import h5py
+    except ImportError as e:
+        raise ImportError('reading event_representations_ds2_nearest.h5 needs h5py, which is not installed; pass read_representations= (a '
+                          'function of the representation directory that returns something that slices to u8 [r, 2 * nbins, H, W])') from e
+    return h5py.File(os.path.join(rep_dir, 'event_representations_ds2_nearest.h5'), 'r')['data']
+
+
+class Gen4Store:
+    """1 Mpx (Gen4, RVT pre-processed) recordings and their labels resident on the device: what RVTGEN4Dataset keeps on disk and in host lists
+    (rvt_gen4.py:93-97, 365-409), as tables that the kernels index.  ``recordings``: a list of ``(name, representations,
+    objframe_idx_2_repr_idx, label_rows, objframe_idx_2_label_idx, label_times)`` -- ``representations`` is anything that has a length and
+    slices to u8 [r, 2 * nbins, H, W] (a numpy array, a memmap, an h5py dataset); ``label_rows`` the structured ``labels`` array of
+    ``labels.npz`` (fields ``GEN4_LABEL_FIELDS``) or float rows [L, 7] in that order; ``label_times`` one time per object frame (another
+    length raises ValueError, as the reference asserts).  ``num_slice``: representations per sample -- the reference's ``num_slice`` slice
+    argument, ``exp.Tm`` on this project's 1 Mpx path.
+
+    The model only ever sees the bin sums (generate_slices with ``'event_sum'``, rvt_gen4.py:120-122), so the sums are what is kept:
+    ``sums`` ``torch.uint16`` [R, 2, H, W], allocated once at its final size; every recording is read ``chunk`` representations at a time,
+    uploaded, and summed into its place by ``ops.stacked_hist_bin_sums`` -- exact, 2 bytes per pixel and polarity where the representations
+    hold ``nbins``, and the u8 form never exists whole on the device.  Built on the host and uploaded once: ``rep_offsets`` int64 [F + 1]
+    (index in ``sums`` of every recording's first representation), ``group_first`` int64 [G] (``rvt_first_index``: the representation that
+    feeds slice 0 of the sample; below ``group_lo`` for a young sequence), ``group_lo`` int64 [G] (the offset of the sample's recording),
+    ``boxes`` float32 [L, 5] rows (x1, y1, x2, y2, class) -- ``gen4_raw_boxes(gen4_rescale_labels(rows, down_sample_factor, sensor_hw))`` per
+    object frame, cut as extract_labels cuts the rows (the last frame open-ended) -- and ``group_start`` int64 [G + 1].  On the host:
+    ``sample_names`` ``<name>_n<num_slice>_a<label time>`` (get_sample_resp, rvt_gen4.py:246-248), ``group_rows``, ``max_group_rows`` and
+    numpy copies of the tables (``host``).  Every object frame is a sample, one without boxes too (the reference's ``__len__`` counts object
+    frames); the flat sample index is recordings in the order given, then object frames in order (resolve_index, rvt_gen4.py:296-300).
+
+    ``device='cpu'`` builds the tables and leaves ``sums`` None: the representations are only measured, there is no summing on the host.
+
+    A store holds the recordings it is given; cutting a dataset that exceeds HBM into shards is the caller's business."""
+
+    def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64):
+        self.num_slice, self.sensor_hw, self.nbins = int(num_slice), (int(sensor_hw[0]), int(sensor_hw[1])), int(nbins)
+        self.down_sample_factor = down_sample_factor
+        self.names, self.sample_names = [], []
+        H, W = self.sensor_hw
+        reps, rep_offsets, boxes, group_start, group_first, group_lo = [], [0], [], [0], [], []
+        for name, rep, obj2repr, rows, obj2label, label_times in recordings:
+            if tuple(rep.shape[1:]) != (2 * self.nbins, H, W):
+                raise ValueError(f'{name}: representations of shape {tuple(rep.shape)}, expected [r, {2 * self.nbins}, {H}, {W}]')
+            obj2repr, obj2label = np.asarray(obj2repr, dtype=np.int64), np.asarray(obj2label, dtype=np.int64)
+            if len(label_times) != len(obj2label):
+                raise ValueError(f'{name}: {len(label_times)} label times for {len(obj2label)} object frames')
+            if getattr(rows, 'dtype', None) is not None and rows.dtype.names:
+                rows = np.stack([rows[k].astype(np.float32) for k in GEN4_LABEL_FIELDS], axis=-1).reshape(-1, 7)
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, 7)
+            self.names.append(name)
+            offset = rep_offsets[-1]
+            reps.append(rep)
+            rep_offsets.append(offset + len(rep))
+            ends = np.r_[obj2label[1:], len(rows)]
+            for k, (a, b) in enumerate(zip(obj2label, ends)):
+                box = gen4_raw_boxes(gen4_rescale_labels(rows[a:b], down_sample_factor, self.sensor_hw))
+                boxes.append(box.astype(np.float32).reshape(-1, 5))
+                group_start.append(group_start[-1] + len(box))
+                group_first.append(int(rvt_first_index(obj2repr, k, self.num_slice, offset)))
+                group_lo.append(offset)
+                self.sample_names.append(f'{name}_n{self.num_slice}_a{int(label_times[k])}')
+        self.host = dict(rep_offsets=np.asarray(rep_offsets, dtype=np.int64), group_first=np.asarray(group_first, dtype=np.int64),
+                         group_lo=np.asarray(group_lo, dtype=np.int64),
+                         boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
+                         group_start=np.asarray(group_start, dtype=np.int64))
+        self.group_rows = np.diff(self.host['group_start'])
+        self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
+        self.device = torch.device(device)
+        for k, v in self.host.items():
+            setattr(self, k, torch.from_numpy(v).to(self.device))
+        self.sums = None
+        if self.device.type != 'cpu':
+            self.sums = torch.empty((rep_offsets[-1], 2, H, W), dtype=torch.uint16, device=self.device)
+            for rep, offset in zip(reps, rep_offsets):
+                for a in range(0, len(rep), int(chunk)):
+                    part = torch.from_numpy(np.ascontiguousarray(rep[a:a + int(chunk)], dtype=np.uint8)).to(self.device)
+                    ops.stacked_hist_bin_sums(part, self.nbins, out=self.sums[offset + a:offset + a + part.shape[0]])
+
+    @classmethod
+    def from_directories(cls, paths, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, rep_name=GEN4_REP_NAME,
+                         read_representations=None):
+        """the streams of the directories ``paths`` (extract_labels, rvt_gen4.py:389-407), every directory in sorted order (the reference
+        takes them as ``os.listdir`` gives them): ``<stream>/labels_v2/labels.npz`` (``labels``, ``objframe_idx_2_label_idx``) and
+        ``timestamps_us.npy``, ``<stream>/event_representations_v2/<rep_name>/objframe_idx_2_repr_idx.npy``, and the representations from
+        ``read_representations(rep_dir)``.  Its default opens ``event_representations_ds2_nearest.h5`` with ``h5py`` (imported there; an
+        ImportError that names ``h5py`` and this argument when it is missing) and returns its ``data``.  ``h5py`` is not among this
+        project's requirements: that default is the one line of the store no test reaches."""
+        import os
+        read = read_representations if read_representations is not None else _h5_representations
+        recs = []
+        for path in ([paths] if isinstance(paths, str) else paths):
+            for stream in sorted(os.listdir(path)):
+                label_dir = os.path.join(path, stream, 'labels_v2')
+                rep_dir = os.path.join(path, stream, 'event_representations_v2', rep_name)
+                labels = np.load(os.path.join(label_dir, 'labels.npz'))
+                recs.append((stream, read(rep_dir), np.load(os.path.join(rep_dir, 'objframe_idx_2_repr_idx.npy')), labels['labels'],
+                             labels['objframe_idx_2_label_idx'], np.load(os.path.join(label_dir, 'timestamps_us.npy'))))
+        return cls(recs, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk)
+
+    def __len__(self):
+        return len(self.sample_names)
+
+    def raw_labels(self, index):
+        """float32 [n, 5] rows (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands them out (``map_val``,
+        ``format='xywh'``, rvt_gen4.py:227-230: ``xyxy2xywh`` of the raw boxes -- rescaled by extract_labels, not transformed)"""
+        a, b = self.host['group_start'][index], self.host['group_start'][index + 1]
+        box = self.host['boxes'][a:b].copy()
+        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        return box
+
+    def frames(self, sample_idx, params, exp, canvas_hw=None):
+        """model input [B, 1, num_slice, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): ``group_first`` and
+        ``group_lo`` gathered on the device, then ``ops.count_store_frames``; ``params``: (nw, nh, dx, dy, flip) per sample, None = the
+        sensor unscaled at the top left; ``canvas_hw``: ``exp.input_size`` unless given.  ``exp.Tm`` must be the store's ``num_slice``;
+        ``exp.aggregation`` is not consulted (the representations are histograms already).  Nothing is read back (graph-capturable)."""
+        if getattr(exp, 'Tm', self.num_slice) != self.num_slice:
+            raise ValueError(f'the store was built for {self.num_slice} slices per sample, the experiment asks for Tm = {exp.Tm}')
+        Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
+        return ops.count_store_frames(self.sums, self.group_first[sample_idx], self.num_slice, Hc, Wc, lo=self.group_lo[sample_idx],
+                                      params=None if params is None else params_on(params, self.device))
+
+    def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
+        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
+        box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
+        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
+                                 canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
+
+
+def hist_store_for(exp, split='train', device=None):
+    """The store of an experiment with ``train_input = 'hist_store'``: ``Gen4Store.from_directories`` over ``exp.data_dir``/train + /val
+    (``split='test'``: /test) when those directories exist, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files,
+    representations per file), default (2, 24); the sensor is the downsampled 1 Mpx camera's, or the canvas where that is smaller).
+    ``num_slice`` is ``exp.Tm``; ``exp.nbins`` (default 10) and ``exp.down_sample_factor`` (default 2) are read where present.  Kept on the
+    experiment: one store per split."""
+    import os
+    cache = exp.__dict__.setdefault('_hist_stores', {})
+    if split not in cache:
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+        nbins, factor = int(getattr(exp, 'nbins', 10)), getattr(exp, 'down_sample_factor', 2)
+        root = str(getattr(exp, 'data_dir', '') or '')
+        dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
+        if root and all(os.path.isdir(d) for d in dirs):
+            cache[split] = Gen4Store.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins)
+        else:
+            n_files, n_reps = getattr(exp, 'store_recordings', (2, 24))[:2]
+            size = exp.test_size if split == 'test' else exp.input_size
+            sensor = (min(360, size[0]), min(640, size[1]))
+            recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
+            cache[split] = Gen4Store(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins)
+    return cache[split]
+
+
+class Gen4StoreDataset(Gen1StoreDataset):
+    """what the trainer and the evaluators ask of a dataset, over a ``Gen4Store`` (``Gen1StoreDataset`` as it is: the sample names carry
+    the label time)"""
+
+
+class Gen4StoreLoader(Gen1StoreLoader):
+    """Training loader of the 1 Mpx path from a ``Gen4Store``: iterable of (frames [B, 1, Tm, 2, Hc, Wc] fp32 on the GPU, targets [B, 50, 5]
+    rows (cls, cx, cy, w, h), zero padded).  The epochs, the draws and the step are ``Gen1StoreLoader``'s: an epoch is a permutation of the
+    samples; per sample ``jitter_params(..., jitter=.3)``, then ``rng.permutation(n)`` of its boxes, in get_random_data's order
+    (rvt_gen4.py:562-588); ``batches(epoch)`` is a function of (seed, epoch); a step uploads indices, params and permutations and nothing
+    else.  ``exp.aggregation`` is not consulted, as in ``SyntheticStackedHistLoader``.  ``store=None``: ``hist_store_for(exp)``."""
+
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
+        self.store = store if store is not None else hist_store_for(exp)
+        self.iters = len(self.store) // batch_size
+        assert self.iters >= 1, 'fewer labels than one batch'
+        self.dataset = Gen4StoreDataset(exp, self.store)
+        self.epoch = 0
+
+
+class Gen4StoreEvalLoader(Gen1StoreEvalLoader):
+    """Evaluation loader over a ``Gen4Store``: iterable of the tuple ``Gen1StoreEvalLoader`` yields -- ``(frames [B, 1, Tm, 2, H, W] fp32 on
+    the GPU, labels [B][n, 5] rows (x, y, w, h, cls), (heights, widths), ids)`` -- by that loader's own loop: ``letterbox_params`` of the
+    sensor on ``exp.test_size``, the raw float32 rows of ``Gen4Store.raw_labels``, the sensor's sizes.  ``exp.aggregation`` is not
+    consulted."""
+
+    def __init__(self, exp, batch_size, indices, store):
+        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+        self.dataset = Gen4StoreDataset(exp, store)
+        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
+
+
 # ------------------------------------------------------------------------------------------------ N-Caltech101 from recordings resident in HBM
 NCALTECH_BACKGROUND = 'BACKGROUND_Google'          # the class the reference leaves out (ncaltech.py:48-51, 129-134)
 

@@ -261,6 +261,50 @@ def stacked_hist_frames(store, first, Tm, Hc, Wc, nbins=10, lo=None, params=None
     return (out, flags) if return_flags else out
 
 
+def stacked_hist_bin_sums(hist, nbins=10, out=None):
+    """The builder of a summed store: ``hist`` u8 [n, 2*nbins, H, W] (channel = polarity * nbins + bin) -> ``torch.uint16`` [n, 2, H, W], the sum
+    over the time bins of each polarity (exact: at most 255 * nbins <= 65025).  ``out``: a contiguous view into a store allocated once
+    (``store[a:a + n]``) that the call fills and returns -- a recording is summed chunk by chunk as it is uploaded and its u8 form never
+    exists whole on the device.  n = 0 is no launch.  Nothing is read back."""
+    _dev(hist, out)
+    assert hist.dtype == torch.uint8 and hist.dim() == 4 and hist.shape[1] == 2 * nbins
+    hist = hist.contiguous()
+    n, _, H, W = hist.shape
+    if out is None:
+        out = torch.empty((n, 2, H, W), dtype=torch.uint16, device=hist.device)
+    assert out.dtype == torch.uint16 and out.shape == (n, 2, H, W) and out.is_contiguous() and out.device == hist.device
+    if n == 0:                               # (an empty tensor has no address to hand to the entry)
+        return out
+    _call('eas_stacked_hist_bin_sums', hist.numel() + 2 * out.numel(), _lib.lib().eas_stacked_hist_bin_sums, ptr(hist), n, int(nbins), H, W,
+          ptr(out), stream())
+    return out
+
+
+def count_store_frames(sums, first, Tm, Hc, Wc, lo=None, params=None, return_flags=False):
+    """``stacked_hist_frames`` on a summed store: ``sums`` ``torch.uint16`` [R, 2, H, W] (``stacked_hist_bin_sums`` of the representations of one
+    or more recordings back to back, resident in HBM) -> fp32 model input [B, 1, Tm, 2, Hc, Wc], bit-identical to ``stacked_hist_frames`` on
+    the unsummed store with the same ``first``, ``lo``, ``params`` (their meaning, the clamping, the zero slices and the flag bit are that
+    operator's).  Nothing is read back (graph-capturable)."""
+    _dev(sums, first, lo, params)
+    assert sums.dtype == torch.uint16 and sums.dim() == 4 and sums.shape[1] == 2
+    assert first.dtype == torch.int64 and first.dim() == 1
+    sums, first = sums.contiguous(), first.contiguous()
+    R, _, H, W = sums.shape
+    B = first.numel()
+    if lo is not None:
+        assert lo.dtype == torch.int64 and lo.shape == (B,)
+        lo = lo.contiguous()
+    if params is not None:
+        assert params.dtype == torch.int32 and params.shape == (B, 5)
+        params = params.contiguous()
+    out = torch.empty((B, 1, Tm, 2, Hc, Wc), dtype=torch.float32, device=sums.device)
+    flags = torch.empty(B, dtype=torch.int32, device=sums.device) if return_flags else None
+    # bytes: every source row at most once per (sample, slice), two bytes per pixel, + the frames (a downscale reads fewer rows)
+    _call('eas_count_store_frames', B * Tm * 2 * 2 * H * W + 4 * out.numel(), _lib.lib().eas_count_store_frames, ptr(sums), R, ptr(first), ptr(lo),
+          ptr(params), B, int(Tm), H, W, Hc, Wc, ptr(out), ptr(flags), stream())
+    return (out, flags) if return_flags else out
+
+
 def label_targets(boxes, group_start, group, params, ih, iw, h, w, perm=None, max_labels=50, return_info=False):
     """The label side of a training batch from a box table in HBM: ``targets`` fp32 [B, max_labels, 5] rows (cls, cx, cy, w, h), zero padded --
     the box half of get_random_data (gen1.py:437, 459-468, 510-521), ``reformat('cxcywh')`` and EventTrainTransform for every sample in one

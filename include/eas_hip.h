@@ -268,6 +268,20 @@ int eas_stacked_hist_event_sum(const uint8_t* hist, const int32_t* n_valid, int 
  * eas_stacked_hist_event_sum on the gathered slices. */
 int eas_stacked_hist_frames(const uint8_t* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B,
                             int Tm, int nbins, int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream);
+/* The summed form of such a store (additive, ABI 9): the model only ever sees the bin sums (generate_slices with 'event_sum',
+ * rvt_gen4.py:120-122), so a recording is kept as uint16 [R][2][H][W] -- exact (a sum is <= 255 * nbins <= 65025) and nbins / 2 times
+ * smaller.  eas_stacked_hist_bin_sums is the builder: hist u8 [n][2*nbins][H][W] (channel = polarity*nbins + bin) -> sums u16 [n][2][H][W],
+ * sums[i][p] = sum over bins of hist[i][p*nbins + bin].  The caller passes ``sums`` already advanced to the chunk's place in the store, so a
+ * recording is summed chunk by chunk as it is uploaded.  n == 0 returns EAS_OK without a launch; nbins > 255: EAS_ERR_UNSUPPORTED; NULL
+ * pointers, an odd ``sums`` address, or with W % 16 == 0 (the 16-byte path) a ``hist`` or ``sums`` that is not 16-byte aligned:
+ * EAS_ERR_INVALID_ARG (with W % 16 == 0 every representation boundary of an aligned store is aligned). */
+int eas_stacked_hist_bin_sums(const uint8_t* hist, int64_t n, int nbins, int H, int W, uint16_t* sums, eas_stream_t stream);
+/* eas_stacked_hist_frames on a summed store: sums u16 [R][2][H][W] (16-byte aligned); every other argument, the clamping of first / lo, the
+ * flag bit, the paste and resize rule, zero slices and the error returns are that entry's (the same kernel body, whose staging step copies
+ * 16-bit rows in place of nbins byte-plane loads and adds).  Bit-identical to eas_stacked_hist_frames on the store that
+ * eas_stacked_hist_bin_sums was fed from. */
+int eas_count_store_frames(const uint16_t* sums, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm,
+                           int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream);
 
 /* The LABEL side of a training batch from a box table that stays in HBM (additive, ABI 9; csrc/labels.hip): the box half of
  * GEN1Dataset.get_random_data (gen1.py:437, 459-468, 510-521; rvt_gen4.py:510-598 and ncaltech.py:272-366 are the same arithmetic), then
