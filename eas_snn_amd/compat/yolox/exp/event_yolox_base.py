@@ -179,6 +179,7 @@ class EventExp(BaseExp):
             from eas_snn_amd.data import SyntheticStackedHistLoader
             return SyntheticStackedHistLoader(self, batch_size)
         if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
+            # ``store_records`` = 'windows': the store keeps only the records its samples read (data.gen1_store_for; the evaluation store too)
             from eas_snn_amd.data import Gen1StoreLoader
             return Gen1StoreLoader(self, batch_size)
         if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)

@@ -552,39 +552,57 @@ class Gen1Store:
 
     def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304)):
         self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
+        self.device = torch.device(device)
+        areas = []
+
+        def keep(area, times):
+            areas.append(area)
+            return len(area) // 8
+        self._scan(recordings, ignore, keep)
+        self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
+        self._upload_tables()
+
+    def _scan(self, recordings, ignore, take):
+        """the label tables (``host``, ``names``, ``sample_names``, ``group_rows``, ``max_group_rows``) of the recordings, taken from the
+        iterable one at a time; ``take(record area uint8, label-group times int64)`` is called once per recording, in order, and returns
+        how many records the store keeps of it (``file_offsets`` is the prefix of those numbers).  Nothing of a recording is held on to
+        here once ``take`` has returned."""
         self.names, self.sample_names = [], []
-        areas, file_offsets, boxes, group_start, group_t, group_file = [], [0], [], [0], [], []
+        tables = dict(file_offsets=[0], boxes=[], group_start=[0], group_t=[], group_file=[])
         for name, dat, rows in recordings:
-            if name in ignore:
-                continue
-            buf = np.frombuffer(dat, dtype=np.uint8) if isinstance(dat, (bytes, bytearray, memoryview)) else np.asarray(dat, dtype=np.uint8)
-            start, _, ev_size = parse_dat_header(buf)
-            if ev_size != 8 or (len(buf) - start) % 8 != 0:
-                raise ValueError(f'{name}: not a .dat recording of 8-byte event records (event size {ev_size}, {len(buf) - start} bytes)')
-            f = len(self.names)
-            self.names.append(name)
-            areas.append(buf[start:])
-            file_offsets.append(file_offsets[-1] + (len(buf) - start) // 8)
-            t = np.asarray(rows['t' if 't' in rows.dtype.names else 'ts']).astype(np.int64)
-            if (np.diff(t) < 0).any():
-                raise ValueError(f'{name}: the label times are not ascending')
-            boxes.append(np.stack([rows['x'], rows['y'], rows['x'] + rows['w'], rows['y'] + rows['h'], rows['class_id']], axis=-1)
-                         .astype(np.float32).reshape(-1, 5))
-            first = np.flatnonzero(np.r_[True, np.diff(t) > 0]) if len(t) else np.zeros(0, dtype=np.int64)
-            for k, a in enumerate(first):
-                self.sample_names.append(f'{name}_r{k}_a{int(t[a])}')
-            group_t += [int(t[a]) for a in first]
-            group_file += [f] * len(first)
-            base = group_start[-1]                              # rows of the recordings in front
-            group_start += [base + int(e) for e in np.r_[first[1:], len(t)]] if len(first) else []
-        self.host = dict(file_offsets=np.asarray(file_offsets, dtype=np.int64),
+            if name not in ignore:
+                self._scan_one(name, dat, rows, tables, take)
+            del dat, rows                                       # released before the iterable is asked for the next recording
+        boxes = tables.pop('boxes')
+        self.host = dict(file_offsets=np.asarray(tables['file_offsets'], dtype=np.int64),
                          boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
-                         group_start=np.asarray(group_start, dtype=np.int64), group_t=np.asarray(group_t, dtype=np.int64),
-                         group_file=np.asarray(group_file, dtype=np.int32))
+                         group_start=np.asarray(tables['group_start'], dtype=np.int64), group_t=np.asarray(tables['group_t'], dtype=np.int64),
+                         group_file=np.asarray(tables['group_file'], dtype=np.int32))
         self.group_rows = np.diff(self.host['group_start'])
         self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
-        self.device = torch.device(device)
-        self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
+
+    def _scan_one(self, name, dat, rows, tables, take):
+        buf = np.frombuffer(dat, dtype=np.uint8) if isinstance(dat, (bytes, bytearray, memoryview)) else np.asarray(dat, dtype=np.uint8)
+        start, _, ev_size = parse_dat_header(buf)
+        if ev_size != 8 or (len(buf) - start) % 8 != 0:
+            raise ValueError(f'{name}: not a .dat recording of 8-byte event records (event size {ev_size}, {len(buf) - start} bytes)')
+        f = len(self.names)
+        t = np.asarray(rows['t' if 't' in rows.dtype.names else 'ts']).astype(np.int64)
+        if (np.diff(t) < 0).any():
+            raise ValueError(f'{name}: the label times are not ascending')
+        self.names.append(name)
+        first = np.flatnonzero(np.r_[True, np.diff(t) > 0]) if len(t) else np.zeros(0, dtype=np.int64)
+        tables['file_offsets'].append(tables['file_offsets'][-1] + int(take(buf[start:], t[first])))
+        tables['boxes'].append(np.stack([rows['x'], rows['y'], rows['x'] + rows['w'], rows['y'] + rows['h'], rows['class_id']], axis=-1)
+                               .astype(np.float32).reshape(-1, 5))
+        for k, a in enumerate(first):
+            self.sample_names.append(f'{name}_r{k}_a{int(t[a])}')
+        tables['group_t'] += [int(t[a]) for a in first]
+        tables['group_file'] += [f] * len(first)
+        base = tables['group_start'][-1]                        # rows of the recordings in front
+        tables['group_start'] += [base + int(e) for e in np.r_[first[1:], len(t)]] if len(first) else []
+
+    def _upload_tables(self):
         for k, v in self.host.items():
             setattr(self, k, torch.from_numpy(v).to(self.device))
 
@@ -636,13 +654,135 @@ class Gen1Store:
                                  canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
 
 
+class Gen1WindowStore(Gen1Store):
+    """A ``Gen1Store`` that keeps of every recording only the records its samples read: the ``Tl`` windows of ``|window|`` us that end at
+    a label (with the reference's 200 ms window and labels a few times per second at most, a fraction of a recording).  Tables,
+    ``sample_names``, ``raw_labels``, ``targets`` and the length are the parent's; ``frames`` is bit-identical to the parent's.
+
+    Which records a window holds depends on the whole recording (the reader's bisection probes, its resets and its steps back,
+    ``ops.event_window_search``), so the search runs on the full recording, once, at build time.  ``recordings`` is any iterable of ``(name,
+    dat_bytes, bbox_rows)`` and is consumed one recording at a time: upload, ``ops.event_window_search`` for all its label groups x ``Tl``
+    windows (the arguments ``Gen1Store.frames`` uses), ``ops.record_ranges_union``, ``ops.records_gather`` into an arena, and the upload is
+    freed -- the device holds the arena and one recording, the host whatever the iterable holds.  Results: ``records`` uint8 (the kept
+    areas back to back), ``file_offsets`` int64 [F + 1] of the kept areas (a recording without labels keeps nothing), ``sample_ranges`` int64
+    [G, Tl, 2] (record indices into ``records`` of every sample's windows; an empty window is an empty range) and the host ints
+    ``total_records``, ``kept_records``, ``capacity_bytes``, ``used_bytes``.
+
+    ``capacity_bytes``: the arena's size; None = 0.8 x the free device memory at the start, or ``source_bytes`` (what the caller knows the
+    record areas to add up to at most; measured here when ``recordings`` is a list or tuple) if that is less.  When the arena is too small
+    the remaining recordings are still scanned, nothing more is stored, and a ValueError names the bytes needed.  ``trim()`` gives back
+    what is not used."""
+
+    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, source_bytes=None):
+        self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
+        self.device = torch.device(device)
+        if capacity_bytes is None:
+            if source_bytes is None and isinstance(recordings, (list, tuple)):
+                source_bytes = sum(len(dat) for _, dat, _ in recordings)
+            capacity_bytes = self._default_capacity(source_bytes)
+        self.capacity_bytes = int(capacity_bytes) // 8 * 8
+        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+        self.total_records, self.kept_records, self._needed_records, self._ranges = 0, 0, 0, []
+        self._scan(recordings, ignore, self._compact)
+        needed, self.used_bytes = self._needed_records * 8, self.kept_records * 8
+        if needed > self.capacity_bytes:
+            del self._arena
+            raise ValueError(f'the windows of these recordings need {needed} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
+        self.records = self._arena[:self.used_bytes]
+        ranges, self._ranges = self._ranges, None
+        self.sample_ranges = torch.cat(ranges) if ranges else torch.zeros((0, self.Tl, 2), dtype=torch.int64, device=self.device)
+        self._upload_tables()
+
+    def _default_capacity(self, source_bytes):
+        free = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if self.device.type == 'cuda' else None
+        if free is None and source_bytes is None:
+            raise ValueError('capacity_bytes (or source_bytes) must be given where the free device memory cannot be asked for')
+        return min(v for v in (free, source_bytes) if v is not None)
+
+    def _window_ranges(self, area, times):
+        """(ranges int64 [G * Tl, 2] into the arena from record 0 of this recording's kept area, records kept): the device steps of one
+        recording, up to the gather.  ``area``: the record area (uint8, host), not empty; ``times``: its label-group times."""
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', UserWarning)                # a read-only host array is only read
+            rec = torch.from_numpy(area).to(self.device)
+        step = self.window[1] - self.window[0]
+        shift = torch.arange(-self.Tl + 1, 1, dtype=torch.int64, device=self.device) * step
+        t = (torch.from_numpy(times).to(self.device)[:, None] + shift[None, :]).reshape(-1)
+        ranges = ops.event_window_search(rec, t, self.window, self.Tl)
+        segments, seg_dst, mapped = ops.record_ranges_union(ranges)
+        kept = int(seg_dst[-1])
+        if self._needed_records + kept <= self.capacity_bytes // 8:
+            ops.records_gather(rec, segments, seg_dst, self._arena, self.kept_records)
+        return mapped, kept
+
+    def _compact(self, area, times):
+        self.total_records += len(area) // 8
+        if len(times) == 0:
+            return 0
+        if len(area) == 0:                                              # no events: every window is empty
+            mapped, kept = torch.zeros((len(times) * self.Tl, 2), dtype=torch.int64, device=self.device), 0
+        else:
+            mapped, kept = self._window_ranges(area, np.ascontiguousarray(times, dtype=np.int64))
+        self._needed_records += kept
+        if self._needed_records > self.capacity_bytes // 8:             # too small: go on counting, store nothing more
+            return 0
+        self._ranges.append((mapped + self.kept_records).reshape(len(times), self.Tl, 2))
+        self.kept_records += kept
+        return kept
+
+    @classmethod
+    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None):
+        """the ``<name>_td.dat`` / ``<name>_bbox.npy`` pairs of the directories ``paths`` as ``Gen1Store.from_directories`` lists them, read
+        one at a time while the store is built: the host holds one recording"""
+        import os
+        pairs = [(path, fn[:-len('_bbox.npy')]) for path in ([paths] if isinstance(paths, str) else paths) for fn in sorted(os.listdir(path))
+                 if fn.endswith('_bbox.npy') and fn[:-len('_bbox.npy')] not in ignore]
+
+        def read():
+            for path, name in pairs:
+                yield name, np.fromfile(os.path.join(path, name + '_td.dat'), dtype=np.uint8), np.load(os.path.join(path, name + '_bbox.npy'))
+        size = sum(os.path.getsize(os.path.join(path, name + '_td.dat')) for path, name in pairs)
+        return cls(read(), Tl, window, device, sensor_hw=sensor_hw, capacity_bytes=capacity_bytes, source_bytes=size)
+
+    def trim(self):
+        """reallocate ``records`` to the used size and let the arena go (the two exist side by side for the time of the copy)"""
+        if self.capacity_bytes != self.used_bytes:
+            self.records = self.records.clone()
+            self._arena, self.capacity_bytes = self.records, self.used_bytes
+        return self
+
+    def frames(self, sample_idx, params, exp, canvas_hw=None):
+        """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device), as ``Gen1Store.frames`` gives
+        it: the windows come from ``sample_ranges`` -- no search, nothing read back (graph-capturable).  The store was built for one
+        ``(Tl, window)``: an experiment that carries another raises ValueError."""
+        asked = (int(getattr(exp, 'Tl', self.Tl)), (int(exp.window * 1000), 0) if hasattr(exp, 'window') else self.window)
+        if asked != (self.Tl, self.window):
+            raise ValueError(f'the store was built for Tl = {self.Tl} and the window {self.window} us, the experiment asks for Tl = {asked[0]} '
+                             f'and {asked[1]}')
+        B, Tl = sample_idx.numel(), self.Tl
+        par = params_on(params, self.device)[:, None, :].expand(B, Tl, 5).reshape(-1, 5)
+        Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
+        out = dat_ranges_to_frames(self.records, self.sample_ranges[sample_idx].reshape(-1, 2), exp.Tm, self.sensor_hw, (Hc, Wc), par,
+                                   aggregation=exp_aggregation(exp))
+        return out.reshape(B, Tl, exp.Tm, 2, Hc, Wc)
+
+
+STORE_RECORDS = ('all', 'windows')          # ``exp.store_records``: every record of the recordings (Gen1Store) / those the samples read
+
+
 def gen1_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'dat_store'``: ``Gen1Store.from_directories`` over ``exp.data_dir``/train + /val
     (``split='test'``: /test) when that directory exists, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files, labels
-    per file, events per file), default (4, 16, 50000); the sensor is Gen1's, or the canvas where that is smaller).  Kept on the
-    experiment: one store per split."""
+    per file, events per file), default (4, 16, 50000); the sensor is Gen1's, or the canvas where that is smaller).  ``exp.store_records``
+    (default ``'all'``) = ``'windows'``: a ``Gen1WindowStore``, trimmed; any other value raises ValueError.  Kept on the experiment: one
+    store per split."""
     import os
-    cache = exp.__dict__.setdefault('_dat_stores', {})
+    kind = getattr(exp, 'store_records', 'all')
+    if kind not in STORE_RECORDS:
+        raise ValueError(f'store_records must be one of {STORE_RECORDS}, got {kind!r}')
+    cls = Gen1WindowStore if kind == 'windows' else Gen1Store
+    cache = exp.__dict__.setdefault('_dat_stores' if kind == 'all' else '_dat_window_stores', {})
     if split not in cache:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -650,13 +790,15 @@ def gen1_store_for(exp, split='train', device=None):
         root = str(getattr(exp, 'data_dir', '') or '')
         dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
         if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = Gen1Store.from_directories(dirs, exp.Tl, window, device)
+            cache[split] = cls.from_directories(dirs, exp.Tl, window, device)
         else:
             n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
             size = exp.test_size if split == 'test' else exp.input_size
             sensor = (min(240, size[0]), min(304, size[1]))
             recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
-            cache[split] = Gen1Store(recs, exp.Tl, window, device, sensor_hw=sensor)
+            cache[split] = cls(recs, exp.Tl, window, device, sensor_hw=sensor)
+        if kind == 'windows':
+            cache[split].trim()
     return cache[split]
 
 

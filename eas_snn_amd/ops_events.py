@@ -62,6 +62,57 @@ def event_window_search(records, label_t, window, num_slice, file_offsets=None, 
     return ranges
 
 
+def record_ranges_union(ranges):
+    """The union of the record ranges int64 [M, 2] (``event_window_search``; unsorted, overlapping, nested, duplicated, touching or empty
+    with a == e) and where every range lies in it: ``segments`` int64 [S, 2] sorted, disjoint, non-empty (touching ranges merge),
+    ``seg_dst`` int64 [S + 1] = the prefix of their lengths from 0, ``mapped`` int64 [M, 2] = every range's position in the segments laid back
+    to back, of the range's own length (an empty range: (0, 0)).  Build-time plumbing on torch's sort and scans; S is read back once."""
+    _dev(ranges)
+    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
+    a, e = ranges[:, 0], ranges[:, 1]
+    full = e > a
+    order = torch.argsort(torch.where(full, a, torch.iinfo(torch.int64).max))          # the empty ranges go last
+    n = int(full.sum())
+    sa, se = a[order[:n]], e[order[:n]]
+    if n == 0:
+        return ranges.new_zeros((0, 2)), ranges.new_zeros(1), torch.zeros_like(ranges)
+    reach = torch.cummax(se, 0).values                                                  # how far the ranges in front of and at i reach
+    first = torch.ones(n, dtype=torch.bool, device=ranges.device)
+    first[1:] = sa[1:] > reach[:-1]                                                     # a gap in front: a segment begins (touching: none)
+    starts = torch.nonzero(first).reshape(-1)
+    seg_a = sa[starts]
+    seg_e = reach[torch.cat([starts[1:], starts.new_tensor([n])]) - 1]
+    seg_dst = torch.cat([seg_a.new_zeros(1), torch.cumsum(seg_e - seg_a, 0)])
+    j = torch.searchsorted(seg_a, a.contiguous(), right=True).clamp_(min=1) - 1       # the segment that begins at or in front of a
+    lo = torch.where(full, seg_dst[j] + (a - seg_a[j]), torch.zeros_like(a))
+    return torch.stack([seg_a, seg_e], 1), seg_dst, torch.stack([lo, lo + (e - a).clamp(min=0)], 1)
+
+
+def records_gather(src, segments, seg_dst, dst, dst_offset=0):
+    """``dst[dst_offset + seg_dst[s] + i] = src[segments[s, 0] + i]`` for every record i of every segment s (``eas_records_gather``): the
+    segments int64 [S, 2] of ``record_ranges_union`` copied back to back into ``dst`` from record ``dst_offset`` on.  ``src``, ``dst``: uint8
+    images of 8-byte records (or any 8-byte-record view) on the device, not overlapping.  The segments are checked against both buffers on the
+    host (one read per call: build time); returns the number of records copied."""
+    _dev(src, segments, seg_dst, dst)
+    s8, d8 = src.view(torch.uint8), dst.view(torch.uint8)
+    assert src.is_contiguous() and dst.is_contiguous() and s8.numel() % 8 == 0 and d8.numel() % 8 == 0, 'records are 8 bytes'
+    assert segments.dtype == torch.int64 and segments.dim() == 2 and segments.shape[1] == 2 and seg_dst.dtype == torch.int64
+    S = segments.shape[0]
+    assert seg_dst.shape == (S + 1,) and int(dst_offset) >= 0
+    if S == 0:
+        return 0
+    length = segments[:, 1] - segments[:, 0]
+    ok = (length >= 0).all() & (length == seg_dst[1:] - seg_dst[:-1]).all() & (segments[:, 0] >= 0).all() & (segments[:, 1] <= s8.numel() // 8).all()
+    ok, first, last = torch.stack([ok.to(torch.int64), seg_dst[0], seg_dst[-1]]).tolist()
+    if not ok or first < 0 or int(dst_offset) + last > d8.numel() // 8:
+        raise ValueError(f'records_gather: the segments do not fit (source {s8.numel() // 8} records, destination {d8.numel() // 8} records, '
+                         f'offset {int(dst_offset)}, span {first}..{last})')
+    seg_src, seg_pos = segments[:, 0].contiguous(), seg_dst + int(dst_offset)       # two tables of their own, alive until the call is enqueued
+    _call('eas_records_gather', 16 * (last - first), _lib.lib().eas_records_gather, ptr(s8), ptr(seg_src), ptr(seg_pos), S, last - first,
+          ptr(d8), stream())
+    return last - first
+
+
 def _dat_ranges_frames(timer, entry, dtype, out_bytes, records, ranges, ns, H, W, tau, return_oob):
     """the two .dat-range wrappers: checks, allocations, the call (``tau``: a tuple, empty for the counts) and the return tuple"""
     _dev(records, ranges)

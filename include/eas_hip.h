@@ -241,6 +241,15 @@ int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, i
  * overwrites them in place: no workspace, no host read of the ranges.  tau <= 0 or NaN: EAS_ERR_INVALID_ARG. */
 int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* ranges, int B, int num_slices, int H, int W, double tau,
                                         double* out, uint32_t* oob_count, eas_stream_t stream);
+/* S segments of 8-byte records copied from one buffer into another (additive, ABI 9; the build step of a store that keeps only the
+ * records its samples read, data.Gen1WindowStore):
+ *     dst[seg_dst[s] + i] = src[seg_src[s] + i]      for 0 <= i < seg_dst[s + 1] - seg_dst[s],  0 <= s < S
+ * seg_src int64 [S] and seg_dst int64 [S + 1] live on the device and are not read on the host; seg_dst ascends (the prefix of the segment
+ * lengths plus the position in dst; a segment may be empty); total = seg_dst[S] - seg_dst[0] comes from the host and only sizes the grid.
+ * The order of the records is kept, nothing outside dst[seg_dst[0] .. seg_dst[S]) is written, src and dst do not overlap and the caller
+ * answers for the segments lying inside src and dst.  Asynchronous on `stream`, no allocation.  A NULL pointer, a pointer that is not
+ * 8-byte aligned, S < 1 or total < 0: EAS_ERR_INVALID_ARG before any HIP call; total == 0: EAS_OK, no launch.  A copy: bit-exact. */
+int eas_records_gather(const void* src, const int64_t* seg_src, const int64_t* seg_dst, int64_t S, int64_t total, void* dst, eas_stream_t stream);
 
 /* Config-4 input (BASELINE configs[3]): RVT stacked histogram -> per-polarity counts on the model canvas.  Replaces
  * RVTGEN4Dataset.generate_slices(..., method='event_sum') (yolox/data/datasets/rvt_gen4.py:109-125: reshape
