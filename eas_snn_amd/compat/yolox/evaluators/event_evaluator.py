@@ -158,7 +158,10 @@ class EventEvaluator:
         ``times`` = [inference, NMS] seconds"""
         n_batches = len(self.dataloader)
         for cur_iter, (imgs, labels, info_imgs, ids) in enumerate(self.dataloader):
-            with torch.no_grad():                       # (the reference: inference_mode; graph replays write ordinary static buffers)
+            if len(ids) == 0:                           # an empty batch (the padding of a sharded evaluation): nothing to infer, but the
+                yield [], labels, info_imgs, ids        # caller's per-batch work -- a gather with the other ranks -- still takes place
+                continue
+            with torch.no_grad():                      # (the reference: inference_mode; graph replays write ordinary static buffers)
                 imgs = imgs.to(dev, torch.float32)
                 # the last batch may be short: not timed, as in the reference (:191-193)
                 timed = cur_iter < n_batches - 1
@@ -191,7 +194,7 @@ class EventEvaluator:
         times = [0.0, 0.0]
         n_samples = max(len(self.dataloader) - 1, 1)
         for outputs, labels, info_imgs, ids in self._run_batches(model, decoder, dev, graph_ok, times):
-            if feed is not None:
+            if feed is not None and len(ids):                         # (an empty batch, the padding of a sharded evaluation, has no rows)
                 self._feed_device_rows(feed, outputs, info_imgs, ids, dev)
             elems, image_wise = self.convert_to_coco_format(outputs, info_imgs, ids, return_outputs=True)
             data_list.extend(elems)

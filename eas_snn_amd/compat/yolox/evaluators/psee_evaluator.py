@@ -54,7 +54,7 @@ class PSEEEvaluator(EventEvaluator):
         for outputs, labels, info_imgs, ids in self._run_batches(model, decoder, dev, graph_ok, times):
             sample_names = [names_of[int(i)] for i in ids]
             labels = [torch.as_tensor(label) for label in labels]
-            if feed is not None:
+            if feed is not None and sample_names:                     # (an empty batch, the padding of a sharded evaluation, has no rows)
                 self._feed_device_rows(feed, outputs, labels, info_imgs, sample_names, dev)
             batch_preds = self.convert_to_prophesee_format(self.convert_to_gt_format(outputs, info_imgs), sample_names)
             batch_labels = self.convert_to_prophesee_format([torch.cat([label, torch.ones_like(label[:, 0:1])], dim=1) for label in labels],

@@ -171,23 +171,34 @@ class EventExp(BaseExp):
         return SyntheticEventDataset(self)
 
     def get_data_loader(self, batch_size, is_distributed, no_aug=False, cache_img=None):
-        from eas_snn_amd.data import SyntheticEventLoader
-        from yolox.utils import get_world_size      # (answers from the launcher's parameters while the process group is still deferred)
+        """``batch_size`` is the global batch.  On N ranks (``is_distributed``) a store loader (``train_input`` = 'dat_store', 'atis_store',
+        'hist_store') gets the per-rank batch, the rank and the world size: with ``store_shard = 'none'`` (the default) every rank holds
+        every recording and keeps rows ``rank::world`` of the single-process batches, so an epoch has ``len(store) // batch_size`` steps;
+        with ``store_shard = 'recordings'`` a rank holds and draws from its own recordings (``data.*_store_for``, ``data.Gen1StoreLoader``).
+        The synthetic loaders are the same on every rank."""
+        from eas_snn_amd.data import SyntheticEventLoader, exp_store_shard
+        from yolox.utils import get_rank, get_world_size      # (answer from the launcher's parameters while the process group is still deferred)
+        ranks = {}
+        exp_store_shard(self)                                   # (an unknown ``store_shard`` raises here, whatever the input)
         if is_distributed:
-            batch_size = batch_size // get_world_size()
+            rank, world = get_rank(), get_world_size()
+            if batch_size % world != 0:
+                raise ValueError(f'the global batch of {batch_size} is not a multiple of the world size {world}')
+            batch_size = batch_size // world
+            ranks = dict(rank=rank, world=world)
         if getattr(self, 'train_input', None) == 'stacked_hist':       # opt-in: the 1 Mpx path (indices into a resident store -> augmented frames)
             from eas_snn_amd.data import SyntheticStackedHistLoader
             return SyntheticStackedHistLoader(self, batch_size)
         if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
             # ``store_records`` = 'windows': the store keeps only the records its samples read (data.gen1_store_for; the evaluation store too)
             from eas_snn_amd.data import Gen1StoreLoader
-            return Gen1StoreLoader(self, batch_size)
+            return Gen1StoreLoader(self, batch_size, **ranks)
         if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)
             from eas_snn_amd.data import NCaltechStoreLoader
-            return NCaltechStoreLoader(self, batch_size)
+            return NCaltechStoreLoader(self, batch_size, **ranks)
         if getattr(self, 'train_input', None) == 'hist_store':         # opt-in: 1 Mpx from recordings in HBM (sample indices -> frames and targets)
             from eas_snn_amd.data import Gen4StoreLoader
-            return Gen4StoreLoader(self, batch_size)
+            return Gen4StoreLoader(self, batch_size, **ranks)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):
@@ -205,7 +216,8 @@ class EventExp(BaseExp):
 
     def get_eval_loader(self, batch_size, is_distributed, **kwargs):
         """reference: event_yolox_base.py:483-507 -- twice the training batch, split over the ranks, samples rank, rank + world, ...
-        in order (DistributedSampler(shuffle=False)); the streams are synthetic and binned on the GPU"""
+        in order (DistributedSampler(shuffle=False)); the streams are synthetic and binned on the GPU.  Over a sharded store
+        (``store_shard = 'recordings'``) a rank evaluates the samples it owns instead (below)."""
         from eas_snn_amd.data import SyntheticEvalLoader
         from yolox.utils import get_rank, get_world_size
         valdataset = self.get_eval_dataset(**kwargs)
@@ -217,15 +229,20 @@ class EventExp(BaseExp):
         n = len(valdataset)
         per_rank = (n + world - 1) // world                 # DistributedSampler pads with the first samples so every rank gets the same count
         idx = [(rank + k * world) % n for k in range(per_rank)]
+        store = getattr(valdataset, 'store', None)
+        if store is not None and store.sharded:
+            # a sharded store: the rank's own samples in ascending order -- no padding, no repeats, every sample once across the ranks
+            # under its global id; the ranks run different numbers of batches (``pad_eval_batches`` where an evaluator minds)
+            idx = store.owned_samples.tolist()
         if getattr(self, 'train_input', None) == 'dat_store':
             from eas_snn_amd.data import Gen1StoreEvalLoader
-            return Gen1StoreEvalLoader(self, batch_size, idx, valdataset.store)
+            return Gen1StoreEvalLoader(self, batch_size, idx, store)
         if getattr(self, 'train_input', None) == 'atis_store':
             from eas_snn_amd.data import NCaltechStoreEvalLoader
-            return NCaltechStoreEvalLoader(self, batch_size, idx, valdataset.store)
+            return NCaltechStoreEvalLoader(self, batch_size, idx, store)
         if getattr(self, 'train_input', None) == 'hist_store':
             from eas_snn_amd.data import Gen4StoreEvalLoader
-            return Gen4StoreEvalLoader(self, batch_size, idx, valdataset.store)
+            return Gen4StoreEvalLoader(self, batch_size, idx, store)
         # synthetic streams on the Gen1 sensor (or on the canvas itself when that is smaller); ``eval_sensor_hw`` / ``eval_events`` override
         sensor = getattr(self, 'eval_sensor_hw', None) or (min(240, self.test_size[0]), min(304, self.test_size[1]))
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)
@@ -250,6 +267,10 @@ class EventExp(BaseExp):
                     return False
             names = getattr(getattr(loader, 'dataset', None), 'sample_names', None)
             if camera in ('gen1', 'gen4') and names is not None and all(timed(n) for n in names):
+                # PSEEEvaluator gathers to rank 0 once per batch (psee_evaluator.py, _evaluate_loop); EventEvaluator's only collectives
+                # come after its loop.  The ranks of a sharded evaluation own different numbers of samples: every loader is made as long
+                # as the longest, with empty batches -- not with repeated samples -- so that the per-batch gathers stay in step.
+                pad_eval_batches(loader)
                 return PSEEEvaluator(dataloader=loader, img_size=self.test_size, confthre=self.test_conf, nmsthre=self.nmsthre,
                                      num_classes=self.num_classes, testdev=testdev, snn_reset=self.use_spike, dataset=camera,
                                      downsample_by_2=(camera == 'gen4'))
@@ -269,6 +290,16 @@ class EventExp(BaseExp):
 
     def eval(self, model, evaluator, is_distributed, half=False, return_outputs=False):
         return evaluator.evaluate(model, is_distributed, half, return_outputs=return_outputs)
+
+
+def pad_eval_batches(loader):
+    """make the evaluation loader of a sharded store as long as the longest rank's (``min_batches``), computed from the assignment that
+    every rank holds: no collective.  Other loaders are left as they are."""
+    import numpy as np
+    store = getattr(loader, 'store', None)
+    if store is not None and getattr(store, 'sharded', False) and store.sample_rank is not None:
+        most = int(np.bincount(store.sample_rank, minlength=store.shard[1]).max())
+        loader.min_batches = (most + loader.batch_size - 1) // loader.batch_size
 
 
 def check_exp_value(exp):

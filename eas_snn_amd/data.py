@@ -469,6 +469,124 @@ def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggr
     return _letterboxed(frames, params, canvas_hw).unsqueeze(1)
 
 
+# ------------------------------------------------------------------------------------------------ stores on N ranks
+STORE_SHARD = ('none', 'recordings')        # ``exp.store_shard``: every rank holds every record / a rank holds the records of its own recordings
+
+
+def shard_recordings(names, weights, world):
+    """{name: rank}: the recordings ``names`` (weights ``weights``, anything that orders and adds) dealt out to ``world`` ranks.  Greedy:
+    in descending weight (ties: the order given), each to the rank with the least load so far (ties: the lower rank) -- a function of the
+    arguments alone, so every rank computes the same assignment without a collective.  When the recording that sets the largest load was
+    placed its rank was the least loaded, so ``max load - min load <= largest weight`` and ``max load <= sum / world + largest weight``."""
+    names, world = list(names), int(world)
+    weights = [int(w) for w in weights]
+    if world < 1 or len(weights) != len(names) or len(set(names)) != len(names):
+        raise ValueError(f'shard_recordings: {len(names)} names ({len(set(names))} distinct), {len(weights)} weights, world {world}')
+    load, out = [0] * world, {}
+    for i in sorted(range(len(names)), key=lambda i: -weights[i]):           # (a stable sort: ties stay in the order given)
+        r = min(range(world), key=lambda r: load[r])                         # (the first of the least loaded: the lower rank)
+        out[names[i]] = r
+        load[r] += weights[i]
+    return out
+
+
+def _shard_plan(names, weights, shard, owned):
+    """(owned names or None = all, {name: rank} or None) of a store built with ``shard=(rank, world)`` and / or ``owned=``"""
+    if shard is None:
+        return (None if owned is None else set(owned)), None
+    rank, world = int(shard[0]), int(shard[1])
+    if not 0 <= rank < world:
+        raise ValueError(f'shard = {shard!r}: the rank must lie in [0, world)')
+    if owned is not None:
+        raise ValueError('give shard= or owned=, not both')
+    ranks = shard_recordings(names, weights, world)
+    return {n for n, r in ranks.items() if r == rank}, ranks
+
+
+def _memory_plan(recordings, name, heavy, shard, owned):
+    """``_shard_plan`` of recordings in memory: the names are ``name(r)``, the weights ``len(heavy(r))`` (looked at with ``shard=`` only)"""
+    if shard is None:
+        return _shard_plan((), (), None, owned)
+    return _shard_plan([name(r) for r in recordings], [len(heavy(r)) for r in recordings], shard, owned)
+
+
+def rank_and_world():
+    """(rank, world size) as ``yolox.utils`` answers them (from the launcher's parameters while the process group is still deferred)"""
+    from yolox import utils
+    return int(utils.get_rank()), int(utils.get_world_size())
+
+
+def exp_store_shard(exp):
+    """``(rank, world)`` for the stores of an experiment with ``store_shard = 'recordings'``, None with ``'none'`` (the default); anything
+    else raises ValueError"""
+    kind = getattr(exp, 'store_shard', 'none')
+    if kind not in STORE_SHARD:
+        raise ValueError(f'store_shard must be one of {STORE_SHARD}, got {kind!r}')
+    return rank_and_world() if kind == 'recordings' else None
+
+
+def _store_key(exp, split):
+    """the key under which ``*_store_for`` keep a store on the experiment: (split, rank, world, store_shard)"""
+    return (split,) + rank_and_world() + (getattr(exp, 'store_shard', 'none'),)
+
+
+class _Sharded:
+    """What a store knows about the ranks.  ``owned_samples`` int64: the ascending global indices of the samples whose records are
+    present (all of them unless the store was built with ``owned=`` / ``shard=``); ``owns(indices)``: numpy bool, on the host;
+    ``shard``: the ``(rank, world)`` it was built for or None; ``sample_rank`` int32 [G]: the rank that holds every sample's records
+    (None unless built with ``shard=``: with ``owned=`` alone the store knows its own recordings only)."""
+    shard, sample_rank = None, None
+
+    def _set_owner(self, sample_owned, shard=None, sample_rank=None):
+        self._sample_owned = np.asarray(sample_owned, dtype=bool).reshape(-1)
+        self.owned_samples = np.flatnonzero(self._sample_owned).astype(np.int64)
+        self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
+        self.sample_rank = None if sample_rank is None else np.asarray(sample_rank, dtype=np.int32).reshape(-1)
+
+    def _adopt(self, shard, ranks, names, sample_file):
+        """a store built with ``owned=`` from an assignment made outside (from the sizes of files): take ``shard`` = (rank, world) and the
+        assignment ``ranks`` = {name: rank} over; ``names``: the recordings in order, ``sample_file``: the recording of every sample"""
+        if shard is not None:
+            by_file = np.array([ranks[n] for n in names], dtype=np.int32)
+            self._set_owner(self._sample_owned, shard, by_file[np.asarray(sample_file, dtype=np.int64)])
+
+    @property
+    def sharded(self):
+        """whether the loaders treat the store as one rank's part of a dataset (a shard of a world of 1 is the whole store)"""
+        return (self.shard is not None and self.shard[1] > 1) or len(self.owned_samples) != len(self._sample_owned)
+
+    def owns(self, indices):
+        idx = np.asarray(indices, dtype=np.int64)
+        ok = (idx >= 0) & (idx < len(self._sample_owned))
+        ok[ok] = self._sample_owned[idx[ok]]
+        return ok
+
+    def check_owned(self, indices):
+        """IndexError for a sample whose records this store does not hold (host; what every loader calls before it uploads indices)"""
+        ok = self.owns(indices)
+        if not ok.all():
+            bad = np.asarray(indices, dtype=np.int64).reshape(-1)[~ok.reshape(-1)]
+            raise IndexError(f'samples {bad[:8].tolist()} are not held by this store (shard {self.shard}, {len(self.owned_samples)} of '
+                             f'{len(self._sample_owned)} samples owned)')
+
+
+def _sharded_iters(store, batch_size, rank):
+    """steps per epoch of a training loader over a sharded store: the smallest owned count of any rank // the per-rank batch, computed from
+    the assignment every rank holds (no collective; all ranks run the same number of steps).  A rank with fewer samples than one batch
+    raises ValueError.  A store built with ``owned=`` alone knows only its own count."""
+    counts = np.bincount(store.sample_rank, minlength=store.shard[1]) if store.sample_rank is not None else {rank: len(store.owned_samples)}
+    for r, n in (counts.items() if isinstance(counts, dict) else enumerate(counts)):
+        if n < batch_size:
+            raise ValueError(f'rank {r} owns {int(n)} samples, fewer than one batch of {batch_size} (store_shard = recordings)')
+    return int(min(counts.values() if isinstance(counts, dict) else counts)) // batch_size
+
+
+def _shard_state(seed, epoch, rank):
+    """the random state of a rank's epoch over a sharded store: MT19937 seeded by the array (seed mod 2^32, epoch, rank) --
+    ``init_by_array``, so two different triples never collapse into one integer seed"""
+    return np.random.RandomState([int(seed) % (1 << 32), int(epoch), int(rank)])
+
+
 # ------------------------------------------------------------------------------------------------ Gen1 from recordings resident in HBM
 def parse_dat_header(buf):
     """(offset of the first event record, event type, event size) of a Prophesee ``.dat`` file image (bytes or a uint8 array), as the
@@ -533,7 +651,7 @@ def synth_gen1_recordings(n_files, labels_per_file, n_events=50_000, sensor_hw=(
     return out
 
 
-class Gen1Store:
+class Gen1Store(_Sharded):
     """Gen1 recordings and their labels resident on the device: what GEN1Dataset keeps on disk and in host lists (gen1.py:43-85), as tables
     that the kernels index.  ``recordings``: a list of ``(name, dat_bytes, bbox_rows)`` -- the byte image of ``<name>_td.dat`` and the
     structured array of ``<name>_bbox.npy`` (fields ``t`` or ``ts``, ``x``, ``y``, ``w``, ``h``, ``class_id``); names in ``ignore`` are left
@@ -548,9 +666,14 @@ class Gen1Store:
     sample index is the group index: recordings in the order given, groups in time order (resolve_index, gen1.py:263-267, with
     ``continuous=True`` as EventExp builds the dataset: no leading groups are dropped).
 
-    A store holds the recordings it is given; cutting a dataset that exceeds HBM into shards is the caller's business."""
+    On N ranks a store holds the labels of every recording and the records of its own: ``owned`` (a collection of recording names, None
+    = all) or ``shard=(rank, world)`` (``shard_recordings`` by ``len(dat_bytes)``; ``recordings`` must be a list then).  A recording that
+    is not owned contributes its rows to ``boxes``, ``group_start``, ``group_t``, ``group_file`` and ``sample_names`` -- these, the flat
+    sample index, ``raw_labels``, ``targets`` and the length are the same on every rank and the same as the unsharded store's -- and a
+    zero-length area to ``records`` / ``file_offsets``; its ``dat_bytes`` may be None and is never touched.  ``owned_samples``, ``owns``,
+    ``shard``, ``sample_rank``: see ``_Sharded``."""
 
-    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304)):
+    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), owned=None, shard=None):
         self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
         self.device = torch.device(device)
         areas = []
@@ -558,21 +681,27 @@ class Gen1Store:
         def keep(area, times):
             areas.append(area)
             return len(area) // 8
-        self._scan(recordings, ignore, keep)
+        self._scan(recordings, ignore, keep, owned, shard)
         self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
         self._upload_tables()
 
-    def _scan(self, recordings, ignore, take):
+    def _scan(self, recordings, ignore, take, owned=None, shard=None):
         """the label tables (``host``, ``names``, ``sample_names``, ``group_rows``, ``max_group_rows``) of the recordings, taken from the
-        iterable one at a time; ``take(record area uint8, label-group times int64)`` is called once per recording, in order, and returns
-        how many records the store keeps of it (``file_offsets`` is the prefix of those numbers).  Nothing of a recording is held on to
-        here once ``take`` has returned."""
+        iterable one at a time; ``take(record area uint8, label-group times int64)`` is called once per owned recording, in order, and
+        returns how many records the store keeps of it (``file_offsets`` is the prefix of those numbers; a recording that is not owned
+        adds 0).  Nothing of a recording is held on to here once ``take`` has returned."""
         self.names, self.sample_names = [], []
         tables = dict(file_offsets=[0], boxes=[], group_start=[0], group_t=[], group_file=[])
+        if shard is not None:
+            recordings = [r for r in recordings if r[0] not in ignore]
+        owned, ranks = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)
         for name, dat, rows in recordings:
             if name not in ignore:
-                self._scan_one(name, dat, rows, tables, take)
+                self._scan_one(name, dat, rows, tables, take if owned is None or name in owned else None)
             del dat, rows                                       # released before the iterable is asked for the next recording
+        file_owned = np.array([owned is None or n in owned for n in self.names], dtype=bool)
+        group_file = np.asarray(tables['group_file'], dtype=np.int64)
+        self._set_owner(file_owned[group_file], shard, None if ranks is None else np.array([ranks[n] for n in self.names], dtype=np.int32)[group_file])
         boxes = tables.pop('boxes')
         self.host = dict(file_offsets=np.asarray(tables['file_offsets'], dtype=np.int64),
                          boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
@@ -582,17 +711,19 @@ class Gen1Store:
         self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
 
     def _scan_one(self, name, dat, rows, tables, take):
-        buf = np.frombuffer(dat, dtype=np.uint8) if isinstance(dat, (bytes, bytearray, memoryview)) else np.asarray(dat, dtype=np.uint8)
-        start, _, ev_size = parse_dat_header(buf)
-        if ev_size != 8 or (len(buf) - start) % 8 != 0:
-            raise ValueError(f'{name}: not a .dat recording of 8-byte event records (event size {ev_size}, {len(buf) - start} bytes)')
+        """``take=None``: a recording that is not owned -- its labels only; ``dat`` is not looked at"""
+        if take is not None:
+            buf = np.frombuffer(dat, dtype=np.uint8) if isinstance(dat, (bytes, bytearray, memoryview)) else np.asarray(dat, dtype=np.uint8)
+            start, _, ev_size = parse_dat_header(buf)
+            if ev_size != 8 or (len(buf) - start) % 8 != 0:
+                raise ValueError(f'{name}: not a .dat recording of 8-byte event records (event size {ev_size}, {len(buf) - start} bytes)')
         f = len(self.names)
         t = np.asarray(rows['t' if 't' in rows.dtype.names else 'ts']).astype(np.int64)
         if (np.diff(t) < 0).any():
             raise ValueError(f'{name}: the label times are not ascending')
         self.names.append(name)
         first = np.flatnonzero(np.r_[True, np.diff(t) > 0]) if len(t) else np.zeros(0, dtype=np.int64)
-        tables['file_offsets'].append(tables['file_offsets'][-1] + int(take(buf[start:], t[first])))
+        tables['file_offsets'].append(tables['file_offsets'][-1] + (int(take(buf[start:], t[first])) if take is not None else 0))
         tables['boxes'].append(np.stack([rows['x'], rows['y'], rows['x'] + rows['w'], rows['y'] + rows['h'], rows['class_id']], axis=-1)
                                .astype(np.float32).reshape(-1, 5))
         for k, a in enumerate(first):
@@ -607,18 +738,30 @@ class Gen1Store:
             setattr(self, k, torch.from_numpy(v).to(self.device))
 
     @classmethod
-    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304)):
+    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), shard=None, read_dat=None):
         """the ``<name>_td.dat`` / ``<name>_bbox.npy`` pairs of the directories ``paths``, every directory in sorted order (the reference
-        takes them as ``os.listdir`` gives them), read with ``numpy.fromfile`` / ``numpy.load``"""
+        takes them as ``os.listdir`` gives them), read with ``numpy.fromfile`` / ``numpy.load``.  ``shard=(rank, world)``: every recording is
+        listed and weighed by the size of its ``_td.dat`` (``os.path.getsize``: nothing of a recording is read for the assignment), every
+        ``_bbox.npy`` is read, and of the ``_td.dat`` files only those ``shard_recordings`` gives to ``rank``.  ``read_dat(path)``: the reader
+        of a ``_td.dat`` (default ``numpy.fromfile(path, dtype=numpy.uint8)``)."""
+        pairs, owned, ranks = cls._listed(paths, ignore, shard)
+        read_dat = read_dat if read_dat is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
+        recs = [(name, read_dat(dat) if owned is None or name in owned else None, np.load(box)) for name, dat, box in pairs]
+        store = cls(recs, Tl, window, device, sensor_hw=sensor_hw, owned=owned)
+        store._adopt(shard, ranks, store.names, store.host['group_file'])
+        return store
+
+    @staticmethod
+    def _listed(paths, ignore, shard):
+        """([(name, path of _td.dat, path of _bbox.npy)] in the order of ``from_directories``, owned names or None, {name: rank} or None)"""
         import os
-        recs = []
-        for path in ([paths] if isinstance(paths, str) else paths):
-            for fn in sorted(os.listdir(path)):
-                if fn.endswith('_bbox.npy'):
-                    name = fn[:-len('_bbox.npy')]
-                    if name not in ignore:
-                        recs.append((name, np.fromfile(os.path.join(path, name + '_td.dat'), dtype=np.uint8), np.load(os.path.join(path, fn))))
-        return cls(recs, Tl, window, device, sensor_hw=sensor_hw)
+        pairs = [(fn[:-len('_bbox.npy')], os.path.join(path, fn[:-len('_bbox.npy')] + '_td.dat'), os.path.join(path, fn))
+                 for path in ([paths] if isinstance(paths, str) else paths) for fn in sorted(os.listdir(path))
+                 if fn.endswith('_bbox.npy') and fn[:-len('_bbox.npy')] not in ignore]
+        owned, ranks = _shard_plan([p[0] for p in pairs], [os.path.getsize(p[1]) for p in pairs] if shard is not None else (), shard, None)
+        return pairs, owned, ranks
+
+
 
     def __len__(self):
         return len(self.sample_names)
@@ -635,7 +778,9 @@ class Gen1Store:
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): label time and recording gathered
         on the device, ``ops.event_window_search`` for the ``Tl`` windows that end at the label (generate_slices with ``continuous``,
         gen1.py:117-125), then ``dat_ranges_to_frames`` with the experiment's ``aggregation``; ``params``: (nw, nh, dx, dy, flip) per
-        sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back (graph-capturable)."""
+        sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back (graph-capturable).  Precondition: the store
+        holds the records of every sample asked for (``owns``; the loaders check their indices on the host before they upload them) -- a
+        sample that is not owned has no records here and comes out as empty frames, silently."""
         B, Tl = sample_idx.numel(), self.Tl
         step = self.window[1] - self.window[0]
         shift = torch.arange(-Tl + 1, 1, dtype=torch.int64, device=self.device) * step
@@ -671,26 +816,41 @@ class Gen1WindowStore(Gen1Store):
     ``capacity_bytes``: the arena's size; None = 0.8 x the free device memory at the start, or ``source_bytes`` (what the caller knows the
     record areas to add up to at most; measured here when ``recordings`` is a list or tuple) if that is less.  When the arena is too small
     the remaining recordings are still scanned, nothing more is stored, and a ValueError names the bytes needed.  ``trim()`` gives back
-    what is not used."""
+    what is not used.
 
-    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, source_bytes=None):
+    ``owned`` / ``shard`` as in ``Gen1Store``: a recording that is not owned is neither uploaded nor searched, keeps nothing, and its
+    samples carry empty ranges in ``sample_ranges`` (which stays [G, Tl, 2] over the global sample index); ``total_records`` and
+    ``kept_records`` count the owned recordings, so the ranks' ``kept_records`` add up to the unsharded store's.  ``shard=`` weighs a
+    recording by ``len(dat_bytes)``, which is only a proxy for what its windows keep: the balance bound of ``shard_recordings`` holds
+    for the bytes read at build time, not for the bytes held."""
+
+    def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, source_bytes=None, owned=None,
+                 shard=None):
         self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
         self.device = torch.device(device)
+        if shard is not None:
+            recordings = [r for r in recordings if r[0] not in ignore]
         if capacity_bytes is None:
             if source_bytes is None and isinstance(recordings, (list, tuple)):
-                source_bytes = sum(len(dat) for _, dat, _ in recordings)
+                mine = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)[0]
+                source_bytes = sum(len(dat) for name, dat, _ in recordings if mine is None or name in mine)
             capacity_bytes = self._default_capacity(source_bytes)
         self.capacity_bytes = int(capacity_bytes) // 8 * 8
         self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
         self.total_records, self.kept_records, self._needed_records, self._ranges = 0, 0, 0, []
-        self._scan(recordings, ignore, self._compact)
+        self._scan(recordings, ignore, self._compact, owned, shard)
         needed, self.used_bytes = self._needed_records * 8, self.kept_records * 8
         if needed > self.capacity_bytes:
             del self._arena
             raise ValueError(f'the windows of these recordings need {needed} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
         self.records = self._arena[:self.used_bytes]
         ranges, self._ranges = self._ranges, None
-        self.sample_ranges = torch.cat(ranges) if ranges else torch.zeros((0, self.Tl, 2), dtype=torch.int64, device=self.device)
+        if self.sharded:                                                # the rows of the owned samples, in their order; the others stay empty
+            self.sample_ranges = torch.zeros((len(self.sample_names), self.Tl, 2), dtype=torch.int64, device=self.device)
+            if ranges:
+                self.sample_ranges[torch.from_numpy(self.owned_samples).to(self.device)] = torch.cat(ranges)
+        else:
+            self.sample_ranges = torch.cat(ranges) if ranges else torch.zeros((0, self.Tl, 2), dtype=torch.int64, device=self.device)
         self._upload_tables()
 
     def _default_capacity(self, source_bytes):
@@ -732,18 +892,21 @@ class Gen1WindowStore(Gen1Store):
         return kept
 
     @classmethod
-    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None):
+    def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, shard=None, read_dat=None):
         """the ``<name>_td.dat`` / ``<name>_bbox.npy`` pairs of the directories ``paths`` as ``Gen1Store.from_directories`` lists them, read
-        one at a time while the store is built: the host holds one recording"""
+        one at a time while the store is built: the host holds one recording.  ``shard`` and ``read_dat`` as there: only the owned
+        ``_td.dat`` files are read (their size is the weight -- a proxy for what the windows keep, see the class)."""
         import os
-        pairs = [(path, fn[:-len('_bbox.npy')]) for path in ([paths] if isinstance(paths, str) else paths) for fn in sorted(os.listdir(path))
-                 if fn.endswith('_bbox.npy') and fn[:-len('_bbox.npy')] not in ignore]
+        pairs, owned, ranks = cls._listed(paths, ignore, shard)
+        read_dat = read_dat if read_dat is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
 
         def read():
-            for path, name in pairs:
-                yield name, np.fromfile(os.path.join(path, name + '_td.dat'), dtype=np.uint8), np.load(os.path.join(path, name + '_bbox.npy'))
-        size = sum(os.path.getsize(os.path.join(path, name + '_td.dat')) for path, name in pairs)
-        return cls(read(), Tl, window, device, sensor_hw=sensor_hw, capacity_bytes=capacity_bytes, source_bytes=size)
+            for name, dat, box in pairs:
+                yield name, read_dat(dat) if owned is None or name in owned else None, np.load(box)
+        size = sum(os.path.getsize(dat) for name, dat, _ in pairs if owned is None or name in owned)
+        store = cls(read(), Tl, window, device, sensor_hw=sensor_hw, capacity_bytes=capacity_bytes, source_bytes=size, owned=owned)
+        store._adopt(shard, ranks, store.names, store.host['group_file'])
+        return store
 
     def trim(self):
         """reallocate ``records`` to the used size and let the arena go (the two exist side by side for the time of the copy)"""
@@ -755,7 +918,7 @@ class Gen1WindowStore(Gen1Store):
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device), as ``Gen1Store.frames`` gives
         it: the windows come from ``sample_ranges`` -- no search, nothing read back (graph-capturable).  The store was built for one
-        ``(Tl, window)``: an experiment that carries another raises ValueError."""
+        ``(Tl, window)``: an experiment that carries another raises ValueError.  The precondition on ``sample_idx`` is the parent's."""
         asked = (int(getattr(exp, 'Tl', self.Tl)), (int(exp.window * 1000), 0) if hasattr(exp, 'window') else self.window)
         if asked != (self.Tl, self.window):
             raise ValueError(f'the store was built for Tl = {self.Tl} and the window {self.window} us, the experiment asks for Tl = {asked[0]} '
@@ -775,28 +938,31 @@ def gen1_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'dat_store'``: ``Gen1Store.from_directories`` over ``exp.data_dir``/train + /val
     (``split='test'``: /test) when that directory exists, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files, labels
     per file, events per file), default (4, 16, 50000); the sensor is Gen1's, or the canvas where that is smaller).  ``exp.store_records``
-    (default ``'all'``) = ``'windows'``: a ``Gen1WindowStore``, trimmed; any other value raises ValueError.  Kept on the experiment: one
-    store per split."""
+    (default ``'all'``) = ``'windows'``: a ``Gen1WindowStore``, trimmed; any other value raises ValueError.  ``exp.store_shard`` =
+    ``'recordings'``: the store of this rank (``shard=`` of ``from_directories`` / of the constructor for the synthetic recordings).  Kept
+    on the experiment: one store per (split, rank, world, store_shard)."""
     import os
     kind = getattr(exp, 'store_records', 'all')
     if kind not in STORE_RECORDS:
         raise ValueError(f'store_records must be one of {STORE_RECORDS}, got {kind!r}')
     cls = Gen1WindowStore if kind == 'windows' else Gen1Store
     cache = exp.__dict__.setdefault('_dat_stores' if kind == 'all' else '_dat_window_stores', {})
+    shard = exp_store_shard(exp)
+    split, name = _store_key(exp, split), split
     if split not in cache:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         window = (exp.window * 1000, 0)
         root = str(getattr(exp, 'data_dir', '') or '')
-        dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
+        dirs = [os.path.join(root, d) for d in (('test',) if name == 'test' else ('train', 'val'))]
         if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = cls.from_directories(dirs, exp.Tl, window, device)
+            cache[split] = cls.from_directories(dirs, exp.Tl, window, device, shard=shard)
         else:
             n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
-            size = exp.test_size if split == 'test' else exp.input_size
+            size = exp.test_size if name == 'test' else exp.input_size
             sensor = (min(240, size[0]), min(304, size[1]))
-            recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
-            cache[split] = cls(recs, exp.Tl, window, device, sensor_hw=sensor)
+            recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(name == 'test'))
+            cache[split] = cls(recs, exp.Tl, window, device, sensor_hw=sensor, shard=shard)
         if kind == 'windows':
             cache[split].trim()
     return cache[split]
@@ -821,16 +987,50 @@ class Gen1StoreLoader:
     (get_random_data, gen1.py:485-511): ``jitter_params(..., jitter=.3)``, then the permutation of its boxes, ``rng.permutation(n)`` -- the
     order ``np.random.shuffle`` gives the rows under the same state.  ``batches(epoch)`` returns the draws of an epoch, a function of (seed,
     epoch) alone; a step uploads them -- sample indices, params, box permutations -- and everything else happens on the device
-    (``store.frames``, ``store.targets``): no host read, no per-sample work.  ``store=None``: ``gen1_store_for(exp)``."""
+    (``store.frames``, ``store.targets``): no host read, no per-sample work.  ``store=None``: ``gen1_store_for(exp)``.
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+    On N ranks (``rank``, ``world``; ``batch_size`` is the per-rank batch b, the global batch is B = b * world):
+
+    * over a store that holds everything (replica mode) the epoch is the single-process epoch of batch B, and a rank keeps rows
+      ``rank::world`` of every batch: ``batches(e)[i]`` equals rows ``rank::world`` of ``Loader(exp, B, store, seed).batches(e)[i]``, array
+      for array, and ``len(loader) == len(store) // B``.  The random state is consumed in the global order -- every rank computes the
+      global draws and keeps its rows -- so the N rank batches of a step, interleaved, are the single-process batch with the same draw
+      per sample: the reference's ``InfiniteSampler`` (``perm[rank::world]``) taken b at a time.
+    * over a sharded store (``store.sharded``) an epoch is a permutation of ``store.owned_samples``, drawn -- with the per-sample draws, in
+      the same order -- from ``_shard_state(seed, epoch, rank)``: a function of (seed, epoch, rank) alone that differs between ranks.
+      ``len(loader)`` is the smallest owned count of any rank // b (``_sharded_iters``).  The rank is the store's (``store.shard``)
+      where it has one.
+
+    Before a step uploads its indices they are checked against ``store.owns`` on the host: IndexError for a sample whose records are
+    not here."""
+
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
         self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
         exp_aggregation(exp)
         self.store = store if store is not None else gen1_store_for(exp)
-        self.iters = len(self.store) // batch_size
-        assert self.iters >= 1, 'fewer labels than one batch'
+        self._plan(rank, world, 'labels')
         self.dataset = Gen1StoreDataset(exp, self.store)
         self.epoch = 0
+
+    def _plan(self, rank, world, what):
+        """``rank``, ``world``, ``sharded`` and ``iters`` of a training loader over ``self.store``"""
+        self.rank, self.world = (int(rank), int(world)) if self.store.shard is None else self.store.shard
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f'rank {rank} of a world of {world}')
+        self.sharded = self.store.sharded
+        if self.sharded:
+            self.iters = _sharded_iters(self.store, self.batch_size, self.rank)
+        else:
+            self.iters = len(self.store) // (self.batch_size * self.world)
+            assert self.iters >= 1, f'fewer {what} than one batch'
+
+    def _epoch(self, epoch):
+        """(random state, sample order, samples drawn per step, the rows of a step that this rank keeps) of an epoch"""
+        if self.sharded:
+            rs = _shard_state(self.seed, epoch, self.rank)
+            return rs, self.store.owned_samples[rs.permutation(len(self.store.owned_samples))], self.batch_size, slice(None)
+        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
+        return rs, rs.permutation(len(self.store)), self.batch_size * self.world, slice(self.rank, None, self.world)
 
     def __len__(self):
         return self.iters
@@ -841,20 +1041,19 @@ class Gen1StoreLoader:
     def batches(self, epoch):
         """[(sample indices int64 [B], params int32 [B, 5], box permutations int32 [B, P])] of an epoch; P = the store's largest group (at
         least 1), a row of a smaller group is filled up with the identity"""
-        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
-        order = rs.permutation(len(self.store))
+        rs, order, drawn, keep = self._epoch(epoch)
         (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
         P = max(self.store.max_group_rows, 1)
         out = []
         for i in range(self.iters):
-            idx = order[i * self.batch_size:(i + 1) * self.batch_size].astype(np.int64)
+            idx = order[i * drawn:(i + 1) * drawn].astype(np.int64)
             par = np.empty((len(idx), 5), dtype=np.int32)
             perm = np.tile(np.arange(P, dtype=np.int32), (len(idx), 1))
             for b, s in enumerate(idx):
                 par[b] = jitter_params(H, W, Hc, Wc, jitter=.3, rng=rs)
                 n = int(self.store.group_rows[s])
                 perm[b, :n] = rs.permutation(n)
-            out.append((idx, par, perm))
+            out.append(tuple(np.ascontiguousarray(a[keep]) for a in (idx, par, perm)))
         return out
 
     def __iter__(self):
@@ -862,6 +1061,7 @@ class Gen1StoreLoader:
         draws = self.batches(self.epoch)
         self.epoch += 1
         for idx, par, perm in draws:
+            self.store.check_owned(idx)
             idx, par, perm = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev), torch.from_numpy(perm).to(dev)
             yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, perm, self.exp.input_size, self.max_labels)
 
@@ -870,22 +1070,34 @@ class Gen1StoreEvalLoader:
     """Evaluation loader over a ``Gen1Store``: iterable of the tuple ``SyntheticEvalLoader`` yields -- ``(frames [B, Tl, Tm, 2, H, W] fp32
     on the GPU, labels [B][n, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
     get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``); the labels are the raw float32 rows of the store
-    (``Gen1Store.raw_labels``), prepared on the host once.  ``indices`` are this rank's samples; the last batch may be short."""
+    (``Gen1Store.raw_labels``), prepared on the host once.  ``indices`` are this rank's samples; the last batch may be short.  An index
+    whose records the store does not hold raises IndexError here, on the host.  ``min_batches``: the loader is at least that long;
+    the batches behind the last sample are empty (B = 0: no frames, no labels, no ids) -- what the ranks of a sharded evaluation, which
+    own different numbers of samples, are padded with where an evaluator meets the other ranks once per batch."""
 
-    def __init__(self, exp, batch_size, indices, store):
-        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+    def __init__(self, exp, batch_size, indices, store, min_batches=0):
+        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
         exp_aggregation(exp)
+        store.check_owned(self.indices)
         self.dataset = Gen1StoreDataset(exp, store)
         self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
 
     def __len__(self):
-        return (len(self.indices) + self.batch_size - 1) // self.batch_size
+        return max((len(self.indices) + self.batch_size - 1) // self.batch_size, self.min_batches)
+
+    def _empty(self):
+        """a batch without samples"""
+        frames = torch.zeros((0, getattr(self.store, 'Tl', 1), self.exp.Tm, 2) + tuple(self.exp.test_size), device=self.store.device)
+        return frames, [], (torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)), torch.zeros(0, dtype=torch.int64)
 
     def __iter__(self):
         (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
         row = letterbox_params(H, W, Hc, Wc)
         for b in range(len(self)):
             ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
+            if not ids:
+                yield self._empty()
+                continue
             idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
             frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
             yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
@@ -935,7 +1147,7 @@ def _h5_representations(rep_dir):
     return h5py.File(os.path.join(rep_dir, 'event_representations_ds2_nearest.h5'), 'r')['data']
 
 
-class Gen4Store:
+class Gen4Store(_Sharded):
     """1 Mpx (Gen4, RVT pre-processed) recordings and their labels resident on the device: what RVTGEN4Dataset keeps on disk and in host lists
     (rvt_gen4.py:93-97, 365-409), as tables that the kernels index.  ``recordings``: a list of ``(name, representations,
     objframe_idx_2_repr_idx, label_rows, objframe_idx_2_label_idx, label_times)`` -- ``representations`` is anything that has a length and
@@ -958,18 +1170,38 @@ class Gen4Store:
 
     ``device='cpu'`` builds the tables and leaves ``sums`` None: the representations are only measured, there is no summing on the host.
 
-    A store holds the recordings it is given; cutting a dataset that exceeds HBM into shards is the caller's business."""
+    On N ranks a store holds the labels of every recording and the bin sums of its own: ``owned`` (a collection of recording names, None
+    = all) or ``shard=(rank, world)`` (``shard_recordings`` by ``len(representations)``).  ``rep_offsets``, ``group_first`` and
+    ``group_lo`` stay in the coordinates of the whole dataset -- with ``boxes``, ``group_start``, ``sample_names``, the flat sample index,
+    ``raw_labels``, ``targets`` and the length they are the same on every rank and the same as the unsharded store's; a recording that
+    is not owned may pass None as its ``representations`` and is never touched (it then counts ``objframe_idx_2_repr_idx[-1] + 1``
+    representations, 0 without object frames: the weight ``from_directories`` gives it).  What ``sums`` holds is described by
+    ``held_offsets`` (host, int64 [F + 1]: a recording that is not owned has a zero-length area) and the device tables ``held_first`` /
+    ``held_lo`` int64 [G] that ``frames`` gathers: ``group_first`` / ``group_lo`` moved to the recording's place in ``sums``; a sample that
+    is not owned has ``held_first = -num_slice``, ``held_lo = 0``: every slice lies in front of its recording and is zero.  Without
+    ``owned`` / ``shard`` the held tables are the group tables themselves.  ``owned_samples``, ``owns``, ``shard``, ``sample_rank``: see
+    ``_Sharded``."""
 
-    def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64):
+    def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, owned=None, shard=None):
         self.num_slice, self.sensor_hw, self.nbins = int(num_slice), (int(sensor_hw[0]), int(sensor_hw[1])), int(nbins)
         self.down_sample_factor = down_sample_factor
         self.names, self.sample_names = [], []
         H, W = self.sensor_hw
         reps, rep_offsets, boxes, group_start, group_first, group_lo = [], [0], [], [0], [], []
+        held_offsets, group_file = [0], []
+        if shard is not None:
+            recordings = list(recordings)
+        owned, ranks = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)
         for name, rep, obj2repr, rows, obj2label, label_times in recordings:
-            if tuple(rep.shape[1:]) != (2 * self.nbins, H, W):
-                raise ValueError(f'{name}: representations of shape {tuple(rep.shape)}, expected [r, {2 * self.nbins}, {H}, {W}]')
             obj2repr, obj2label = np.asarray(obj2repr, dtype=np.int64), np.asarray(obj2label, dtype=np.int64)
+            mine = owned is None or name in owned
+            if not mine:                                        # labels only: the representations are not looked at beyond their number
+                n_rep = len(rep) if rep is not None else (int(obj2repr[-1]) + 1 if len(obj2repr) else 0)
+                rep = np.zeros((0, 2 * self.nbins, H, W), dtype=np.uint8)
+            elif tuple(rep.shape[1:]) != (2 * self.nbins, H, W):
+                raise ValueError(f'{name}: representations of shape {tuple(rep.shape)}, expected [r, {2 * self.nbins}, {H}, {W}]')
+            else:
+                n_rep = len(rep)
             if len(label_times) != len(obj2label):
                 raise ValueError(f'{name}: {len(label_times)} label times for {len(obj2label)} object frames')
             if getattr(rows, 'dtype', None) is not None and rows.dtype.names:
@@ -978,7 +1210,9 @@ class Gen4Store:
             self.names.append(name)
             offset = rep_offsets[-1]
             reps.append(rep)
-            rep_offsets.append(offset + len(rep))
+            rep_offsets.append(offset + n_rep)
+            held_offsets.append(held_offsets[-1] + len(rep))
+            group_file += [len(self.names) - 1] * len(obj2label)
             ends = np.r_[obj2label[1:], len(rows)]
             for k, (a, b) in enumerate(zip(obj2label, ends)):
                 box = gen4_raw_boxes(gen4_rescale_labels(rows[a:b], down_sample_factor, self.sensor_hw))
@@ -996,34 +1230,51 @@ class Gen4Store:
         self.device = torch.device(device)
         for k, v in self.host.items():
             setattr(self, k, torch.from_numpy(v).to(self.device))
+        file_owned = np.array([owned is None or n in owned for n in self.names], dtype=bool)
+        self.group_file = group_file = np.asarray(group_file, dtype=np.int64)                # (host: the recording of every sample)
+        self._set_owner(file_owned[group_file], shard, None if ranks is None else np.array([ranks[n] for n in self.names], dtype=np.int32)[group_file])
+        self.held_offsets = np.asarray(held_offsets, dtype=np.int64)
+        self.held_first, self.held_lo = self.group_first, self.group_lo
+        if self.sharded:
+            move = (self.held_offsets[:-1] - self.host['rep_offsets'][:-1])[group_file]
+            first = np.where(self._sample_owned, self.host['group_first'] + move, -self.num_slice)
+            lo = np.where(self._sample_owned, self.host['group_lo'] + move, 0)
+            self.held_first, self.held_lo = (torch.from_numpy(v.astype(np.int64)).to(self.device) for v in (first, lo))
         self.sums = None
         if self.device.type != 'cpu':
-            self.sums = torch.empty((rep_offsets[-1], 2, H, W), dtype=torch.uint16, device=self.device)
-            for rep, offset in zip(reps, rep_offsets):
+            self.sums = torch.empty((held_offsets[-1], 2, H, W), dtype=torch.uint16, device=self.device)
+            for rep, offset in zip(reps, held_offsets):
                 for a in range(0, len(rep), int(chunk)):
                     part = torch.from_numpy(np.ascontiguousarray(rep[a:a + int(chunk)], dtype=np.uint8)).to(self.device)
                     ops.stacked_hist_bin_sums(part, self.nbins, out=self.sums[offset + a:offset + a + part.shape[0]])
 
     @classmethod
     def from_directories(cls, paths, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, rep_name=GEN4_REP_NAME,
-                         read_representations=None):
+                         read_representations=None, shard=None):
         """the streams of the directories ``paths`` (extract_labels, rvt_gen4.py:389-407), every directory in sorted order (the reference
         takes them as ``os.listdir`` gives them): ``<stream>/labels_v2/labels.npz`` (``labels``, ``objframe_idx_2_label_idx``) and
         ``timestamps_us.npy``, ``<stream>/event_representations_v2/<rep_name>/objframe_idx_2_repr_idx.npy``, and the representations from
         ``read_representations(rep_dir)``.  Its default opens ``event_representations_ds2_nearest.h5`` with ``h5py`` (imported there; an
         ImportError that names ``h5py`` and this argument when it is missing) and returns its ``data``.  ``h5py`` is not among this
-        project's requirements: that default is the one line of the store no test reaches."""
+        project's requirements: that default is the one line of the store no test reaches.  ``shard=(rank, world)``: every stream is
+        listed and its label files are read; a stream weighs the last entry of its ``objframe_idx_2_repr_idx.npy`` + 1 (0 for an empty
+        file) -- the representations that its samples can reach, known without opening them --, and ``read_representations`` is called for
+        the streams ``shard_recordings`` gives to ``rank`` only."""
         import os
         read = read_representations if read_representations is not None else _h5_representations
-        recs = []
+        listed = []
         for path in ([paths] if isinstance(paths, str) else paths):
             for stream in sorted(os.listdir(path)):
                 label_dir = os.path.join(path, stream, 'labels_v2')
                 rep_dir = os.path.join(path, stream, 'event_representations_v2', rep_name)
                 labels = np.load(os.path.join(label_dir, 'labels.npz'))
-                recs.append((stream, read(rep_dir), np.load(os.path.join(rep_dir, 'objframe_idx_2_repr_idx.npy')), labels['labels'],
-                             labels['objframe_idx_2_label_idx'], np.load(os.path.join(label_dir, 'timestamps_us.npy'))))
-        return cls(recs, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk)
+                listed.append((stream, rep_dir, np.load(os.path.join(rep_dir, 'objframe_idx_2_repr_idx.npy')), labels['labels'],
+                               labels['objframe_idx_2_label_idx'], np.load(os.path.join(label_dir, 'timestamps_us.npy'))))
+        owned, ranks = _shard_plan([r[0] for r in listed], [int(r[2][-1]) + 1 if len(r[2]) else 0 for r in listed], shard, None)
+        recs = [(r[0], read(r[1]) if owned is None or r[0] in owned else None) + r[2:] for r in listed]
+        store = cls(recs, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk, owned=owned)
+        store._adopt(shard, ranks, store.names, store.group_file)
+        return store
 
     def __len__(self):
         return len(self.sample_names)
@@ -1040,11 +1291,14 @@ class Gen4Store:
         """model input [B, 1, num_slice, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): ``group_first`` and
         ``group_lo`` gathered on the device, then ``ops.count_store_frames``; ``params``: (nw, nh, dx, dy, flip) per sample, None = the
         sensor unscaled at the top left; ``canvas_hw``: ``exp.input_size`` unless given.  ``exp.Tm`` must be the store's ``num_slice``;
-        ``exp.aggregation`` is not consulted (the representations are histograms already).  Nothing is read back (graph-capturable)."""
+        ``exp.aggregation`` is not consulted (the representations are histograms already).  Nothing is read back (graph-capturable).
+        Precondition: the store holds the bin sums of every sample asked for (``owns``; the loaders check their indices on the host before
+        they upload them) -- a sample that is not owned comes out as zero frames, silently.  ``group_first`` / ``group_lo`` in the text
+        above are ``held_first`` / ``held_lo``, the same tables unless the store is sharded."""
         if getattr(exp, 'Tm', self.num_slice) != self.num_slice:
             raise ValueError(f'the store was built for {self.num_slice} slices per sample, the experiment asks for Tm = {exp.Tm}')
         Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
-        return ops.count_store_frames(self.sums, self.group_first[sample_idx], self.num_slice, Hc, Wc, lo=self.group_lo[sample_idx],
+        return ops.count_store_frames(self.sums, self.held_first[sample_idx], self.num_slice, Hc, Wc, lo=self.held_lo[sample_idx],
                                       params=None if params is None else params_on(params, self.device))
 
     def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
@@ -1058,24 +1312,27 @@ def hist_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'hist_store'``: ``Gen4Store.from_directories`` over ``exp.data_dir``/train + /val
     (``split='test'``: /test) when those directories exist, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files,
     representations per file), default (2, 24); the sensor is the downsampled 1 Mpx camera's, or the canvas where that is smaller).
-    ``num_slice`` is ``exp.Tm``; ``exp.nbins`` (default 10) and ``exp.down_sample_factor`` (default 2) are read where present.  Kept on the
-    experiment: one store per split."""
+    ``num_slice`` is ``exp.Tm``; ``exp.nbins`` (default 10) and ``exp.down_sample_factor`` (default 2) are read where present.
+    ``exp.store_shard`` = ``'recordings'``: the store of this rank.  Kept on the experiment: one store per (split, rank, world,
+    store_shard)."""
     import os
     cache = exp.__dict__.setdefault('_hist_stores', {})
+    shard = exp_store_shard(exp)
+    split, name = _store_key(exp, split), split
     if split not in cache:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         nbins, factor = int(getattr(exp, 'nbins', 10)), getattr(exp, 'down_sample_factor', 2)
         root = str(getattr(exp, 'data_dir', '') or '')
-        dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
+        dirs = [os.path.join(root, d) for d in (('test',) if name == 'test' else ('train', 'val'))]
         if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = Gen4Store.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins)
+            cache[split] = Gen4Store.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard)
         else:
             n_files, n_reps = getattr(exp, 'store_recordings', (2, 24))[:2]
-            size = exp.test_size if split == 'test' else exp.input_size
+            size = exp.test_size if name == 'test' else exp.input_size
             sensor = (min(360, size[0]), min(640, size[1]))
-            recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
-            cache[split] = Gen4Store(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins)
+            recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(name == 'test'))
+            cache[split] = Gen4Store(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
     return cache[split]
 
 
@@ -1089,13 +1346,13 @@ class Gen4StoreLoader(Gen1StoreLoader):
     rows (cls, cx, cy, w, h), zero padded).  The epochs, the draws and the step are ``Gen1StoreLoader``'s: an epoch is a permutation of the
     samples; per sample ``jitter_params(..., jitter=.3)``, then ``rng.permutation(n)`` of its boxes, in get_random_data's order
     (rvt_gen4.py:562-588); ``batches(epoch)`` is a function of (seed, epoch); a step uploads indices, params and permutations and nothing
-    else.  ``exp.aggregation`` is not consulted, as in ``SyntheticStackedHistLoader``.  ``store=None``: ``hist_store_for(exp)``."""
+    else.  ``exp.aggregation`` is not consulted, as in ``SyntheticStackedHistLoader``.  ``store=None``: ``hist_store_for(exp)``.  ``rank``,
+    ``world`` and a sharded store: as in ``Gen1StoreLoader``."""
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
         self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
         self.store = store if store is not None else hist_store_for(exp)
-        self.iters = len(self.store) // batch_size
-        assert self.iters >= 1, 'fewer labels than one batch'
+        self._plan(rank, world, 'labels')
         self.dataset = Gen4StoreDataset(exp, self.store)
         self.epoch = 0
 
@@ -1106,8 +1363,9 @@ class Gen4StoreEvalLoader(Gen1StoreEvalLoader):
     sensor on ``exp.test_size``, the raw float32 rows of ``Gen4Store.raw_labels``, the sensor's sizes.  ``exp.aggregation`` is not
     consulted."""
 
-    def __init__(self, exp, batch_size, indices, store):
-        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+    def __init__(self, exp, batch_size, indices, store, min_batches=0):
+        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
+        store.check_owned(self.indices)
         self.dataset = Gen4StoreDataset(exp, store)
         self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
 
@@ -1156,7 +1414,7 @@ def synth_ncaltech_recordings(n_files, n_events, sensor_hw=(180, 240), n_classes
     return out
 
 
-class NCaltechStore:
+class NCaltechStore(_Sharded):
     """N-Caltech101 recordings and their boxes resident on the device: what NCaltech keeps on disk (ncaltech.py:43-61, 172-178), as tables that
     the kernels index.  ``recordings``: a list of ``(class_name, stem, atis_bytes, annotation_bytes)`` -- the byte images of
     ``Caltech101/<class>/<stem>.bin`` and its ``annotation`` file; recordings of ``BACKGROUND_Google`` are left out.  ``Tl``: macro slices per
@@ -1166,12 +1424,20 @@ class NCaltechStore:
     indices), ``index`` (``ops.atis_store_index(records)``, the buffer's overflow prefix: two launches over the store, never again), ``boxes``
     float32 [F, 5] rows (x1, y1, x2, y2, class) (``raw_bboxes``, ncaltech.py:176-177) and ``group_start`` = arange(F + 1): one box per
     sample.  On the host: ``sample_names`` ``<class>-<stem>`` (ncaltech.py:59, 194), ``class_names`` (given, else the sorted names of the
-    recordings' classes), ``max_file_records`` and numpy copies of the tables (``host``).  The flat sample index is the recording's."""
+    recordings' classes), ``max_file_records`` and numpy copies of the tables (``host``).  The flat sample index is the recording's.
 
-    def __init__(self, recordings, Tl, window, device, class_names=None, sensor_hw=(180, 240)):
+    On N ranks a store holds the boxes of every recording and the records of its own: ``owned`` (a collection of sample names
+    ``<class>-<stem>``, None = all) or ``shard=(rank, world)`` (``shard_recordings`` by ``len(atis_bytes)``).  A recording that is not
+    owned contributes its box, its name and a zero-length area to ``records`` / ``file_offsets``; its ``atis_bytes`` may be None and is
+    never touched.  ``boxes``, ``group_start``, ``sample_names``, ``class_names``, ``raw_labels``, ``targets`` and the length are the same
+    on every rank and the same as the unsharded store's; ``max_file_records`` is that of the owned recordings.  ``owned_samples``,
+    ``owns``, ``shard``, ``sample_rank``: see ``_Sharded``."""
+
+    def __init__(self, recordings, Tl, window, device, class_names=None, sensor_hw=(180, 240), owned=None, shard=None):
         self.Tl, self.sensor_hw = int(Tl), (int(sensor_hw[0]), int(sensor_hw[1]))
         self.window = None if window is None else (int(window[0]), int(window[1]))
         recordings = [r for r in recordings if r[0] != NCALTECH_BACKGROUND]
+        owned, ranks = _memory_plan(recordings, lambda r: f'{r[0]}-{r[1]}', lambda r: r[2], shard, owned)
         if class_names is None:
             class_names = sorted({r[0] for r in recordings})
         self.class_names = list(class_names)
@@ -1179,6 +1445,8 @@ class NCaltechStore:
         self.sample_names = []
         areas, file_offsets, boxes = [], [0], []
         for cls, stem, rec, ann in recordings:
+            if owned is not None and f'{cls}-{stem}' not in owned:
+                rec = b''                                       # labels only: the recording is not looked at
             buf = np.frombuffer(rec, dtype=np.uint8) if isinstance(rec, (bytes, bytearray, memoryview)) else np.asarray(rec, dtype=np.uint8)
             if len(buf) % 5 != 0:
                 raise ValueError(f'{cls}/{stem}: not an ATIS recording of 5-byte records ({len(buf)} bytes)')
@@ -1190,6 +1458,8 @@ class NCaltechStore:
         self.host = dict(file_offsets=np.asarray(file_offsets, dtype=np.int64), boxes=np.asarray(boxes, dtype=np.float32).reshape(F, 5),
                          group_start=np.arange(F + 1, dtype=np.int64))
         self.max_file_records = int(np.diff(self.host['file_offsets']).max()) if F else 0
+        self._set_owner([owned is None or n in owned for n in self.sample_names], shard,
+                        None if ranks is None else [ranks[n] for n in self.sample_names])
         self.device = torch.device(device)
         self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
         for k, v in self.host.items():
@@ -1198,22 +1468,30 @@ class NCaltechStore:
         self.index = ops.atis_store_index(self.records) if self.device.type == 'cuda' else None
 
     @classmethod
-    def from_directory(cls, root, split, Tl, window, device, class_names=None, sensor_hw=(180, 240)):
+    def from_directory(cls, root, split, Tl, window, device, class_names=None, sensor_hw=(180, 240), shard=None, read_bin=None):
         """the recordings of ``<root>/<split>.txt`` -- ``data_path label_path`` per line, relative to ``root``; lines that name
         ``BACKGROUND_Google`` are dropped (ncaltech.py:48-51) --, read with ``numpy.fromfile``.  The class of a sample is the directory of its
         label file, its stem the data file's name up to the first dot.  ``class_names=None``: the sorted directory names of
-        ``<root>/Caltech101`` without ``BACKGROUND_Google`` (ncaltech.py:129-134)."""
+        ``<root>/Caltech101`` without ``BACKGROUND_Google`` (ncaltech.py:129-134).  ``shard=(rank, world)``: every line is listed and every
+        annotation read; a recording weighs the size of its ``.bin`` (``os.path.getsize``), and only the recordings ``shard_recordings``
+        gives to ``rank`` are read.  ``read_bin(path)``: the reader of a recording (default ``numpy.fromfile(path, dtype=numpy.uint8)``)."""
         import os
+        read_bin = read_bin if read_bin is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
         with open(os.path.join(root, split + '.txt')) as f:
             lines = [ln for ln in f.readlines() if NCALTECH_BACKGROUND not in ln]
         if class_names is None:
             class_names = [n.strip() for n in sorted(os.listdir(os.path.join(root, 'Caltech101'))) if NCALTECH_BACKGROUND not in n]
-        recs = []
+        listed = []
         for ln in lines:
             data_path, label_path = ln.strip().split(' ')
-            recs.append((label_path.split('/')[-2], data_path.split('/')[-1].split('.')[0],
-                         np.fromfile(os.path.join(root, data_path), dtype=np.uint8), np.fromfile(os.path.join(root, label_path), dtype=np.uint8)))
-        return cls(recs, Tl, window, device, class_names=class_names, sensor_hw=sensor_hw)
+            listed.append((label_path.split('/')[-2], data_path.split('/')[-1].split('.')[0], os.path.join(root, data_path),
+                           np.fromfile(os.path.join(root, label_path), dtype=np.uint8)))
+        names = [f'{c}-{stem}' for c, stem, _, _ in listed]
+        owned, ranks = _shard_plan(names, [os.path.getsize(r[2]) for r in listed] if shard is not None else (), shard, None)
+        recs = [(c, stem, read_bin(path) if owned is None or n in owned else None, ann) for n, (c, stem, path, ann) in zip(names, listed)]
+        store = cls(recs, Tl, window, device, class_names=class_names, sensor_hw=sensor_hw, owned=owned)
+        store._adopt(shard, ranks, store.sample_names, np.arange(len(store)))
+        return store
 
     def __len__(self):
         return len(self.sample_names)
@@ -1229,7 +1507,8 @@ class NCaltechStore:
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): the store operator that
         ``exp.aggregation`` / ``exp.measure`` select, as ``atis_to_frames`` selects its own, on the B recordings alone, then the cubic
         letterbox; ``params``: (nw, nh, dx, dy, flip) per sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back
-        (graph-capturable)."""
+        (graph-capturable).  Precondition: the store holds the records of every sample asked for (``owns``; the loaders check their
+        indices on the host before they upload them) -- a sample that is not owned has no records here."""
         kind = _atis_choice((self.Tl, exp.Tm, self.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))[-1]
         op = {'latest': ops.event_latest_surface_atis_store, 'timesurface': ops.event_timesurface_atis_store,
               'count': ops.event_histogram_atis_store}[kind]
@@ -1247,23 +1526,27 @@ class NCaltechStore:
 def ncaltech_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'atis_store'``: ``NCaltechStore.from_directory`` over ``exp.data_dir`` when it holds
     ``<split>.txt``, seeded synthetic recordings otherwise (``exp.atis_store_recordings`` = (files, events per file), default (16, 20000);
-    the sensor is N-Caltech101's, or the canvas where that is smaller).  Kept on the experiment: one store per split."""
+    the sensor is N-Caltech101's, or the canvas where that is smaller).  ``exp.store_shard`` = ``'recordings'``: the store of this rank.
+    Kept on the experiment: one store per (split, rank, world, store_shard)."""
     import os
     cache = exp.__dict__.setdefault('_atis_stores', {})
+    shard = exp_store_shard(exp)
+    split, name = _store_key(exp, split), split
     if split not in cache:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         window = (exp.window * 1000, 0) if getattr(exp, 'window', None) is not None else None
         root = str(getattr(exp, 'data_dir', '') or '')
-        if root and os.path.isfile(os.path.join(root, split + '.txt')):
-            cache[split] = NCaltechStore.from_directory(root, split, exp.Tl, window, device)
+        if root and os.path.isfile(os.path.join(root, name + '.txt')):
+            cache[split] = NCaltechStore.from_directory(root, name, exp.Tl, window, device, shard=shard)
         else:
             n_files, n_events = getattr(exp, 'atis_store_recordings', (16, 20_000))
-            size = exp.input_size if split == 'train' else exp.test_size
+            size = exp.input_size if name == 'train' else exp.test_size
             sensor = (min(180, size[0]), min(240, size[1]))
             n_classes = max(int(exp.num_classes), 1)
-            recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(split != 'train'))
-            cache[split] = NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor)
+            recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(name != 'train'))
+            cache[split] = NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor,
+                                         shard=shard)
     return cache[split]
 
 
@@ -1285,14 +1568,16 @@ class NCaltechStoreLoader:
     order (NCaltech.get_random_data, ncaltech.py:330-350): ``jitter_params(..., jitter=.1)`` and nothing else -- ``np.random.shuffle`` of the
     sample's single box consumes no random state.  ``batches(epoch)`` returns the draws of an epoch, a function of (seed, epoch) alone; a
     step uploads them -- sample indices and params -- and everything else happens on the device (``store.frames``, ``store.targets``): no
-    host read, no per-sample work.  ``store=None``: ``ncaltech_store_for(exp)``."""
+    host read, no per-sample work.  ``store=None``: ``ncaltech_store_for(exp)``.  ``rank``, ``world`` and a sharded store: the rules of
+    ``Gen1StoreLoader`` (rows ``rank::world`` of the global batch / a permutation of the owned samples from ``_shard_state``; the index
+    check before the upload)."""
+    _plan, _epoch = Gen1StoreLoader._plan, Gen1StoreLoader._epoch
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50):
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
         self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
         self.store = store if store is not None else ncaltech_store_for(exp)
         _atis_choice((self.store.Tl, exp.Tm, self.store.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))
-        self.iters = len(self.store) // batch_size
-        assert self.iters >= 1, 'fewer recordings than one batch'
+        self._plan(rank, world, 'recordings')
         self.dataset = NCaltechStoreDataset(exp, self.store)
         self.epoch = 0
 
@@ -1304,14 +1589,13 @@ class NCaltechStoreLoader:
 
     def batches(self, epoch):
         """[(sample indices int64 [B], params int32 [B, 5])] of an epoch"""
-        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
-        order = rs.permutation(len(self.store))
+        rs, order, drawn, keep = self._epoch(epoch)
         (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
         out = []
         for i in range(self.iters):
-            idx = order[i * self.batch_size:(i + 1) * self.batch_size].astype(np.int64)
+            idx = order[i * drawn:(i + 1) * drawn].astype(np.int64)
             par = np.array([jitter_params(H, W, Hc, Wc, jitter=.1, rng=rs) for _ in idx], dtype=np.int32).reshape(len(idx), 5)
-            out.append((idx, par))
+            out.append(tuple(np.ascontiguousarray(a[keep]) for a in (idx, par)))
         return out
 
     def __iter__(self):
@@ -1319,6 +1603,7 @@ class NCaltechStoreLoader:
         draws = self.batches(self.epoch)
         self.epoch += 1
         for idx, par in draws:
+            self.store.check_owned(idx)
             idx, par = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev)
             yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, self.exp.input_size, self.max_labels)
 
@@ -1328,21 +1613,24 @@ class NCaltechStoreEvalLoader:
     fp32 on the GPU, labels [B][1, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
     get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``, the cubic resize: N-Caltech101 resizes in evaluation too); the
     labels are the raw float32 rows of the store (``NCaltechStore.raw_labels``), prepared on the host once; the sizes are the sensor's and
-    the ids index ``sample_names``.  ``indices`` are this rank's samples; the last batch may be short."""
+    the ids index ``sample_names``.  ``indices`` are this rank's samples; the last batch may be short.  The index check and ``min_batches``
+    are ``Gen1StoreEvalLoader``'s."""
+    __len__, _empty = Gen1StoreEvalLoader.__len__, Gen1StoreEvalLoader._empty
 
-    def __init__(self, exp, batch_size, indices, store):
-        self.exp, self.batch_size, self.indices, self.store = exp, batch_size, list(indices), store
+    def __init__(self, exp, batch_size, indices, store, min_batches=0):
+        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
+        store.check_owned(self.indices)
         self.dataset = NCaltechStoreDataset(exp, store)
         self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
-
-    def __len__(self):
-        return (len(self.indices) + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
         (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
         row = letterbox_params(H, W, Hc, Wc)
         for b in range(len(self)):
             ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
+            if not ids:
+                yield self._empty()
+                continue
             idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
             frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
             yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
