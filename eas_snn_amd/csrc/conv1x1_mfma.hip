@@ -955,7 +955,7 @@ int w1_group_select(const W1Shape& sh, const W1GroupArgs& a, int blocks, hipStre
 
 int eas_conv1x1_wgrad_slices(int NI, int Cin, int Cout, int HW, int x_terms, int planes) {
     W1Geom g{};
-    if (HW % 16 != 0) return 0;
+    if (HW % 16 != 0 || (planes && Cin % 8 != 0)) return 0;      // what eas_conv1x1_wgrad_dispatch refuses
     return w1_plan(g, NI, Cin, Cout, HW, x_terms, planes != 0).slices;
 }
 

@@ -64,6 +64,20 @@ def test_weight_gradient_queries_say_zero_where_the_launch_refuses():
             assert 1 <= lib.eas_conv_wgrad_parts(NI, Cin, Cout, H, W, s, xt) <= 8, (NI, Cin, Cout, H, W, s, xt)
 
 
+def test_1x1_weight_gradient_query_says_zero_where_the_launch_refuses():
+    """the 1x1 branch of eas_conv_wgrad_workspace_floats (conv1x1_mfma.hip eas_conv1x1_wgrad_slices; no GPU needed): 0 for maps whose pixel
+    count is no multiple of 16 in every input form, and for spike planes whose channels are not whole 8-groups -- what
+    eas_conv1x1_wgrad_dispatch refuses; whole slabs of Cout * Cin floats otherwise."""
+    lib = eas_snn_amd.hip_library()
+    for xt in (1, 2, 3):
+        assert lib.eas_conv_wgrad_workspace_floats(2, 16, 24, 5, 7, 1, 1, xt) == 0, xt          # HW = 35
+        assert lib.eas_conv_wgrad_workspace_floats(2, 16, 24, 6, 8, 1, 2, xt) == 0, xt          # no stride-2 1x1
+        floats = lib.eas_conv_wgrad_workspace_floats(2, 16, 24, 6, 8, 1, 1, xt)
+        assert floats > 0 and floats % (24 * 16) == 0, xt
+    assert lib.eas_conv_wgrad_workspace_floats(2, 12, 24, 6, 8, 1, 1, 2) == 0
+    assert lib.eas_conv_wgrad_workspace_floats(2, 12, 24, 6, 8, 1, 1, 3) > 0 and lib.eas_conv_wgrad_workspace_floats(2, 12, 24, 6, 8, 1, 1, 1) > 0
+
+
 def test_stride2_input_gradient_query_is_the_launch_rule_and_the_route_follows_it():
     """eas_conv_dgrad_s2_supported is the plan eas_conv_dgrad_s2 launches by (conv_s2d.hip; no GPU needed): 1 for every row of the
     fp64-compared GPU cases, 0 for an odd output width (Wo = 5), output channels that are no multiple of 8 (Cout = 12), rows wider than the

@@ -2,6 +2,7 @@
 Integer work is compared bit-exact; fp32 membrane potentials / gradients to 1e-4 relative (north_star)."""
 import glob
 import os
+import re
 
 import numpy as np
 import pytest
@@ -1776,12 +1777,32 @@ def test_stride2_convolution_on_rows_wider_than_the_tile_takes_the_library_input
     assert err < 1e-5, f'{err:.2e}'
 
 
+def _conv1x1_kernels(tr):
+    """the distinct conv1x1_* kernel instances of a kernel trace, as 'conv1x1_mfma_kernel<3, 1, 2, false, false, 3>'"""
+    out = set()
+    for sym in tr.kernels:
+        if 'conv1x1_' in sym:
+            s = re.sub(r'^void\s+', '', sym).replace('(anonymous namespace)::', '')
+            out.add(s[:s.index('>(') + 1] if '>(' in s else s)
+    return sorted(out)
+
+
+# (NI, Cin, Cout, H, W) of the real-valued 1x1 rows below -> the BatchNorm + activation (LM = 3) instance conv1x1_dispatch_t picks for it
+FUSED_ANN_1X1_INSTANCES = {
+    (3, 64, 32, 8, 10): 'conv1x1_mfma_kernel<3, 1, 1, false, false, 3>', (2, 128, 128, 16, 20): 'conv1x1_mfma_kernel<3, 1, 1, false, false, 3>',
+    (2, 96, 96, 32, 40): 'conv1x1_mfma_kernel<3, 1, 1, false, false, 3>', (64, 128, 128, 16, 20): 'conv1x1_mfma_kernel<3, 1, 1, false, false, 3>',
+    (64, 256, 128, 32, 40): 'conv1x1_mfma_sharedA_kernel<3, 4, 1, false, 3>', (64, 512, 256, 8, 10): 'conv1x1_mfma_sharedA_kernel<3, 2, 1, false, 3>',
+    (16, 8, 24, 64, 160): 'conv1x1_mfma_kernel<3, 1, 2, false, false, 3>', (16, 256, 1024, 5, 160): 'conv1x1_mfma_sharedA_kernel<3, 4, 2, false, 3>'}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('NI,Cin,Ca,Cb,H,W,k,s,spikes', [(3, 64, 32, 0, 8, 10, 1, 1, False), (2, 128, 64, 64, 16, 20, 1, 1, False), (2, 32, 40, 0, 16, 20, 3, 1, False),
                                                        (2, 64, 64, 0, 32, 40, 3, 2, False), (64, 256, 128, 128, 8, 10, 3, 1, False), (4, 512, 256, 0, 8, 10, 1, 1, True),
                                                        (2, 96, 48, 48, 32, 40, 1, 1, False), (2, 24, 48, 0, 16, 160, 3, 1, False), (3, 128, 72, 56, 16, 20, 3, 1, True),
                                                        (64, 128, 128, 128, 32, 40, 3, 1, False), (64, 256, 64, 64, 32, 40, 1, 1, False), (64, 128, 128, 0, 32, 40, 3, 2, False),
-                                                       (64, 512, 256, 0, 8, 10, 1, 1, False), (64, 128, 128, 0, 16, 20, 1, 1, False)])
+                                                       (64, 512, 256, 0, 8, 10, 1, 1, False), (64, 128, 128, 0, 16, 20, 1, 1, False),
+                                                       # the smallest 1x1 layers on a direct tile of two pixel tiles per wave and on the shared (4,2) tile
+                                                       (16, 8, 24, 0, 64, 160, 1, 1, False), (16, 256, 1024, 0, 5, 160, 1, 1, False)])
 @pytest.mark.parametrize('cat', [False, True])
 def test_fused_real_valued_eval_block_is_bit_identical_to_conv_then_bn_silu(dev, NI, Cin, Ca, Cb, H, W, k, s, spikes, cat):
     """eas_conv_bn_act_eval (conv -> BatchNorm with running statistics -> SiLU in the epilogue of the 1x1 / 3x3 kernels) against eas_conv_fwd
@@ -1814,6 +1835,8 @@ def test_fused_real_valued_eval_block_is_bit_identical_to_conv_then_bn_silu(dev,
         with ops.kernel_trace() as tr:
             got = ops.conv_bn_act_eval(x, conv, bns, cats=[(bufs[i], 8) for i in range(len(bns))] if cat else None)
         assert [n for n, _ in tr.calls if n.startswith('eas_conv')] == ['eas_conv_bn_act_eval'], tr.calls
+        if k == 1:       # the LM = 3 instance this row stands for
+            assert _conv1x1_kernels(tr) == [FUSED_ANN_1X1_INSTANCES[(NI, Cin, Ca + Cb, H, W)]], _conv1x1_kernels(tr)
         got = got if Cb else [got]
         for i, (c, bn) in enumerate(zip(convs, bns)):
             want = ops.bn_silu(ops.conv2d(x, c), bn)
@@ -1826,7 +1849,16 @@ def test_fused_real_valued_eval_block_is_bit_identical_to_conv_then_bn_silu(dev,
 FUSED_EVAL_CASES = [  # T, N, Cin, Cout, H, W, k, stride
     (3, 2, 16, 32, 8, 10, 3, 1), (3, 5, 32, 64, 16, 20, 3, 1), (3, 3, 64, 64, 32, 40, 3, 1), (3, 2, 32, 64, 16, 20, 3, 2), (5, 2, 48, 96, 16, 20, 3, 1),
     (5, 3, 24, 48, 32, 40, 3, 2), (3, 7, 64, 32, 8, 10, 1, 1), (3, 2, 128, 64, 16, 20, 1, 1), (5, 2, 96, 48, 16, 20, 1, 1), (3, 4, 512, 256, 8, 10, 1, 1),
-    (5, 2, 384, 192, 8, 10, 1, 1), (3, 2, 32, 40, 64, 80, 3, 1), (3, 1, 32, 64, 128, 160, 1, 1), (3, 64, 256, 256, 8, 10, 3, 1)]
+    (5, 2, 384, 192, 8, 10, 1, 1), (3, 2, 32, 40, 64, 80, 3, 1), (3, 1, 32, 64, 128, 160, 1, 1), (3, 64, 256, 256, 8, 10, 3, 1),
+    # 1x1 layers with enough blocks for two channel tiles per wave: the direct form, and from 256 input channels the shared-fragment form
+    (3, 64, 16, 512, 5, 20, 1, 1), (5, 64, 16, 512, 5, 20, 1, 1), (3, 64, 256, 512, 5, 20, 1, 1), (5, 64, 256, 512, 5, 20, 1, 1)]
+# (T, N, Cin, Cout, H, W) of the 1x1 rows -> the fused-neuron (LM = 1) instance eas_conv1x1_lif_dispatch picks for it: all six
+FUSED_EVAL_1X1_INSTANCES = {
+    (3, 7, 64, 32, 8, 10): 'conv1x1_mfma_kernel<1, 1, 3, false, true, 1>', (3, 2, 128, 64, 16, 20): 'conv1x1_mfma_kernel<1, 1, 3, false, true, 1>',
+    (5, 2, 96, 48, 16, 20): 'conv1x1_mfma_kernel<1, 1, 5, false, true, 1>', (3, 4, 512, 256, 8, 10): 'conv1x1_mfma_kernel<1, 1, 3, false, true, 1>',
+    (5, 2, 384, 192, 8, 10): 'conv1x1_mfma_kernel<1, 1, 5, false, true, 1>', (3, 1, 32, 64, 128, 160): 'conv1x1_mfma_kernel<1, 1, 3, false, true, 1>',
+    (3, 64, 16, 512, 5, 20): 'conv1x1_mfma_kernel<1, 2, 3, false, true, 1>', (5, 64, 16, 512, 5, 20): 'conv1x1_mfma_kernel<1, 2, 5, false, true, 1>',
+    (3, 64, 256, 512, 5, 20): 'conv1x1_mfma_sharedA_kernel<1, 2, 3, true, 1>', (5, 64, 256, 512, 5, 20): 'conv1x1_mfma_sharedA_kernel<1, 2, 5, true, 1>'}
 
 
 @pytest.mark.gpu
@@ -1879,6 +1911,8 @@ def test_fused_eval_step_is_bit_identical_to_conv_then_bn_lif(dev, monkeypatch, 
         names = [c[0] for c in tr.calls]
         assert ('eas_conv_bn_lif_eval' in names) == fused, names
         assert not fused or not any(n.startswith('eas_conv_fwd') or n.startswith('eas_bn_lif') for n in names), names
+        if fused and k == 1:      # the LM = 1 instance this row stands for
+            assert _conv1x1_kernels(tr) == [FUSED_EVAL_1X1_INSTANCES[(T, N, Cin, Cout, H, W)]], _conv1x1_kernels(tr)
         runs.append((ops.dense(out).clone(), blk.act.v.clone(), None if rate is None else rate.clone()))
     functional.reset_net(blk)
     (o1, v1, r1), (o0, v0, r0) = runs
