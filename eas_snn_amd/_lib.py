@@ -168,6 +168,10 @@ PROTOTYPES = {
     'eas_stacked_hist_frames': (C.c_int, [_P, C.c_int64, _P, _P, _P] + [C.c_int] * 7 + [_P, _P, _P]),
     'eas_stacked_hist_bin_sums': (C.c_int, [_P, C.c_int64] + [C.c_int] * 3 + [_P, _P]),
     'eas_count_store_frames': (C.c_int, [_P, C.c_int64, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P]),
+    'eas_count_rows_measure': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    'eas_count_rows_pack': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_int64, _P]),
+    'eas_count_rows_unpack': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    'eas_packed_store_frames': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P]),
     'eas_label_targets': (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P] + [C.c_int] * 7 + [_P, _P, _P, _P]),
     'eas_lif_fwd': (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int64, _P]),
     'eas_lif_bwd': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,

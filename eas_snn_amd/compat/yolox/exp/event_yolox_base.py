@@ -197,6 +197,7 @@ class EventExp(BaseExp):
             from eas_snn_amd.data import NCaltechStoreLoader
             return NCaltechStoreLoader(self, batch_size, **ranks)
         if getattr(self, 'train_input', None) == 'hist_store':         # opt-in: 1 Mpx from recordings in HBM (sample indices -> frames and targets)
+            # ``store_sums`` = 'packed': the store keeps the bin sums in packed rows (data.hist_store_for; the evaluation store too)
             from eas_snn_amd.data import Gen4StoreLoader
             return Gen4StoreLoader(self, batch_size, **ranks)
         return SyntheticEventLoader(self, batch_size)

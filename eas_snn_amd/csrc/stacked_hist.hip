@@ -1,6 +1,7 @@
 // RVT "stacked histogram" representations -> per-polarity event counts on the model canvas: three kernels over shared pieces (SliceRule:
 // which representation feeds a slice; bin_sums16: the bin sum of 16 pixels; the paste and resize rule of count_resize.h; the row sources
-// BinPlanes / SumPlanes: what the band kernel stages, from the representations as they are or from their bin sums).
+// BinPlanes / SumPlanes / PackedPlanes: what the band kernel stages, from the representations as they are, from their bin sums or from the
+// bin sums in packed rows), and the three kernels that measure, pack and unpack such rows.
 //
 // eas_stacked_hist_event_sum, the config-4 input: replaces RVTGEN4Dataset.generate_slices(..., method='event_sum') + the zero padding of the
 // validation letterbox (yolox/data/datasets/rvt_gen4.py:109-125 and :516-533 with scale 1).
@@ -156,7 +157,9 @@ __global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_bin_sums_kernel(const 
 // the representations as they are, u8 [R][2 * nbins][H][W]: nbins byte-plane loads and adds
 template <int NB>
 struct BinPlanes {
-    using elem = uint8_t;
+    using handle = const uint8_t* __restrict__;
+    static constexpr int kMaxW = 65536;                                       // a tap is 16 bits
+    static bool valid(const uint8_t* store) { return store && !((uintptr_t)store & 15); }
     const uint8_t* src0;
     int64_t plane;
     int nbins, W;
@@ -172,7 +175,9 @@ struct BinPlanes {
 // their bin sums, u16 [R][2][H][W] (eas_stacked_hist_bin_sums): a copy of 16-bit rows, 16-byte loads where rows are 16-byte aligned
 // (W % 8 == 0: a row then ends on a 16-byte boundary, so a group holds 8 or 16 pixels), element by element otherwise
 struct SumPlanes {
-    using elem = uint16_t;
+    using handle = const uint16_t* __restrict__;
+    static constexpr int kMaxW = 65536;
+    static bool valid(const uint16_t* store) { return store && !((uintptr_t)store & 15); }
     const uint16_t* src0;
     int W;
     bool aligned;
@@ -197,6 +202,148 @@ struct SumPlanes {
     }
 };
 
+// ---- packed rows ---------------------------------------------------------------------------------------------------------------------------
+// The bin sums of one source row (one polarity of one representation), cut into G = ceil(W / 16) <= 64 groups of 16 pixels (pixels at and
+// behind W: zero).  A group is zero (nothing stored), narrow (every sum <= 255: 16 bytes, pixel order) or wide (sixteen u16: the eight
+// words of sums16).  Row table int64 [rows][3] = (nz, wide, offset): bit g of nz / wide = group g is not zero / is wide, offset = the row's
+// first 16-byte unit in the payload; group g starts at unit offset + popcount(nz & below(g)) + popcount(wide & below(g)).
+__device__ __forceinline__ uint4 narrow_bytes(const uint32_t (&sum)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        w[q] = (sum[2 * q] & 0xffu) | ((sum[2 * q] >> 8) & 0xff00u) | ((sum[2 * q + 1] & 0xffu) << 16) | ((sum[2 * q + 1] & 0xff0000u) << 8);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void widen_bytes(const uint4& v, uint32_t (&sum)[8]) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        sum[2 * q] = (w[q] & 0xffu) | ((w[q] & 0xff00u) << 8);
+        sum[2 * q + 1] = ((w[q] >> 16) & 0xffu) | ((w[q] >> 8) & 0xff0000u);
+    }
+}
+// units of the payload in front of group g of a row, counted from the row's offset
+__device__ __forceinline__ uint64_t units_below(uint64_t nz, uint64_t wide, int g) {
+    const uint64_t below = ((uint64_t)1 << g) - 1;
+    return (uint64_t)(__popcll(nz & below) + __popcll(wide & below));
+}
+
+// a store of packed rows as the kernels take it, by value: the row table, the payload and its length in units.  The table is device data
+// nobody has validated: a group whose units do not lie inside [0, units) is never read and comes out as zeros.
+struct PackedRows {
+    const int64_t* rows;
+    const uint4* payload;
+    int64_t units;
+};
+// group g (0 <= g < 64) of the row whose three words stand at ``words``, as the eight words of sums16
+__device__ __forceinline__ void packed_group16(const int64_t* __restrict__ words, const uint4* __restrict__ payload, uint64_t units, int g,
+                                               uint32_t (&sum)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) sum[q] = 0;
+    const uint64_t nz = (uint64_t)words[0];
+    if (!((nz >> g) & 1)) return;                                               // a zero group: the payload is not touched
+    const uint64_t wide = (uint64_t)words[1], unit = (uint64_t)words[2] + units_below(nz, wide, g);
+    const bool is_wide = (wide >> g) & 1;
+    if (unit >= units || units - unit < (is_wide ? 2u : 1u)) return;
+    const uint4 a = payload[unit];
+    if (is_wide) {
+        const uint4 b = payload[unit + 1];
+        sum[0] = a.x; sum[1] = a.y; sum[2] = a.z; sum[3] = a.w;
+        sum[4] = b.x; sum[5] = b.y; sum[6] = b.z; sum[7] = b.w;
+    } else {
+        widen_bytes(a, sum);
+    }
+}
+// the packed rows of the summed store, table int64 [R][2][H][3] (eas_count_rows_pack): per group the row's three words, then nothing, 16 or
+// 32 bytes of payload
+struct PackedPlanes {
+    using handle = PackedRows;
+    static constexpr int kMaxW = 1024;                                        // 64 groups: one bit each in nz and wide
+    static bool valid(const PackedRows& s) {
+        return s.rows && !((uintptr_t)s.rows & 7) && s.units >= 0 && (s.payload || s.units == 0) && !((uintptr_t)s.payload & 15);
+    }
+    const int64_t* rows0;
+    const uint4* payload;
+    uint64_t units;
+    __device__ __forceinline__ PackedPlanes(const PackedRows& store, int64_t rep, int p, int, int H, int)
+        : rows0(store.rows + (rep * 2 + p) * ((int64_t)H * 3)), payload(store.payload), units((uint64_t)store.units) {}
+    __device__ __forceinline__ void sums16(int row, int x0, uint32_t (&sum)[8]) const {
+        packed_group16(rows0 + (int64_t)row * 3, payload, units, x0 >> 4, sum);
+    }
+};
+
+// The three row kernels: one wave per row, lane g takes group g (G <= 64).  ``row`` runs over [n][2][H] of a chunk of u16 sums.
+constexpr int kRowsPerBlock = EAS_BLOCK / 64;
+
+// lane g's group of row ``row`` of the u16 sums [n][2][H][W], through SumPlanes
+__device__ __forceinline__ void sums_group16(const uint16_t* __restrict__ sums, int64_t row, int H, int W, int g, uint32_t (&sum)[8]) {
+    const int64_t plane = row / H;
+    const SumPlanes src(sums, plane >> 1, (int)(plane & 1), 0, H, W);
+    src.sums16((int)(row - plane * H), g * 16, sum);
+}
+
+// eas_count_rows_measure: two ballots give the row's masks; lane 0 writes (nz, wide, units of the row)
+__global__ __launch_bounds__(EAS_BLOCK) void count_rows_measure_kernel(const uint16_t* __restrict__ sums, int64_t n_rows, int H, int W,
+                                                                       int64_t* __restrict__ table) {
+    const int lane = threadIdx.x & 63, G = (W + 15) >> 4;
+    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows) return;                                                  // (the whole wave)
+    uint32_t any = 0, high = 0;
+    if (lane < G) {
+        uint32_t sum[8];
+        sums_group16(sums, row, H, W, lane, sum);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { any |= sum[q]; high |= sum[q] & 0xff00ff00u; }
+    }
+    const uint64_t nz = __ballot(any != 0), wide = __ballot(high != 0);
+    if (lane == 0) {
+        table[row * 3] = (int64_t)nz;
+        table[row * 3 + 1] = (int64_t)wide;
+        table[row * 3 + 2] = __popcll(nz) + __popcll(wide);
+    }
+}
+
+// eas_count_rows_pack: the table is trusted for the class and the place of every group; nothing outside units [unit_lo, unit_hi) is written
+__global__ __launch_bounds__(EAS_BLOCK) void count_rows_pack_kernel(const uint16_t* __restrict__ sums, int64_t n_rows, int H, int W,
+                                                                    const int64_t* __restrict__ table, uint4* __restrict__ payload, uint64_t unit_lo,
+                                                                    uint64_t unit_hi) {
+    const int lane = threadIdx.x & 63, G = (W + 15) >> 4;
+    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows || lane >= G) return;
+    const uint64_t nz = (uint64_t)table[row * 3], wide = (uint64_t)table[row * 3 + 1];
+    if (!((nz >> lane) & 1)) return;
+    const uint64_t unit = (uint64_t)table[row * 3 + 2] + units_below(nz, wide, lane);
+    const bool is_wide = (wide >> lane) & 1;
+    if (unit < unit_lo || unit >= unit_hi || unit_hi - unit < (is_wide ? 2u : 1u)) return;
+    uint32_t sum[8];
+    sums_group16(sums, row, H, W, lane, sum);
+    if (is_wide) {
+        payload[unit] = make_uint4(sum[0], sum[1], sum[2], sum[3]);
+        payload[unit + 1] = make_uint4(sum[4], sum[5], sum[6], sum[7]);
+    } else {
+        payload[unit] = narrow_bytes(sum);
+    }
+}
+
+// eas_count_rows_unpack: the inverse -- 16-byte stores where rows are 16-byte aligned (W % 8 == 0), elements otherwise
+__global__ __launch_bounds__(EAS_BLOCK) void count_rows_unpack_kernel(PackedRows store, int64_t n_rows, int W, uint16_t* __restrict__ sums) {
+    const int lane = threadIdx.x & 63, G = (W + 15) >> 4;
+    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows || lane >= G) return;
+    uint32_t sum[8];
+    packed_group16(store.rows + row * 3, store.payload, (uint64_t)store.units, lane, sum);
+    const int x0 = lane * 16, n_left = W - x0;
+    uint16_t* d = sums + row * W + x0;
+    if ((W & 7) == 0) {
+        reinterpret_cast<uint4*>(d)[0] = make_uint4(sum[0], sum[1], sum[2], sum[3]);
+        if (n_left >= 16) reinterpret_cast<uint4*>(d)[1] = make_uint4(sum[4], sum[5], sum[6], sum[7]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            if (e < n_left) d[e] = (uint16_t)(sum[e >> 1] >> (16 * (e & 1)));
+    }
+}
+
 // ---- training input: indices into a resident store -> augmented frames (eas_stacked_hist_frames) --------------------------------------
 // RVTGEN4Dataset.__getitem__ for a training sample (rvt_gen4.py:190-235): the last Tm representations up to the label's
 // (generate_slices, :109-125, zero slices in front of a young sequence), the bin sum, then get_random_data's resize / paste / flip with cv2.INTER_LINEAR (:510-598) -- the arithmetic of
@@ -209,14 +356,15 @@ struct SumPlanes {
 // slices and bands outside the paste rectangle are stores only.  Everything read from device memory is clamped: a slice index by
 // SliceRule, the paste row by Paste (count_resize.h), and a source row or column index comes out of linear_tap, which clamps to the sensor.
 // The staging step reads through a row source (above): BinPlanes for eas_stacked_hist_frames, SumPlanes -- the same rows already summed,
-// 2 bytes per pixel in place of nbins -- for eas_count_store_frames; everything else is one body.
+// 2 bytes per pixel in place of nbins -- for eas_count_store_frames, PackedPlanes -- those rows packed -- for eas_packed_store_frames;
+// everything else is one body.  The source's handle (a pointer, or PackedRows) comes in by value.
 constexpr int kFrameBandRows = 8;             // output rows per block at most (fewer on wide sensors: frames_band_rows)
 constexpr int kFrameLdsBytes = 48 * 1024;     // staged rows + tap tables
 
 struct XTap { uint32_t s01; float w1; };      // s0 | s1 << 16; w1 < 0: outside the paste rectangle
 
 template <typename Src>
-__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(const typename Src::elem* __restrict__ store, int64_t R,
+__global__ __launch_bounds__(EAS_BLOCK) void stacked_hist_frames_kernel(typename Src::handle store, int64_t R,
                                                                         const int64_t* __restrict__ first, const int64_t* __restrict__ lo,
                                                                         const int32_t* __restrict__ params, int Tm, int nbins_rt, int H, int W,
                                                                         int Hc, int Wc, int band_rows, int nbands, float* __restrict__ out,
@@ -325,14 +473,14 @@ int frames_band_rows(int W, int Wc) {
     return rows;
 }
 
-// the two frame entries: the argument checks, the band plan and the launch of the band kernel on the entry's row source
+// the three frame entries: the argument checks, the band plan and the launch of the band kernel on the entry's row source
 template <typename Src>
-int frames_call(const typename Src::elem* store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm, int nbins,
+int frames_call(typename Src::handle store, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm, int nbins,
                 int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream) {
-    if (!store || !first || !out || R < 1 || B < 1 || Tm < 1 || nbins < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
-    if ((((uintptr_t)store | (uintptr_t)out) & 15) || (((uintptr_t)first | (uintptr_t)lo) & 7) || (((uintptr_t)params | (uintptr_t)flags) & 3))
+    if (!Src::valid(store) || !first || !out || R < 1 || B < 1 || Tm < 1 || nbins < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1) return EAS_ERR_INVALID_ARG;
+    if (((uintptr_t)out & 15) || (((uintptr_t)first | (uintptr_t)lo) & 7) || (((uintptr_t)params | (uintptr_t)flags) & 3))
         return EAS_ERR_INVALID_ARG;
-    if (Wc % 16 != 0 || nbins > 255 || W > 65536) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32; taps are 16 bits
+    if (Wc % 16 != 0 || nbins > 255 || W > Src::kMaxW) return EAS_ERR_UNSUPPORTED;      // model canvases are multiples of 32; taps are 16 bits
     const int band_rows = frames_band_rows(W, Wc);
     if (band_rows < 1) return EAS_ERR_UNSUPPORTED;
     const int nbands = (Hc + band_rows - 1) / band_rows;
@@ -376,6 +524,63 @@ extern "C" int eas_stacked_hist_frames(const uint8_t* store, int64_t R, const in
 extern "C" int eas_count_store_frames(const uint16_t* sums, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm,
                                       int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream) {
     return frames_call<SumPlanes>(sums, R, first, lo, params, B, Tm, 1, H, W, Hc, Wc, out, flags, stream);
+}
+
+extern "C" int eas_packed_store_frames(const int64_t* table, const uint8_t* payload, int64_t units, int64_t R, const int64_t* first, const int64_t* lo,
+                                       const int32_t* params, int B, int Tm, int H, int W, int Hc, int Wc, float* out, uint32_t* flags,
+                                       eas_stream_t stream) {
+    return frames_call<PackedPlanes>(PackedRows{table, reinterpret_cast<const uint4*>(payload), units}, R, first, lo, params, B, Tm, 1, H, W, Hc, Wc, out,
+                                     flags, stream);
+}
+
+namespace {
+// what the three row entries ask of their common arguments; the u16 side is read or written in 16-byte pieces where W % 8 == 0
+int rows_args(const uint16_t* sums, int64_t n, int H, int W, const int64_t* table, int64_t* blocks) {
+    if (!sums || !table || n < 0 || H < 1 || W < 1) return EAS_ERR_INVALID_ARG;
+    if (((uintptr_t)table & 7) || ((uintptr_t)sums & ((W & 7) == 0 ? 15 : 1))) return EAS_ERR_INVALID_ARG;
+    if (W > PackedPlanes::kMaxW) return EAS_ERR_UNSUPPORTED;
+    *blocks = (n * 2 * H + kRowsPerBlock - 1) / kRowsPerBlock;
+    return *blocks > INT32_MAX ? EAS_ERR_UNSUPPORTED : EAS_OK;
+}
+}  // namespace
+
+extern "C" int eas_count_rows_measure(const uint16_t* sums, int64_t n, int H, int W, int64_t* table, eas_stream_t stream) {
+    int64_t blocks;
+    if (const int err = rows_args(sums, n, H, W, table, &blocks)) return err;
+    if (n == 0) return EAS_OK;
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH(count_rows_measure_kernel, dim3((unsigned)blocks), dim3(EAS_BLOCK), 0, st, sums, n * 2 * H, H, W, table);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+extern "C" int eas_count_rows_pack(const uint16_t* sums, int64_t n, int H, int W, const int64_t* table, uint8_t* payload, int64_t unit_lo,
+                                   int64_t unit_hi, eas_stream_t stream) {
+    int64_t blocks;
+    if (const int err = rows_args(sums, n, H, W, table, &blocks)) return err;
+    if (unit_lo < 0 || unit_hi < unit_lo || (!payload && unit_hi > unit_lo) || ((uintptr_t)payload & 15)) return EAS_ERR_INVALID_ARG;
+    if (n == 0 || unit_hi == unit_lo) return EAS_OK;
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH(count_rows_pack_kernel, dim3((unsigned)blocks), dim3(EAS_BLOCK), 0, st, sums, n * 2 * H, H, W, table, reinterpret_cast<uint4*>(payload),
+               (uint64_t)unit_lo, (uint64_t)unit_hi);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+extern "C" int eas_count_rows_unpack(const int64_t* table, const uint8_t* payload, int64_t units, int64_t n, int H, int W, uint16_t* sums,
+                                     eas_stream_t stream) {
+    int64_t blocks;
+    if (const int err = rows_args(sums, n, H, W, table, &blocks)) return err;
+    const PackedRows store{table, reinterpret_cast<const uint4*>(payload), units};
+    if (!PackedPlanes::valid(store)) return EAS_ERR_INVALID_ARG;
+    if (n == 0) return EAS_OK;
+    hipStream_t st = eas_s(stream);
+    EAS_CLEAR_ERR();
+    EAS_LAUNCH(count_rows_unpack_kernel, dim3((unsigned)blocks), dim3(EAS_BLOCK), 0, st, store, n * 2 * H, W, sums);
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
 }
 
 extern "C" int eas_stacked_hist_bin_sums(const uint8_t* hist, int64_t n, int nbins, int H, int W, uint16_t* sums, eas_stream_t stream) {

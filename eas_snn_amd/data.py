@@ -1242,11 +1242,17 @@ class Gen4Store(_Sharded):
             self.held_first, self.held_lo = (torch.from_numpy(v.astype(np.int64)).to(self.device) for v in (first, lo))
         self.sums = None
         if self.device.type != 'cpu':
-            self.sums = torch.empty((held_offsets[-1], 2, H, W), dtype=torch.uint16, device=self.device)
-            for rep, offset in zip(reps, held_offsets):
-                for a in range(0, len(rep), int(chunk)):
-                    part = torch.from_numpy(np.ascontiguousarray(rep[a:a + int(chunk)], dtype=np.uint8)).to(self.device)
-                    ops.stacked_hist_bin_sums(part, self.nbins, out=self.sums[offset + a:offset + a + part.shape[0]])
+            self._sum_recordings(reps, held_offsets, int(chunk))
+
+    def _sum_recordings(self, reps, held_offsets, chunk):
+        """the device side of the build: ``sums`` at its final size, every recording uploaded ``chunk`` representations at a time and summed
+        into its place (``reps``: the representations of every recording, empty where not owned; ``held_offsets``: their places)"""
+        H, W = self.sensor_hw
+        self.sums = torch.empty((held_offsets[-1], 2, H, W), dtype=torch.uint16, device=self.device)
+        for rep, offset in zip(reps, held_offsets):
+            for a in range(0, len(rep), chunk):
+                part = torch.from_numpy(np.ascontiguousarray(rep[a:a + chunk], dtype=np.uint8)).to(self.device)
+                ops.stacked_hist_bin_sums(part, self.nbins, out=self.sums[offset + a:offset + a + part.shape[0]])
 
     @classmethod
     def from_directories(cls, paths, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, rep_name=GEN4_REP_NAME,
@@ -1298,8 +1304,12 @@ class Gen4Store(_Sharded):
         if getattr(exp, 'Tm', self.num_slice) != self.num_slice:
             raise ValueError(f'the store was built for {self.num_slice} slices per sample, the experiment asks for Tm = {exp.Tm}')
         Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
-        return ops.count_store_frames(self.sums, self.held_first[sample_idx], self.num_slice, Hc, Wc, lo=self.held_lo[sample_idx],
-                                      params=None if params is None else params_on(params, self.device))
+        return self._frames_from(self.held_first[sample_idx], self.held_lo[sample_idx], Hc, Wc,
+                                 None if params is None else params_on(params, self.device))
+
+    def _frames_from(self, first, lo, Hc, Wc, params):
+        """the frame operator of this store's form on gathered indices"""
+        return ops.count_store_frames(self.sums, first, self.num_slice, Hc, Wc, lo=lo, params=params)
 
     def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
         """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
@@ -1308,17 +1318,100 @@ class Gen4Store(_Sharded):
                                  canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
 
 
+class Gen4PackedStore(Gen4Store):
+    """``Gen4Store`` with the bin sums in packed rows (include/eas_hip.h states the format): a row -- one sensor row of one polarity of one
+    representation -- is cut into groups of 16 pixels; an all-zero group stores nothing, a group whose sums are all at most 255 stores 16
+    bytes, any other its sixteen u16.  ``rows`` int64 [R, 2, H, 3] = (nz, wide, offset) per row, ``payload`` uint8 [used_bytes]; ``sums`` stays
+    None.  The frames are bit-identical to the parent's (``ops.packed_store_frames``: the band kernel decodes a group where it stages it);
+    labels, names, ``targets``, ``raw_labels``, ``owned`` / ``shard`` and ``from_directories`` are the parent's.
+
+    The build, per chunk of ``chunk`` representations: upload, ``ops.stacked_hist_bin_sums`` into a chunk-sized scratch,
+    ``ops.count_rows_pack`` into the arena at the position reached -- the full u16 form never exists on the device.  The arena is allocated
+    once, ``capacity_bytes`` (None: the smaller of the u16 size of what the store holds -- rows counted in whole groups, which no packing
+    exceeds -- and 0.8 of the free device memory); recordings that need more raise ValueError naming the bytes needed, after everything was
+    measured.  ``used_bytes``: what the rows take; ``nbytes``: table + used payload; ``trim()`` gives the rest of the arena back.  A sensor
+    wider than 1024 pixels raises ValueError (64 groups per row).  ``device='cpu'`` builds the tables and leaves ``rows`` / ``payload`` None."""
+
+    def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, owned=None, shard=None,
+                 capacity_bytes=None):
+        if int(sensor_hw[1]) > ops.PACKED_MAX_W:
+            raise ValueError(f'packed rows hold at most 64 groups of 16 pixels: a sensor of width {int(sensor_hw[1])} > {ops.PACKED_MAX_W}')
+        self.capacity_bytes = None if capacity_bytes is None else int(capacity_bytes)
+        self.rows, self.payload, self.used_bytes = None, None, 0
+        super().__init__(recordings, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk,
+                         owned=owned, shard=shard)
+
+    def _sum_recordings(self, reps, held_offsets, chunk):
+        H, W = self.sensor_hw
+        R = int(held_offsets[-1])
+        if self.capacity_bytes is None:
+            u16_bytes = R * 2 * H * ((W + 15) // 16) * 32
+            self.capacity_bytes = min(u16_bytes, int(0.8 * torch.cuda.mem_get_info(self.device)[0]))
+        self.capacity_bytes = max(self.capacity_bytes, 0) // 16 * 16
+        self.rows = torch.empty((R, 2, H, 3), dtype=torch.int64, device=self.device)
+        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+        scratch = torch.empty((min(chunk, max([len(r) for r in reps], default=0)), 2, H, W), dtype=torch.uint16, device=self.device)
+        units, needed, full = 0, 0, False
+        for rep, offset in zip(reps, held_offsets):
+            for a in range(0, len(rep), chunk):
+                part = torch.from_numpy(np.ascontiguousarray(rep[a:a + chunk], dtype=np.uint8)).to(self.device)
+                n = part.shape[0]
+                sums = ops.stacked_hist_bin_sums(part, self.nbins, out=scratch[:n])
+                del part
+                try:
+                    took = ops.count_rows_pack(sums, self.rows[offset + a:offset + a + n], self._arena, units, dry_run=full)
+                except ops.PackedArenaFull as e:                # too small: go on measuring, store nothing more
+                    took, full = e.units, True
+                needed += took
+                units += 0 if full else took
+        if full:
+            del self._arena, self.rows
+            self.rows = None
+            raise ValueError(f'the packed rows of these recordings need {needed * 16} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
+        self.used_bytes = units * 16
+        self.payload = self._arena[:self.used_bytes]
+
+    @property
+    def nbytes(self):
+        """bytes of the row table and of the payload in use"""
+        return self.rows.numel() * 8 + self.used_bytes
+
+    def trim(self):
+        """reallocate ``payload`` to the used size and let the arena go (the two exist side by side for the time of the copy)"""
+        if self.capacity_bytes != self.used_bytes:
+            self.payload = self.payload.clone()
+            self._arena, self.capacity_bytes = self.payload, self.used_bytes
+        return self
+
+    def unpacked(self, a, b):
+        """``torch.uint16`` [b - a, 2, H, W]: the bin sums of the held representations ``a`` .. ``b`` in the parent's form"""
+        return ops.count_rows_unpack(self.rows[a:b], self.payload, self.sensor_hw[1])
+
+    def _frames_from(self, first, lo, Hc, Wc, params):
+        """``frames`` is the parent's: ``held_first`` / ``held_lo`` gathered on the device, then ``ops.packed_store_frames`` in place of
+        ``ops.count_store_frames`` (nothing read back, graph-capturable)"""
+        return ops.packed_store_frames(self.rows, self.payload, first, self.num_slice, Hc, Wc, lo=lo, params=params, W=self.sensor_hw[1])
+
+
+STORE_SUMS = ('u16', 'packed')              # ``exp.store_sums``: the bin sums as uint16 planes (Gen4Store) / in packed rows (Gen4PackedStore)
+
+
 def hist_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'hist_store'``: ``Gen4Store.from_directories`` over ``exp.data_dir``/train + /val
     (``split='test'``: /test) when those directories exist, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files,
     representations per file), default (2, 24); the sensor is the downsampled 1 Mpx camera's, or the canvas where that is smaller).
     ``num_slice`` is ``exp.Tm``; ``exp.nbins`` (default 10) and ``exp.down_sample_factor`` (default 2) are read where present.
-    ``exp.store_shard`` = ``'recordings'``: the store of this rank.  Kept on the experiment: one store per (split, rank, world,
-    store_shard)."""
+    ``exp.store_shard`` = ``'recordings'``: the store of this rank.  ``exp.store_sums`` (default ``'u16'``) = ``'packed'``: a
+    ``Gen4PackedStore``; any other value raises ValueError.  Kept on the experiment: one store per (split, rank, world, store_shard,
+    store_sums)."""
     import os
+    kind = getattr(exp, 'store_sums', 'u16')
+    if kind not in STORE_SUMS:
+        raise ValueError(f'store_sums must be one of {STORE_SUMS}, got {kind!r}')
+    cls = Gen4PackedStore if kind == 'packed' else Gen4Store
     cache = exp.__dict__.setdefault('_hist_stores', {})
     shard = exp_store_shard(exp)
-    split, name = _store_key(exp, split), split
+    split, name = _store_key(exp, split) + (kind,), split
     if split not in cache:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -1326,13 +1419,13 @@ def hist_store_for(exp, split='train', device=None):
         root = str(getattr(exp, 'data_dir', '') or '')
         dirs = [os.path.join(root, d) for d in (('test',) if name == 'test' else ('train', 'val'))]
         if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = Gen4Store.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard)
+            cache[split] = cls.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard)
         else:
             n_files, n_reps = getattr(exp, 'store_recordings', (2, 24))[:2]
             size = exp.test_size if name == 'test' else exp.input_size
             sensor = (min(360, size[0]), min(640, size[1]))
             recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(name == 'test'))
-            cache[split] = Gen4Store(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
+            cache[split] = cls(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
     return cache[split]
 
 

@@ -356,6 +356,100 @@ def count_store_frames(sums, first, Tm, Hc, Wc, lo=None, params=None, return_fla
     return (out, flags) if return_flags else out
 
 
+PACKED_MAX_W = 1024          # 64 groups of 16 pixels: one bit each in the two masks of a row
+
+
+class PackedArenaFull(ValueError):
+    """``count_rows_pack`` found the arena too small; ``units``: what the chunk takes (nothing was written to the arena)"""
+
+    def __init__(self, msg, units):
+        super().__init__(msg)
+        self.units = units
+
+
+def _packed_rows_args(sums, table, payload):
+    """the shapes and types the three row operators share; returns (n, H, W)"""
+    _dev(sums, table, payload)
+    assert sums.dtype == torch.uint16 and sums.dim() == 4 and sums.shape[1] == 2 and sums.is_contiguous()
+    n, _, H, W = sums.shape
+    if W > PACKED_MAX_W:
+        raise ValueError(f'packed rows hold at most 64 groups of 16 pixels: W = {W} > {PACKED_MAX_W}')
+    assert table.dtype == torch.int64 and table.shape == (n, 2, H, 3) and table.is_contiguous() and table.device == sums.device
+    assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous() and payload.device == sums.device
+    return n, H, W
+
+
+def count_rows_pack(sums, table_out, payload, unit_offset, dry_run=False):
+    """Packs the bin sums ``sums`` ``torch.uint16`` [n, 2, H, W] (``stacked_hist_bin_sums``) into rows of 16-pixel groups -- a zero group stores
+    nothing, a group whose maximum is at most 255 16 bytes, any other 32 (include/eas_hip.h states the format) -- behind unit ``unit_offset``
+    (units of 16 bytes) of the arena ``payload`` (uint8 [capacity], 16-byte aligned), and fills ``table_out`` int64 [n, 2, H, 3] = (nz, wide,
+    offset) -- a contiguous view into a table allocated once (``table[a:a + n]``).  Three steps: ``eas_count_rows_measure`` (masks and units
+    of every row), an exclusive scan of the units on the device plus ``unit_offset``, ``eas_count_rows_pack``.  Returns the units used: the one
+    value a call reads back.  An arena that cannot take them raises ``PackedArenaFull`` (a ValueError that names the bytes needed) before
+    anything is written to it; ``dry_run``: measure and fill the table only, the arena is neither checked nor written.  W > 1024 raises
+    ValueError."""
+    n, H, W = _packed_rows_args(sums, table_out, payload)
+    unit_offset = int(unit_offset)
+    assert unit_offset >= 0
+    if n == 0:
+        return 0
+    _call('eas_count_rows_measure', 2 * sums.numel() + 8 * table_out.numel(), _lib.lib().eas_count_rows_measure, ptr(sums), n, H, W, ptr(table_out),
+          stream())
+    third = table_out[..., 2]
+    ends = torch.cumsum(third.reshape(-1), 0)
+    units = int(ends[-1])                                      # (the read of a build step)
+    third.copy_((ends - third.reshape(-1) + unit_offset).reshape(third.shape))
+    if dry_run:
+        return units
+    if (unit_offset + units) * 16 > payload.numel():
+        raise PackedArenaFull(f'the packed rows need {(unit_offset + units) * 16} bytes, the arena holds {payload.numel()}', units)
+    _call('eas_count_rows_pack', 2 * sums.numel() + 8 * table_out.numel() + 16 * units, _lib.lib().eas_count_rows_pack, ptr(sums), n, H, W,
+          ptr(table_out), ptr(payload), unit_offset, unit_offset + units, stream())
+    return units
+
+
+def count_rows_unpack(table, payload, W):
+    """The inverse of ``count_rows_pack``: ``table`` int64 [n, 2, H, 3] (the rows of n representations, a contiguous view ``table[a:b]`` of a
+    store's table; the offsets stay positions in the whole ``payload``) and ``payload`` uint8 [used bytes] -> ``torch.uint16`` [n, 2, H, W]."""
+    _dev(table, payload)
+    assert table.dtype == torch.int64 and table.dim() == 4 and table.shape[1] == 2 and table.shape[3] == 3 and table.is_contiguous()
+    n, _, H, _ = table.shape
+    sums = torch.empty((n, 2, H, int(W)), dtype=torch.uint16, device=table.device)
+    _packed_rows_args(sums, table, payload)
+    if n:
+        _call('eas_count_rows_unpack', 2 * sums.numel() + 8 * table.numel() + payload.numel(), _lib.lib().eas_count_rows_unpack, ptr(table),
+              ptr(payload), payload.numel() // 16, n, H, int(W), ptr(sums), stream())
+    return sums
+
+
+def packed_store_frames(table, payload, first, Tm, Hc, Wc, lo=None, params=None, return_flags=False, *, W):
+    """``count_store_frames`` on a store in packed rows: ``table`` int64 [R, 2, H, 3] and ``payload`` uint8 [used bytes] (``count_rows_pack`` of
+    the bin sums of one or more recordings back to back; ``W``, by keyword: the sensor's width, which the table does not carry) -> fp32 model input
+    [B, 1, Tm, 2, Hc, Wc], bit-identical to ``count_store_frames`` on those sums with the same ``first``, ``lo``, ``params``.  Nothing is read
+    back (graph-capturable)."""
+    _dev(table, payload, first, lo, params)
+    assert table.dtype == torch.int64 and table.dim() == 4 and table.shape[1] == 2 and table.shape[3] == 3
+    assert payload.dtype == torch.uint8 and payload.dim() == 1
+    assert first.dtype == torch.int64 and first.dim() == 1
+    if W > PACKED_MAX_W:
+        raise ValueError(f'packed rows hold at most 64 groups of 16 pixels: W = {W} > {PACKED_MAX_W}')
+    table, payload, first = table.contiguous(), payload.contiguous(), first.contiguous()
+    R, _, H, _ = table.shape
+    B = first.numel()
+    if lo is not None:
+        assert lo.dtype == torch.int64 and lo.shape == (B,)
+        lo = lo.contiguous()
+    if params is not None:
+        assert params.dtype == torch.int32 and params.shape == (B, 5)
+        params = params.contiguous()
+    out = torch.empty((B, 1, Tm, 2, Hc, Wc), dtype=torch.float32, device=table.device)
+    flags = torch.empty(B, dtype=torch.int32, device=table.device) if return_flags else None
+    # bytes: at most what the u16 store reads (every group wide) + the row words + the frames
+    _call('eas_packed_store_frames', B * Tm * 2 * H * (2 * int(W) + 24) + 4 * out.numel(), _lib.lib().eas_packed_store_frames, ptr(table), ptr(payload),
+          payload.numel() // 16, R, ptr(first), ptr(lo), ptr(params), B, int(Tm), H, int(W), Hc, Wc, ptr(out), ptr(flags), stream())
+    return (out, flags) if return_flags else out
+
+
 def label_targets(boxes, group_start, group, params, ih, iw, h, w, perm=None, max_labels=50, return_info=False):
     """The label side of a training batch from a box table in HBM: ``targets`` fp32 [B, max_labels, 5] rows (cls, cx, cy, w, h), zero padded --
     the box half of get_random_data (gen1.py:437, 459-468, 510-521), ``reformat('cxcywh')`` and EventTrainTransform for every sample in one

@@ -291,6 +291,32 @@ int eas_stacked_hist_bin_sums(const uint8_t* hist, int64_t n, int nbins, int H, 
  * eas_stacked_hist_bin_sums was fed from. */
 int eas_count_store_frames(const uint16_t* sums, int64_t R, const int64_t* first, const int64_t* lo, const int32_t* params, int B, int Tm,
                            int H, int W, int Hc, int Wc, float* out, uint32_t* flags, eas_stream_t stream);
+/* The summed store in PACKED ROWS (additive, ABI 9).  A row is one sensor row of one polarity of one representation, rows in the order
+ * [R][2][H]; it is cut into G = ceil(W / 16) groups of 16 pixels (pixels at and behind W count as zero; G <= 64, so W > 1024 is
+ * EAS_ERR_UNSUPPORTED).  A group is zero (all 16 sums 0: nothing stored), narrow (maximum <= 255: 16 bytes, one per pixel, pixel order) or
+ * wide (sixteen little-endian u16).  table: int64 [n][2][H][3] = (nz, wide, offset) as bit patterns -- bit g of nz: group g is not zero, bit
+ * g of wide: group g is wide, offset: the row's first unit of 16 bytes in the payload; group g starts at unit
+ * offset + popcount(nz & ((1 << g) - 1)) + popcount(wide & ((1 << g) - 1)), a row takes popcount(nz) + popcount(wide) units.  payload: 16-byte
+ * aligned, every access a 16-byte load or store.  sums: u16 [n][2][H][W] (eas_stacked_hist_bin_sums), 16-byte aligned where W % 8 == 0.
+ * eas_count_rows_measure writes (nz, wide, units of the row) for every row of ``sums``; the caller turns the third word into offsets (an
+ * exclusive scan plus the position reached in the payload) and hands the table to eas_count_rows_pack, which writes every group to its
+ * place.  That kernel trusts the table for class and place, and writes nothing outside units [unit_lo, unit_hi) of ``payload`` (the chunk's
+ * range; the caller checks unit_hi against the payload's capacity).  eas_count_rows_unpack is the inverse for the n representations whose
+ * rows ``table`` points to; ``units`` is the length of the payload: a group the table places outside [0, units) is not read and comes
+ * out as zeros.  n == 0 returns EAS_OK without a launch. */
+int eas_count_rows_measure(const uint16_t* sums, int64_t n, int H, int W, int64_t* table, eas_stream_t stream);
+int eas_count_rows_pack(const uint16_t* sums, int64_t n, int H, int W, const int64_t* table, uint8_t* payload, int64_t unit_lo, int64_t unit_hi,
+                        eas_stream_t stream);
+int eas_count_rows_unpack(const int64_t* table, const uint8_t* payload, int64_t units, int64_t n, int H, int W, uint16_t* sums,
+                          eas_stream_t stream);
+/* eas_count_store_frames on such a store: table int64 [R][2][H][3] (8-byte aligned), payload of ``units`` units (16-byte aligned; NULL only
+ * with units == 0); every other argument, the clamping of first / lo, the flag bit, the paste and resize rule, zero slices and the error
+ * returns are that entry's (the same kernel body, whose staging step decodes a group where it stages it: the row's three words, then
+ * nothing, 16 or 32 bytes of payload), and W > 1024 is EAS_ERR_UNSUPPORTED.  Bit-identical to eas_count_store_frames on the sums that
+ * eas_count_rows_pack was fed from.  As in eas_count_rows_unpack a group placed outside the payload is zeros. */
+int eas_packed_store_frames(const int64_t* table, const uint8_t* payload, int64_t units, int64_t R, const int64_t* first, const int64_t* lo,
+                            const int32_t* params, int B, int Tm, int H, int W, int Hc, int Wc, float* out, uint32_t* flags,
+                            eas_stream_t stream);
 
 /* The LABEL side of a training batch from a box table that stays in HBM (additive, ABI 9; csrc/labels.hip): the box half of
  * GEN1Dataset.get_random_data (gen1.py:437, 459-468, 510-521; rvt_gen4.py:510-598 and ncaltech.py:272-366 are the same arithmetic), then
