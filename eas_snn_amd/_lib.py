@@ -164,6 +164,11 @@ PROTOTYPES = {
     'eas_event_window_search': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P]),
     'eas_event_histogram_dat_ranges': (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P, _P]),
     'eas_records_gather': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    'eas_records_pack_measure': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    'eas_records_pack': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_int64, _P]),
+    'eas_records_unpack': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
+    'eas_event_histogram_packed_ranges': (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P] + [C.c_int] * 4 + [_P, _P, _P, _P]),
+    'eas_event_latest_surface_packed_ranges': (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P] + [C.c_int] * 4 + [C.c_double, _P, _P, _P, _P]),
     'eas_stacked_hist_event_sum': (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
     'eas_stacked_hist_frames': (C.c_int, [_P, C.c_int64, _P, _P, _P] + [C.c_int] * 7 + [_P, _P, _P]),
     'eas_stacked_hist_bin_sums': (C.c_int, [_P, C.c_int64] + [C.c_int] * 3 + [_P, _P]),

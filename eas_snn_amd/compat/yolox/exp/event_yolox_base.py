@@ -26,6 +26,7 @@ _DEFAULTS = dict(
     no_aug_epochs=0, ema=True, optimizer='ADAM', weight_decay=0, momentum=0.9, print_interval=10, eval_interval=10,
     save_history_ckpt=False,
     test_size=(640, 640), test_conf=0.01, nmsthre=0.65,
+    store_events='dat',      # not the reference's: how a window store of train_input = 'dat_store' keeps its records (data.STORE_EVENTS)
 )
 
 
@@ -191,6 +192,7 @@ class EventExp(BaseExp):
             return SyntheticStackedHistLoader(self, batch_size)
         if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
             # ``store_records`` = 'windows': the store keeps only the records its samples read (data.gen1_store_for; the evaluation store too)
+            # ``store_events`` = 'packed' (with 'windows'): those records in packed form, 4 bytes per event where exact
             from eas_snn_amd.data import Gen1StoreLoader
             return Gen1StoreLoader(self, batch_size, **ranks)
         if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)

@@ -4,7 +4,8 @@
 // One thread handles 4 consecutive events (16-B / 8-B / 8-B / 4-B vector loads); the atomics are
 // int32 `global_atomic_add` without return, so results are bit-exact and order independent.
 // Every source (decoded arrays, .dat records with offsets, .dat record ranges) sends an event to its bin, a count or a latest time, by one route:
-// bin_event<Acc> (event_bin.h).  Record ranges: one walk, dat_ranges_kernel<Acc>, behind one host template, dat_ranges_frames<Acc>.
+// bin_event<Acc> (event_bin.h).  Record ranges: one walk, dat_ranges_kernel<Acc, Src>, behind one host template, ranges_frames<Acc, Src>
+// (Src, record_source.h: the 8-byte records or the packed records of records.hip).
 #include <stdlib.h>
 
 #include <string.h>
@@ -12,6 +13,7 @@
 #include "eas_common.h"
 #include "count_resize.h"
 #include "event_bin.h"
+#include "record_source.h"
 #include "latest_surface.h"
 
 namespace {
@@ -188,28 +190,36 @@ __global__ __launch_bounds__(EAS_WAVE) void event_window_search_kernel(const uin
 }
 
 // Samples given as arbitrary (possibly overlapping) record ranges of a .dat image: blockIdx.y = sample, blocks stride over its range; nothing
-// is read back.  ``Acc`` (event_bin.h) is the only difference between the entries: CountAcc -> micro-slice count frames, LatestAcc -> the
-// latest times in the output's own 64-bit bins (eas_event_latest_surface_dat_ranges, finished by latest_finish_kernel).
-template <typename Acc>
-__global__ __launch_bounds__(EAS_BLOCK) void dat_ranges_kernel(const uint2* __restrict__ rec, const int64_t* __restrict__ ranges, int ns, int H,
-                                                               int W, typename Acc::Bin* __restrict__ out, uint32_t* __restrict__ oob,
-                                                               const Acc acc) {
+// is read back.  ``Acc`` (event_bin.h) is the difference between the frames: CountAcc -> micro-slice count frames, LatestAcc -> the latest
+// times in the output's own 64-bit bins (eas_event_latest_surface_*_ranges, finished by latest_finish_kernel).  ``Src`` (record_source.h)
+// is where record i comes from: RawRecords -> the 8-byte records (the _dat_ranges entries), PackedRecords -> the packed records (the
+// _packed_ranges entries).  The window of a range is the one rule for the walk and for the finishing pass (RangesWin).
+template <typename Src>
+__device__ __forceinline__ SampleWin ranges_window(const Src& src, int64_t a, int64_t e, int ns) {
+    RecEvent first, last;
+    if (!src.admit(a, e) || !src.load(a, first) || !src.load(e - 1, last)) return SampleWin{0u, 0u};
+    return make_window(first.t, last.t, ns);
+}
+
+template <typename Acc, typename Src>
+__global__ __launch_bounds__(EAS_BLOCK) void dat_ranges_kernel(const Src src, const int64_t* __restrict__ ranges, int ns, int H, int W,
+                                                               typename Acc::Bin* __restrict__ out, uint32_t* __restrict__ oob, const Acc acc) {
     const int b = blockIdx.y;
     const int64_t a = ranges[2 * b], e = ranges[2 * b + 1];
-    if (e <= a) return;
-    const SampleWin w = make_window(rec[a].x, rec[e - 1].x, ns);
+    const SampleWin w = ranges_window(src, a, e, ns);
+    if (w.win == 0) return;                        // (empty, refused, or a window of zero length: bin_event would drop every event)
     for (int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint2 v = rec[i];
-        bin_event(v.x, v.y & 16383u, (v.y >> 14) & 16383u, (v.y >> 28) & 1u, w, b, ns, H, W, out, oob, acc);
+        RecEvent v;
+        if (src.load(i, v)) bin_event(v.t, v.x, v.y, v.p, w, b, ns, H, W, out, oob, acc);
     }
 }
 
 // the window of sample b of such ranges, for the finishing pass (latest_surface.h latest_finish_kernel)
-struct DatRangesWin {
-    const uint2* rec; const int64_t* ranges; int ns;
+template <typename Src>
+struct RangesWin {
+    Src src; const int64_t* ranges; int ns;
     __device__ __forceinline__ void operator()(int b, uint32_t& t0, uint32_t& win) const {
-        const uint2* r = rec;
-        const SampleWin w = sample_window_of(ranges[2 * b], ranges[2 * b + 1], [r](int64_t i) { return r[i].x; }, ns);
+        const SampleWin w = ranges_window(src, ranges[2 * b], ranges[2 * b + 1], ns);
         t0 = w.t0;
         win = w.win;
     }
@@ -671,18 +681,60 @@ int histogram_impl(const uint32_t* t, const uint16_t* x, const uint16_t* y, cons
     return EAS_OK;
 }
 
-// The two entries for record ranges: one argument rule, the bins zeroed, one launch.  The ranges live on the device (no host read): a fixed
-// number of blocks per sample strides over whatever it holds; the sample is a block's y index, hence the bound on B.
-template <typename Acc>
-int dat_ranges_frames(const void* records, const int64_t* ranges, int B, int ns, int H, int W, typename Acc::Bin* out, uint32_t* oob_count,
-                      const Acc& acc, hipStream_t st) {
-    if (!records || !ranges || !out || B < 1 || ns < 1 || H < 1 || W < 1 || ((uintptr_t)records & 7)) return EAS_ERR_INVALID_ARG;
+// The entries for record ranges: one argument rule, the bins (and the words the walk counts and flags in) zeroed, one launch.  The ranges
+// live on the device (no host read): a fixed number of blocks per sample strides over whatever it holds; the sample is a block's y index,
+// hence the bound on B.  ``src_ok``: what the source's own arguments came to (raw_source / packed_source below).
+static inline uint32_t* source_flags(const RawRecords&) { return nullptr; }
+static inline uint32_t* source_flags(const PackedRecords& src) { return src.flags; }
+static inline RawRecords without_flags(const RawRecords& src) { return src; }
+static inline PackedRecords without_flags(PackedRecords src) {
+    src.flags = nullptr;
+    return src;
+}
+
+template <typename Acc, typename Src>
+int ranges_frames(const Src& src, int src_ok, const int64_t* ranges, int B, int ns, int H, int W, typename Acc::Bin* out, uint32_t* oob_count,
+                  const Acc& acc, hipStream_t st) {
+    if (src_ok == EAS_ERR_INVALID_ARG || !ranges || !out || B < 1 || ns < 1 || H < 1 || W < 1) return EAS_ERR_INVALID_ARG;
+    if (src_ok != EAS_OK) return src_ok;
     if (B > 65535) return EAS_ERR_UNSUPPORTED;
     EAS_CLEAR_ERR();
     if (!zero_counts((int32_t*)out, (size_t)B * ns * 2 * H * W * sizeof(typename Acc::Bin), oob_count, st)) return EAS_ERR_LAUNCH;
-    EAS_LAUNCH(dat_ranges_kernel<Acc>, dim3(64, B), dim3(EAS_BLOCK), 0, st, (const uint2*)records, ranges, ns, H, W, out, oob_count, acc);
+    if (!zero_counts(nullptr, 0, source_flags(src), st)) return EAS_ERR_LAUNCH;          // the flags are written by a call, not accumulated
+    EAS_LAUNCH((dat_ranges_kernel<Acc, Src>), dim3(64, B), dim3(EAS_BLOCK), 0, st, src, ranges, ns, H, W, out, oob_count, acc);
     EAS_CHECK_LAUNCH();
     return EAS_OK;
+}
+
+// the time surfaces: the walk into the output's own bins, then the finishing pass in place (it finds the windows again, without flagging
+// what the walk has flagged)
+template <typename Src>
+int ranges_surfaces(const Src& src, int src_ok, const int64_t* ranges, int B, int num_slices, int H, int W, double tau, double* out,
+                    uint32_t* oob_count, hipStream_t st) {
+    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;  // also NaN
+    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
+    const int launched = ranges_frames(src, src_ok, ranges, B, num_slices, H, W, bins, oob_count, LatestAcc{}, st);
+    if (launched != EAS_OK) return launched;
+    EAS_LAUNCH(latest_finish_kernel<RangesWin<Src>>, dim3(eas_grid_1d((int64_t)B * 2 * H * W)), dim3(EAS_BLOCK), 0, st, (int64_t)B, num_slices, H,
+               W, tau, bins, RangesWin<Src>{without_flags(src), ranges, num_slices});
+    EAS_CHECK_LAUNCH();
+    return EAS_OK;
+}
+
+int raw_source(const void* records, RawRecords& src) {
+    src = RawRecords{(const uint2*)records};
+    return !records || ((uintptr_t)records & 7) ? EAS_ERR_INVALID_ARG : EAS_OK;
+}
+
+// table [nb][2] and payload [units] of packed records (record_source.h) as a source
+int packed_source(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, int H, int W, uint32_t* flags, PackedRecords& src) {
+    RecWidths w = {1, 1, 29};
+    const bool geometry = rec_widths(H, W, w);
+    src = PackedRecords{(const uint2*)table, payload, nb, units, w.xb, w.yb, flags};
+    if (nb < 0 || units < 0 || (nb > 0 && !table) || (units > 0 && !payload) || units > ((int64_t)1 << 31) || H < 1 || W < 1)
+        return EAS_ERR_INVALID_ARG;                // (a store that holds nothing: no table, no payload, every range empty or refused)
+    if (((uintptr_t)table & 7) || ((uintptr_t)payload & 15) || ((uintptr_t)flags & 3)) return EAS_ERR_INVALID_ARG;
+    return geometry ? EAS_OK : EAS_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -718,20 +770,31 @@ int eas_event_window_search(const void* records, const int64_t* file_offsets, in
 
 int eas_event_histogram_dat_ranges(const void* records, const int64_t* ranges, int B, int Tm, int H, int W, int32_t* out, uint32_t* oob_count,
                                    eas_stream_t stream) {
-    return dat_ranges_frames(records, ranges, B, Tm, H, W, out, oob_count, CountAcc{}, eas_s(stream));
+    RawRecords src;
+    const int ok = raw_source(records, src);
+    return ranges_frames(src, ok, ranges, B, Tm, H, W, out, oob_count, CountAcc{}, eas_s(stream));
 }
 
 int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* ranges, int B, int num_slices, int H, int W, double tau, double* out,
                                         uint32_t* oob_count, eas_stream_t stream) {
-    if (!(tau > 0.0)) return EAS_ERR_INVALID_ARG;  // also NaN
-    hipStream_t st = eas_s(stream);
-    unsigned long long* bins = reinterpret_cast<unsigned long long*>(out);
-    const int launched = dat_ranges_frames(records, ranges, B, num_slices, H, W, bins, oob_count, LatestAcc{}, st);
-    if (launched != EAS_OK) return launched;
-    EAS_LAUNCH(latest_finish_kernel<DatRangesWin>, dim3(eas_grid_1d((int64_t)B * 2 * H * W)), dim3(EAS_BLOCK), 0, st, (int64_t)B, num_slices, H, W,
-               tau, bins, DatRangesWin{(const uint2*)records, ranges, num_slices});
-    EAS_CHECK_LAUNCH();
-    return EAS_OK;
+    RawRecords src;
+    const int ok = raw_source(records, src);
+    return ranges_surfaces(src, ok, ranges, B, num_slices, H, W, tau, out, oob_count, eas_s(stream));
+}
+
+int eas_event_histogram_packed_ranges(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, const int64_t* ranges, int B,
+                                      int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, eas_stream_t stream) {
+    PackedRecords src;
+    const int ok = packed_source(table, nb, payload, units, H, W, flags, src);
+    return ranges_frames(src, ok, ranges, B, Tm, H, W, out, oob_count, CountAcc{}, eas_s(stream));
+}
+
+int eas_event_latest_surface_packed_ranges(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, const int64_t* ranges, int B,
+                                           int num_slices, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags,
+                                           eas_stream_t stream) {
+    PackedRecords src;
+    const int ok = packed_source(table, nb, payload, units, H, W, flags, src);
+    return ranges_surfaces(src, ok, ranges, B, num_slices, H, W, tau, out, oob_count, eas_s(stream));
 }
 
 int eas_counts_to_canvas(const int32_t* counts, int64_t F, int H, int W, int Hc, int Wc, float* out,

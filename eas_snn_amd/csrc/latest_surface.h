@@ -44,8 +44,8 @@ __device__ __forceinline__ void surface_walk_in_place(unsigned long long* bins, 
 }
 
 // The finishing pass of the record entries, in place over bins [rows][ns][2][H][W]: one thread per (row, polarity, pixel), adjacent lanes on
-// adjacent pixels, the ns micro slices 2 * H * W bins apart.  ``win(row, t0, w)`` gives a row's first time and micro window: DatRangesWin
-// (events.hip; row = sample: its range's two record times, (0, 0) when empty) or AtisSliceWin (events_atis.hip; row = the plan's AtisSlice).
+// adjacent pixels, the ns micro slices 2 * H * W bins apart.  ``win(row, t0, w)`` gives a row's first time and micro window: RangesWin<Src>
+// (events.hip; row = sample: its range's two record times, from the 8-byte or the packed records, window 0 when empty) or AtisSliceWin (events_atis.hip; row = the plan's AtisSlice).
 template <typename RowWin>
 __global__ __launch_bounds__(EAS_BLOCK) void latest_finish_kernel(int64_t nrows, int ns, int H, int W, double tau, unsigned long long* __restrict__ bins,
                                                                   const RowWin win) {

@@ -469,6 +469,19 @@ def dat_ranges_to_frames(records, ranges, Tm, sensor_hw, canvas_hw, params, aggr
     return _letterboxed(frames, params, canvas_hw).unsqueeze(1)
 
 
+def packed_ranges_to_frames(table, payload, ranges, Tm, sensor_hw, canvas_hw, params, aggregation='micro_sum', tau=50e3):
+    """``dat_ranges_to_frames`` on packed records: ``table`` / ``payload`` of ``ops.records_pack`` and ranges int64 [B, 2] of logical record
+    indices -> model input [B, 1, Tm, 2, Hc, Wc] fp32, bit-identical to ``dat_ranges_to_frames`` on the records that were packed; nothing
+    read back in between (graph-capturable).  The operators are ``ops.event_histogram_packed_ranges`` /
+    ``ops.event_latest_surface_packed_ranges``; everything else is that function's."""
+    H, W = sensor_hw
+    if check_aggregation(aggregation) == 'timesurface':
+        frames = ops.event_latest_surface_packed_ranges(table, payload, ranges, Tm, H, W, tau=tau)
+    else:
+        frames = ops.event_histogram_packed_ranges(table, payload, ranges, Tm, H, W)
+    return _letterboxed(frames, params, canvas_hw).unsqueeze(1)
+
+
 # ------------------------------------------------------------------------------------------------ stores on N ranks
 STORE_SHARD = ('none', 'recordings')        # ``exp.store_shard``: every rank holds every record / a rank holds the records of its own recordings
 
@@ -835,15 +848,10 @@ class Gen1WindowStore(Gen1Store):
                 mine = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)[0]
                 source_bytes = sum(len(dat) for name, dat, _ in recordings if mine is None or name in mine)
             capacity_bytes = self._default_capacity(source_bytes)
-        self.capacity_bytes = int(capacity_bytes) // 8 * 8
-        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+        self._open_arena(int(capacity_bytes))
         self.total_records, self.kept_records, self._needed_records, self._ranges = 0, 0, 0, []
         self._scan(recordings, ignore, self._compact, owned, shard)
-        needed, self.used_bytes = self._needed_records * 8, self.kept_records * 8
-        if needed > self.capacity_bytes:
-            del self._arena
-            raise ValueError(f'the windows of these recordings need {needed} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
-        self.records = self._arena[:self.used_bytes]
+        self._close_arena()
         ranges, self._ranges = self._ranges, None
         if self.sharded:                                                # the rows of the owned samples, in their order; the others stay empty
             self.sample_ranges = torch.zeros((len(self.sample_names), self.Tl, 2), dtype=torch.int64, device=self.device)
@@ -853,15 +861,27 @@ class Gen1WindowStore(Gen1Store):
             self.sample_ranges = torch.cat(ranges) if ranges else torch.zeros((0, self.Tl, 2), dtype=torch.int64, device=self.device)
         self._upload_tables()
 
+    def _open_arena(self, capacity_bytes):
+        self.capacity_bytes = capacity_bytes // 8 * 8
+        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+
+    def _close_arena(self):
+        """after the scan: ``used_bytes`` and the view of the arena that holds the records, or the ValueError of an arena too small"""
+        needed, self.used_bytes = self._needed_records * 8, self.kept_records * 8
+        if needed > self.capacity_bytes:
+            del self._arena
+            raise ValueError(f'the windows of these recordings need {needed} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
+        self.records = self._arena[:self.used_bytes]
+
     def _default_capacity(self, source_bytes):
         free = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if self.device.type == 'cuda' else None
         if free is None and source_bytes is None:
             raise ValueError('capacity_bytes (or source_bytes) must be given where the free device memory cannot be asked for')
         return min(v for v in (free, source_bytes) if v is not None)
 
-    def _window_ranges(self, area, times):
-        """(ranges int64 [G * Tl, 2] into the arena from record 0 of this recording's kept area, records kept): the device steps of one
-        recording, up to the gather.  ``area``: the record area (uint8, host), not empty; ``times``: its label-group times."""
+    def _window_union(self, area, times):
+        """(the recording on the device, segments, seg_dst, mapped): upload, ``ops.event_window_search`` for every label group x ``Tl``
+        windows, ``ops.record_ranges_union``.  ``area``: the record area (uint8, host), not empty; ``times``: its label-group times."""
         import warnings
         with warnings.catch_warnings():
             warnings.simplefilter('ignore', UserWarning)                # a read-only host array is only read
@@ -870,7 +890,12 @@ class Gen1WindowStore(Gen1Store):
         shift = torch.arange(-self.Tl + 1, 1, dtype=torch.int64, device=self.device) * step
         t = (torch.from_numpy(times).to(self.device)[:, None] + shift[None, :]).reshape(-1)
         ranges = ops.event_window_search(rec, t, self.window, self.Tl)
-        segments, seg_dst, mapped = ops.record_ranges_union(ranges)
+        return (rec,) + ops.record_ranges_union(ranges)
+
+    def _window_ranges(self, area, times):
+        """(ranges int64 [G * Tl, 2] into the arena from record 0 of this recording's kept area, records kept): the device steps of one
+        recording, up to the gather"""
+        rec, segments, seg_dst, mapped = self._window_union(area, times)
         kept = int(seg_dst[-1])
         if self._needed_records + kept <= self.capacity_bytes // 8:
             ops.records_gather(rec, segments, seg_dst, self._arena, self.kept_records)
@@ -926,12 +951,105 @@ class Gen1WindowStore(Gen1Store):
         B, Tl = sample_idx.numel(), self.Tl
         par = params_on(params, self.device)[:, None, :].expand(B, Tl, 5).reshape(-1, 5)
         Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
-        out = dat_ranges_to_frames(self.records, self.sample_ranges[sample_idx].reshape(-1, 2), exp.Tm, self.sensor_hw, (Hc, Wc), par,
-                                   aggregation=exp_aggregation(exp))
+        out = self._frames_from(self.sample_ranges[sample_idx].reshape(-1, 2), exp.Tm, (Hc, Wc), par, exp_aggregation(exp))
         return out.reshape(B, Tl, exp.Tm, 2, Hc, Wc)
+
+    def _frames_from(self, ranges, Tm, canvas_hw, params, aggregation):
+        return dat_ranges_to_frames(self.records, ranges, Tm, self.sensor_hw, canvas_hw, params, aggregation=aggregation)
+
+
+class Gen1PackedWindowStore(Gen1WindowStore):
+    """``Gen1WindowStore`` with the kept records in packed form (include/eas_hip.h states the format): blocks of 64 records, a narrow
+    block -- coordinates inside the sensor, times within ``2^DB - 1`` us of the block's minimum; DB = 14 on Gen1 -- as 64 words of 4 bytes,
+    any other block as its 64 records.  ``table`` int32 [NB, 2] (the bit patterns of base time and unit | wide << 31), ``payload`` uint8
+    [used_bytes]; ``records`` stays None.  The frames are bit-identical to the parent's (``packed_ranges_to_frames``: the parent's range
+    kernels with the packed records as their source); tables, names, ``raw_labels``, ``targets``, ``owned`` / ``shard`` and
+    ``from_directories`` are the parent's.
+
+    The build, per recording, is the parent's up to the gather, which goes into a scratch of that recording's kept records;
+    ``ops.records_pack`` packs the scratch behind the arena's current unit.  Every recording starts on a fresh block: ``sample_ranges`` and
+    ``file_offsets`` are LOGICAL record indices (block * 64 + lane), and the padding behind a recording's last record lies in no range.
+    The device holds the arena, the table, one recording and that recording's kept records.  ``capacity_bytes``: the arena's size (None:
+    the parent's rule -- the source's size bounds what any packing needs up to 512 bytes per recording); the table is allocated beside it,
+    8 bytes per 256 of the arena.  An arena that is too small raises ValueError naming the bytes needed, after everything was measured.
+    ``used_bytes``: the payload in use; ``nbytes()``: payload + table; ``narrow_blocks`` / ``wide_blocks``; ``kept_records`` and
+    ``total_records`` count records as the parent does; ``unpacked(a, e)``: logical records [a, e) as 8-byte records; ``trim()`` gives the
+    rest of the arena and of the table back.  A sensor that leaves fewer than 8 bits for the time raises ValueError."""
+
+    def _open_arena(self, capacity_bytes):
+        ops.records_widths(*self.sensor_hw)
+        self.records = None
+        self.capacity_bytes = capacity_bytes // ops.RECORDS_UNIT * ops.RECORDS_UNIT
+        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+        self._table = torch.empty((self.capacity_bytes // ops.RECORDS_UNIT, 2), dtype=torch.int32, device=self.device)  # a block takes a unit at least
+        self._blocks, self._units, self._needed_units, self._full = 0, 0, 0, False
+
+    def _window_ranges(self, area, times):
+        """(ranges int64 [G * Tl, 2] of logical records from this recording's first block, records kept, blocks taken)"""
+        rec, segments, seg_dst, mapped = self._window_union(area, times)
+        kept = int(seg_dst[-1])
+        if kept == 0:
+            return mapped, 0, 0
+        scratch = torch.empty(8 * kept, dtype=torch.uint8, device=self.device)
+        ops.records_gather(rec, segments, seg_dst, scratch)
+        nb = (kept + ops.RECORDS_BLOCK - 1) // ops.RECORDS_BLOCK
+        full = self._full or self._blocks + nb > self._table.shape[0]      # (more blocks than the arena has units: it cannot take them either)
+        table = torch.empty((nb, 2), dtype=torch.int32, device=self.device) if full else self._table[self._blocks:self._blocks + nb]
+        try:
+            took = ops.records_pack(scratch, table, self._arena, self._units, *self.sensor_hw, dry_run=full)
+        except ops.PackedArenaFull as e:                                    # too small: go on measuring, store nothing more
+            took, full = e.units, True
+        self._full = full
+        self._needed_units += took
+        self._units += 0 if self._full else took
+        return mapped, kept, nb
+
+    def _compact(self, area, times):
+        self.total_records += len(area) // 8
+        if len(times) == 0:
+            return 0
+        if len(area) == 0:                                              # no events: every window is empty
+            mapped, kept, nb = torch.zeros((len(times) * self.Tl, 2), dtype=torch.int64, device=self.device), 0, 0
+        else:
+            mapped, kept, nb = self._window_ranges(area, np.ascontiguousarray(times, dtype=np.int64))
+        if self._full:
+            return 0
+        self._ranges.append((mapped + self._blocks * ops.RECORDS_BLOCK).reshape(len(times), self.Tl, 2))
+        self._blocks += nb
+        self.kept_records += kept
+        return nb * ops.RECORDS_BLOCK
+
+    def _close_arena(self):
+        if self._full:
+            del self._arena, self._table
+            raise ValueError(f'the packed records of these recordings need {self._needed_units * ops.RECORDS_UNIT} bytes, the arena holds '
+                             f'{self.capacity_bytes} (capacity_bytes)')
+        self.used_bytes = self._units * ops.RECORDS_UNIT
+        self.payload, self.table = self._arena[:self.used_bytes], self._table[:self._blocks]
+        self.wide_blocks = self._units - self._blocks                   # a narrow block takes one unit, a wide block two
+        self.narrow_blocks = self._blocks - self.wide_blocks
+
+    def nbytes(self):
+        """bytes of the payload in use and of the table"""
+        return self.used_bytes + self.table.numel() * 4
+
+    def trim(self):
+        """reallocate ``payload`` and ``table`` to the used size and let the arena go (old and new exist side by side for the time of the copy)"""
+        if self.capacity_bytes != self.used_bytes:
+            self.payload, self.table = self.payload.clone(), self.table.clone()
+            self._arena, self._table, self.capacity_bytes = self.payload, self.table, self.used_bytes
+        return self
+
+    def unpacked(self, a, e):
+        """uint8 [8 * (e - a)]: the logical records ``a`` .. ``e`` as the parent holds them (8-byte records)"""
+        return ops.records_unpack(self.table, self.payload, a, e, *self.sensor_hw)
+
+    def _frames_from(self, ranges, Tm, canvas_hw, params, aggregation):
+        return packed_ranges_to_frames(self.table, self.payload, ranges, Tm, self.sensor_hw, canvas_hw, params, aggregation=aggregation)
 
 
 STORE_RECORDS = ('all', 'windows')          # ``exp.store_records``: every record of the recordings (Gen1Store) / those the samples read
+STORE_EVENTS = ('dat', 'packed')            # ``exp.store_events``: the kept records as 8-byte .dat records / packed (Gen1PackedWindowStore)
 
 
 def gen1_store_for(exp, split='train', device=None):
@@ -939,14 +1057,20 @@ def gen1_store_for(exp, split='train', device=None):
     (``split='test'``: /test) when that directory exists, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files, labels
     per file, events per file), default (4, 16, 50000); the sensor is Gen1's, or the canvas where that is smaller).  ``exp.store_records``
     (default ``'all'``) = ``'windows'``: a ``Gen1WindowStore``, trimmed; any other value raises ValueError.  ``exp.store_shard`` =
-    ``'recordings'``: the store of this rank (``shard=`` of ``from_directories`` / of the constructor for the synthetic recordings).  Kept
-    on the experiment: one store per (split, rank, world, store_shard)."""
+    ``'recordings'``: the store of this rank (``shard=`` of ``from_directories`` / of the constructor for the synthetic recordings).
+    ``exp.store_events`` (default ``'dat'``) = ``'packed'`` with ``store_records = 'windows'``: a ``Gen1PackedWindowStore``, trimmed;
+    ``'packed'`` with ``store_records = 'all'``, or any other value, raises ValueError before any device work.  Kept on the experiment: one
+    store per (split, rank, world, store_shard), the three kinds of store apart."""
     import os
-    kind = getattr(exp, 'store_records', 'all')
+    kind, events = getattr(exp, 'store_records', 'all'), getattr(exp, 'store_events', 'dat')
     if kind not in STORE_RECORDS:
         raise ValueError(f'store_records must be one of {STORE_RECORDS}, got {kind!r}')
-    cls = Gen1WindowStore if kind == 'windows' else Gen1Store
-    cache = exp.__dict__.setdefault('_dat_stores' if kind == 'all' else '_dat_window_stores', {})
+    if events not in STORE_EVENTS:
+        raise ValueError(f'store_events must be one of {STORE_EVENTS}, got {events!r}')
+    if events == 'packed' and kind != 'windows':
+        raise ValueError(f"store_events = 'packed' packs the records a window store keeps: it needs store_records = 'windows', got {kind!r}")
+    cls = (Gen1PackedWindowStore if events == 'packed' else Gen1WindowStore) if kind == 'windows' else Gen1Store
+    cache = exp.__dict__.setdefault('_dat_stores' if kind == 'all' else '_dat_packed_stores' if events == 'packed' else '_dat_window_stores', {})
     shard = exp_store_shard(exp)
     split, name = _store_key(exp, split), split
     if split not in cache:

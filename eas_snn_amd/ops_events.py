@@ -450,6 +450,117 @@ def packed_store_frames(table, payload, first, Tm, Hc, Wc, lo=None, params=None,
     return (out, flags) if return_flags else out
 
 
+RECORDS_BLOCK, RECORDS_UNIT = 64, 256       # records per block of the packed records; bytes per payload unit (narrow block: 1, wide: 2)
+RECORDS_FLAG_RANGE, RECORDS_FLAG_TABLE = 1, 2       # flag bits of the packed-range operators: a refused range / a table entry outside the payload
+
+
+def records_widths(H, W):
+    """(XB, YB, DB) of packed records on an ``H`` x ``W`` sensor: bits of W - 1 and of H - 1 (each at least 1) and what 31 bits leave for the
+    time offset inside a block; ValueError where that is fewer than 8 bits or a side exceeds the record's 14-bit fields"""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f'a sensor of {H} x {W}')
+    xb, yb = max((W - 1).bit_length(), 1), max((H - 1).bit_length(), 1)
+    if 31 - xb - yb < 8 or H > 16384 or W > 16384:
+        raise ValueError(f'packed records: a sensor of {H} x {W} takes {xb} + {yb} bits and leaves {31 - xb - yb} for the time (8 at least)')
+    return xb, yb, 31 - xb - yb
+
+
+def _packed_records_args(table, payload):
+    """the shapes and types of a packed store; returns (blocks, units)"""
+    _dev(table, payload)
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 2 and table.is_contiguous()
+    assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous() and payload.device == table.device
+    return table.shape[0], payload.numel() // RECORDS_UNIT
+
+
+def records_pack(records, table_out, payload, unit_offset, H, W, dry_run=False):
+    """Packs the 8-byte records ``records`` (uint8 [8 * n] or any 8-byte-record view, on the device) in blocks of 64 -- a narrow block 256
+    bytes, a wide block 512 (include/eas_hip.h states the format) -- behind unit ``unit_offset`` (units of 256 bytes) of the arena
+    ``payload`` (uint8 [capacity], 16-byte aligned), and fills ``table_out`` int32 [ceil(n / 64), 2] = the bit patterns of (base time, unit |
+    wide << 31) -- a contiguous view into a table allocated once.  Three steps: ``eas_records_pack_measure`` (base and units of every block),
+    an exclusive scan of the units on the device plus ``unit_offset``, ``eas_records_pack``.  The records behind record n - 1 in the last
+    block are copies of it.  Returns the units used: the one value a call reads back.  An arena that cannot take them raises
+    ``PackedArenaFull`` (a ValueError that names the bytes needed) before anything is written to it; ``dry_run``: measure and fill the table
+    only, the arena is neither checked nor written.  A sensor that leaves fewer than 8 bits for the time raises ValueError."""
+    records_widths(H, W)
+    _dev(records)
+    rec = records.view(torch.uint8)
+    assert records.is_contiguous() and rec.dim() == 1 and rec.numel() % 8 == 0, 'records are 8 bytes'
+    n, unit_offset = rec.numel() // 8, int(unit_offset)
+    nb = (n + RECORDS_BLOCK - 1) // RECORDS_BLOCK
+    _packed_records_args(table_out, payload)
+    assert table_out.shape[0] == nb and table_out.device == rec.device and unit_offset >= 0
+    if n == 0:
+        return 0
+    _call('eas_records_pack_measure', 8 * n + 8 * nb, _lib.lib().eas_records_pack_measure, ptr(rec), n, int(H), int(W), ptr(table_out), stream())
+    second = table_out[:, 1]
+    ends = torch.cumsum(second, 0, dtype=torch.int64)
+    units = int(ends[-1])                                      # (the read of a build step)
+    if unit_offset + units > 1 << 31:
+        raise ValueError(f'packed records: unit {unit_offset + units} is beyond the 2^31 units (512 GB) a table addresses')
+    # the place, and the wide flag in bit 31: as int32, place - 2^31
+    second.copy_(ends - second + unit_offset - (second == 2).to(torch.int64) * (1 << 31))
+    if dry_run:
+        return units
+    if (unit_offset + units) * RECORDS_UNIT > payload.numel():
+        raise PackedArenaFull(f'the packed records need {(unit_offset + units) * RECORDS_UNIT} bytes, the arena holds {payload.numel()}', units)
+    _call('eas_records_pack', 8 * n + 8 * nb + RECORDS_UNIT * units, _lib.lib().eas_records_pack, ptr(rec), n, int(H), int(W), ptr(table_out),
+          ptr(payload), unit_offset, unit_offset + units, stream())
+    return units
+
+
+def records_unpack(table, payload, a, e, H, W, return_flags=False):
+    """The inverse of ``records_pack``: the logical records [a, e) of the store ``table`` int32 [NB, 2] / ``payload`` uint8 [used bytes] as
+    8-byte records, uint8 [8 * (e - a)], byte for byte what was packed (padding included where the range covers it).  ``a < 0``, ``e < a``
+    or ``e > 64 * NB`` raises ValueError.  ``return_flags``: also int32 [1], bit 1 set when a table entry placed a block outside the payload
+    (those records come out as zeros)."""
+    records_widths(H, W)
+    nb, units = _packed_records_args(table, payload)
+    a, e = int(a), int(e)
+    if a < 0 or e < a or e > nb * RECORDS_BLOCK:
+        raise ValueError(f'records_unpack: [{a}, {e}) is no range of {nb * RECORDS_BLOCK} packed records')
+    out = torch.empty(8 * (e - a), dtype=torch.uint8, device=table.device)
+    flags = torch.zeros(1, dtype=torch.int32, device=table.device) if return_flags else None
+    if e > a:
+        _call('eas_records_unpack', 12 * (e - a), _lib.lib().eas_records_unpack, ptr(table), nb, ptr(payload), units, a, e, int(H), int(W), ptr(out),
+              ptr(flags), stream())
+    return (out, flags) if return_flags else out
+
+
+def _packed_ranges_frames(entry, dtype, out_bytes, table, payload, ranges, ns, H, W, tau, return_oob, return_flags):
+    """the two packed-range wrappers: checks, allocations, the call (``tau``: a tuple, empty for the counts) and the return tuple"""
+    records_widths(H, W)
+    nb, units = _packed_records_args(table, payload)
+    _dev(ranges)
+    assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2 and ranges.device == table.device
+    B = ranges.shape[0]
+    out = torch.empty((B, ns, 2, H, W), dtype=dtype, device=table.device)
+    oob = torch.empty(1, dtype=torch.int32, device=table.device) if return_oob else None
+    flags = torch.empty(1, dtype=torch.int32, device=table.device) if return_flags else None
+    # bytes: at most the table and the payload once + the frames
+    _call(entry, 8 * nb + RECORDS_UNIT * units + out_bytes * out.numel(), getattr(_lib.lib(), entry), ptr(table) if nb else None, nb,
+          ptr(payload) if units else None, units, ptr(ranges.contiguous()), B, ns, H, W, *tau, ptr(out), ptr(oob), ptr(flags), stream())
+    ret = (out,) + ((oob,) if return_oob else ()) + ((flags,) if return_flags else ())
+    return ret if len(ret) > 1 else out
+
+
+def event_histogram_packed_ranges(table, payload, ranges, Tm, H, W, return_oob=False, return_flags=False):
+    """``event_histogram_dat_ranges`` on packed records: ``table`` int32 [NB, 2] and ``payload`` uint8 [used bytes] (``records_pack``),
+    ``ranges`` int64 [B, 2] of LOGICAL record indices -> count frames int32 [B, Tm, 2, H, W], bit-identical to ``event_histogram_dat_ranges``
+    on the records that were packed.  Nothing is read back (graph-capturable).  Optional returns, in this order: the events outside the
+    sensor that were dropped (int32 [1]); the flags (int32 [1], written by the call): bit 0 a range with a < 0, e > 64 * NB or e < a -- zero
+    frames --, bit 1 a table entry that places a block outside the payload -- its records are skipped."""
+    return _packed_ranges_frames('eas_event_histogram_packed_ranges', torch.int32, 4, table, payload, ranges, Tm, H, W, (), return_oob, return_flags)
+
+
+def event_latest_surface_packed_ranges(table, payload, ranges, num_slices, H, W, tau=50e3, return_oob=False, return_flags=False):
+    """``event_latest_surface_dat_ranges`` on packed records (the arguments and optional returns of ``event_histogram_packed_ranges``):
+    float64 [B, num_slices, 2, H, W], bit-identical to that operator on the records that were packed"""
+    return _packed_ranges_frames('eas_event_latest_surface_packed_ranges', torch.float64, 24, table, payload, ranges, num_slices, H, W,
+                                 (float(tau),), return_oob, return_flags)
+
+
 def label_targets(boxes, group_start, group, params, ih, iw, h, w, perm=None, max_labels=50, return_info=False):
     """The label side of a training batch from a box table in HBM: ``targets`` fp32 [B, max_labels, 5] rows (cls, cx, cy, w, h), zero padded --
     the box half of get_random_data (gen1.py:437, 459-468, 510-521), ``reformat('cxcywh')`` and EventTrainTransform for every sample in one

@@ -250,6 +250,45 @@ int eas_event_latest_surface_dat_ranges(const void* records, const int64_t* rang
  * answers for the segments lying inside src and dst.  Asynchronous on `stream`, no allocation.  A NULL pointer, a pointer that is not
  * 8-byte aligned, S < 1 or total < 0: EAS_ERR_INVALID_ARG before any HIP call; total == 0: EAS_OK, no launch.  A copy: bit-exact. */
 int eas_records_gather(const void* src, const int64_t* seg_src, const int64_t* seg_dst, int64_t S, int64_t total, void* dst, eas_stream_t stream);
+/* Such records in PACKED form (additive, ABI 9; data.Gen1PackedWindowStore): 4 bytes per event where that is exact.  The records are taken in
+ * blocks of 64 consecutive records, one per lane of a wave: logical record i lives in block i >> 6, lane i & 63.  Field widths from the
+ * sensor: XB = bits of W - 1, YB = bits of H - 1 (each at least 1), DB = 31 - XB - YB (Gen1, 240 x 304: 9 / 8 / 14); DB < 8, H or W above
+ * 16384 (the record's fields hold 14 bits): EAS_ERR_UNSUPPORTED.  A block is NARROW when every one of its records has x < 2^XB, y < 2^YB,
+ * bits 29-31 of its second word zero and t - base < 2^DB, base being the MINIMUM time of the block (not the first record's: a block may
+ * straddle two kept segments or two recordings, where time steps backwards).  A narrow block stores 64 little-endian words
+ *     x | y << XB | p << (XB + YB) | (t - base) << (XB + YB + 1)
+ * = 256 bytes; any other block is WIDE and stores its 64 records as they are, 512 bytes.  The records behind the last record of a pack
+ * call, in that call's last block, are padding that no range addresses: copies of the call's last record -- a copy of a record of the
+ * block moves neither the minimum nor any condition, so padding never turns a narrow block wide.
+ * table: uint32 [NB][2] = (base, unit | wide << 31), 8-byte aligned; a unit is 256 bytes of ``payload`` (16-byte aligned), a narrow block
+ * takes one and a wide block two, so 31 bits of unit address 512 GB.  Bounds: table + payload <= the raw records + 8 bytes per block (1.6 %)
+ * whatever the records hold, and exactly 264 bytes per block (0.516 of raw) when no block is wide.  Unpacking gives the records back byte
+ * for byte.
+ * eas_records_pack_measure: records [n] -> table[blk] = (base, units of the block: 1 or 2), NB = ceil(n / 64) entries, one wave per block
+ * (a wave-wide minimum and one ballot).  The caller turns the second word into places (an exclusive scan plus the unit reached, the wide
+ * flag in bit 31) and hands the table to eas_records_pack, which writes every block to its place and nothing outside units
+ * [unit_lo, unit_hi) of ``payload``: a block the table places outside them is not written.  It trusts the table for the class.
+ * eas_records_unpack: logical records [a, e) of a store of nb blocks and ``units`` payload units -> out, 8-byte records; a block whose table
+ * entry places it outside [0, units) is not read, comes out as zero records and sets bit 1 of flags[0] (uint32, nullable, written by the
+ * call).  n == 0 / e == a: EAS_OK, no kernel.  NULL or misaligned pointers, negative counts, a < 0, e < a, e > 64 * nb, unit_lo < 0,
+ * unit_hi < unit_lo, more than 2^31 units: EAS_ERR_INVALID_ARG before any HIP call. */
+int eas_records_pack_measure(const void* records, int64_t n, int H, int W, uint32_t* table, eas_stream_t stream);
+int eas_records_pack(const void* records, int64_t n, int H, int W, const uint32_t* table, uint8_t* payload, int64_t unit_lo, int64_t unit_hi,
+                     eas_stream_t stream);
+int eas_records_unpack(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, int64_t a, int64_t e, int H, int W, void* out,
+                       uint32_t* flags, eas_stream_t stream);
+/* eas_event_histogram_dat_ranges / eas_event_latest_surface_dat_ranges on packed records: ``ranges`` holds LOGICAL record indices into a
+ * store of nb blocks (table) and ``units`` payload units; out, oob_count, tau, the bound on B and every rule of the frames are those
+ * entries' (the same kernels with another record source), so the frames are bit-identical to theirs on the records that were packed.
+ * Everything that arrives as device data is bounded before it addresses memory: a range with a < 0, e > 64 * nb or e < a is walked as
+ * empty (zero frames) and sets bit 0 of flags[0]; a record whose table entry places its block outside [0, units) is skipped and sets bit 1
+ * (a range whose first or last record is such a record gives zero frames).  flags: uint32 [1], nullable, written by the call -- zeroed on
+ * the stream, then set -- never accumulated.  nb == 0 (units == 0) is a store that holds nothing: table and payload may be NULL. */
+int eas_event_histogram_packed_ranges(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, const int64_t* ranges, int B,
+                                      int Tm, int H, int W, int32_t* out, uint32_t* oob_count, uint32_t* flags, eas_stream_t stream);
+int eas_event_latest_surface_packed_ranges(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, const int64_t* ranges, int B,
+                                           int num_slices, int H, int W, double tau, double* out, uint32_t* oob_count, uint32_t* flags,
+                                           eas_stream_t stream);
 
 /* Config-4 input (BASELINE configs[3]): RVT stacked histogram -> per-polarity counts on the model canvas.  Replaces
  * RVTGEN4Dataset.generate_slices(..., method='event_sum') (yolox/data/datasets/rvt_gen4.py:109-125: reshape
