@@ -67,6 +67,12 @@ class EasConvProblem(C.Structure):
                 ('NI', C.c_int), ('Cin', C.c_int), ('Cout', C.c_int), ('Hi', C.c_int), ('Wi', C.c_int), ('accumulate', C.c_int)]
 
 
+class EasConvPlan(C.Structure):
+    """include/eas_hip.h EasConvPlan: the tile a 3x3 planner chose"""
+    _fields_ = [(k, C.c_int) for k in ('cand', 'wvm', 'wvn', 'wn', 'threads', 'vec', 'single', 'parts', 'RT', 'bpi', 'nseg', 'grid_x',
+                                       'grid_y', 'grid_z', 'lds_bytes')]
+
+
 class EasBnSiluFwdProblem(C.Structure):
     """include/eas_hip.h EasBnSiluFwdProblem"""
     _fields_ = [('y', C.c_void_p), ('mean', C.c_void_p), ('invstd', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p),
@@ -252,6 +258,9 @@ PROTOTYPES = {
     'eas_spp_pool_planes_bwd': (C.c_int, [_P, _P, _P, C.c_int64] + [C.c_int] * 6 + [_P]),
     'eas_conv_fwd_group_plan': (C.c_int, [C.POINTER(EasConvProblem), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'eas_conv_fwd_group': (C.c_int, [C.POINTER(EasConvProblem), C.c_int, C.c_int, C.c_int, _P]),
+    'eas_conv_fwd_plan': (C.c_int, [C.c_int] * 8 + [C.POINTER(EasConvPlan)]),
+    'eas_conv_dgrad_s2_plan': (C.c_int, [C.c_int] * 5 + [C.POINTER(EasConvPlan)]),
+    'eas_conv_fwd_group_tile_plan': (C.c_int, [C.POINTER(EasConvProblem), C.c_int, C.c_int, C.c_int, C.POINTER(EasConvPlan)]),
     'eas_bn_silu_fwd_group': (C.c_int, [C.POINTER(EasBnSiluFwdProblem), C.c_int, _P]),
     'eas_bn_silu_bwd_group': (C.c_int, [C.POINTER(EasBnSiluBwdProblem), C.c_int, _P]),
     'eas_conv_wgrad_group_plan': (C.c_int, [C.POINTER(EasWgradProblem), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -124,7 +124,7 @@ int plan_group3(const EasConvProblem* pr, int n, ConvGroupArgsT<G>& a, int& best
     for (int p = 0; p < n; ++p) {
         G& g = a.g[p];
         const int gxp = a.first[p + 1] - a.first[p];
-        conv_plan_note("group", best, a.vec2[p] ? 2 : 4, g, dim3(gxp, grid_y, a.first[n]), lds);
+        conv_plan_note("group", best, c.wvm, c.wvn, c.wn, a.vec2[p] ? 2 : 4, g, dim3(gxp, grid_y, a.first[n]), lds, p);
         if (nb_out) nb_out[p] = gxp;
         g.stats = pr[p].stats;
         g.stats_nb = gxp;
@@ -187,6 +187,15 @@ extern "C" {
 // blocks write (what EasConvProblem.stats must hold: Cout * nb * 2 doubles); EAS_ERR_UNSUPPORTED: run the problems one by one
 int eas_conv_fwd_group_plan(const EasConvProblem* problems, int n, int ksize, int x_terms, int* nb_out) {
     return conv_group_impl(problems, n, ksize, x_terms, nullptr, nb_out, true);
+}
+
+// include/eas_hip.h: the tile of a grouped 3x3 launch, out[p] = problem p's part of the plan as plan_group3 left it at its exit
+int eas_conv_fwd_group_tile_plan(const EasConvProblem* problems, int n, int ksize, int x_terms, EasConvPlan* out) {
+    if (!out) return EAS_ERR_INVALID_ARG;
+    if (ksize == 1) return EAS_ERR_UNSUPPORTED;          // (the 1x1 family: conv1x1_mfma.hip)
+    const int rc = conv_group_impl(problems, n, ksize, x_terms, nullptr, nullptr, true);
+    for (int p = 0; rc == EAS_OK && p < n; ++p) out[p] = tl_conv_plan[p];
+    return rc;
 }
 
 int eas_conv_fwd_group(const EasConvProblem* problems, int n, int ksize, int x_terms, eas_stream_t stream) {

@@ -59,7 +59,8 @@ int dispatch_tile_lif(const float* x, const bf16x8* wp, ConvGeom g, hipStream_t 
         }
     }
     if (best < 0) return EAS_ERR_UNSUPPORTED;
-    conv_plan_note(LM == 1 ? "lif time-major" : "lif shared", best, VEC, best_g, conv_tile_grid(best_g, cands[best].wvm), best_lds);
+    conv_plan_note(LM == 1 ? "lif time-major" : "lif shared", best, cands[best].wvm, cands[best].wvn, cands[best].wn, VEC, best_g,
+                   conv_tile_grid(best_g, cands[best].wvm), best_lds);
     if (query) return EAS_OK;
     return cands[best].fn(x, wp, nullptr, nullptr, nullptr, best_g, best_lds, st);
 }

@@ -345,4 +345,15 @@ int eas_conv_fwd_supported(int NI, int Cin, int Cout, int Hi, int Wi, int ksize,
     return conv_fwd_impl(nullptr, nullptr, nullptr, nullptr, NI, Cin, Cout, Hi, Wi, ksize, stride, x_terms, nullptr, nullptr, true) == EAS_OK ? 1 : 0;
 }
 
+// The tile eas_conv_fwd (x_terms 1 / 3) / eas_conv_fwd_planes (x_terms 2) launches for this 3x3 geometry, as dispatch_tile left it at its
+// exit (conv_plan_note): the status the launch would give, *out filled when it is EAS_OK.  Nothing is launched; needs no GPU.  The 1x1
+// family (conv1x1_mfma.hip) has launch rules of its own: EAS_ERR_UNSUPPORTED here.
+int eas_conv_fwd_plan(int NI, int Cin, int Cout, int Hi, int Wi, int ksize, int stride, int x_terms, EasConvPlan* out) {
+    if (!out) return EAS_ERR_INVALID_ARG;
+    if (ksize == 1) return EAS_ERR_UNSUPPORTED;
+    const int rc = conv_fwd_impl(nullptr, nullptr, nullptr, nullptr, NI, Cin, Cout, Hi, Wi, ksize, stride, x_terms, nullptr, nullptr, true);
+    if (rc == EAS_OK) *out = tl_conv_plan[0];
+    return rc;
+}
+
 }  // extern "C"

@@ -708,7 +708,17 @@ static int conv_launch_prep(const void* kern, bool& attr_set, ConvGeomCore& g, i
 }
 
 // development (EAS_CONV_PLAN): one line per planned tile, from the planners' common exit -- before a query returns, so without a GPU
-static void conv_plan_note(const char* who, int cand, int vec, const ConvGeomCore& g, const dim3& grid, size_t lds) {
+// and the same facts as plain ints for the plan queries (eas_conv_fwd_plan, eas_conv_dgrad_s2_plan, eas_conv_fwd_group_tile_plan): the
+// planner that ran last on this thread left its decision in tl_conv_plan[slot] (slot = the problem of a grouped plan, else 0) -- the
+// launch's own choice, carried like tl_pixel_blocks, not a second copy of the rule
+thread_local EasConvPlan tl_conv_plan[8] = {};      // (8: the most problems of a grouped launch, kMaxGroup of conv_group.hip)
+
+static void conv_plan_note(const char* who, int cand, int wvm, int wvn, int wn, int vec, const ConvGeomCore& g, const dim3& grid, size_t lds,
+                           int slot = 0) {
+    EasConvPlan& p = tl_conv_plan[slot];
+    p.cand = cand; p.wvm = wvm; p.wvn = wvn; p.wn = wn; p.threads = 64 * wvm * wvn; p.vec = vec;
+    p.single = g.single; p.parts = g.parts; p.RT = g.RT; p.bpi = g.bpi; p.nseg = g.nseg;
+    p.grid_x = (int)grid.x; p.grid_y = (int)grid.y; p.grid_z = (int)grid.z; p.lds_bytes = (int)lds;
     static const bool on = eas_dev_env("EAS_CONV_PLAN") != nullptr;
     if (on)
         fprintf(stderr, "conv plan %s: cand %d vec %d RT %d bpi %d nseg %d Q %d single %d parts %d grid %u %u %u lds %zu | rows %d/%d RS %d Wst %d gx0 %d "
@@ -806,7 +816,7 @@ int dispatch_tile(const float* x, const bf16x8* wp, const float* bias, float* y,
     if (best < 0) return EAS_ERR_UNSUPPORTED;
     const dim3 grid = conv_tile_grid(best_g, cands[best].wvm * cands[best].wm);
     tl_pixel_blocks = grid.x * best_g.parts;
-    conv_plan_note("fwd", best, VEC, best_g, grid, best_lds);
+    conv_plan_note("fwd", best, cands[best].wvm, cands[best].threads / (64 * cands[best].wvm), cands[best].wn, VEC, best_g, grid, best_lds);
     if (!y) return EAS_OK;                       // geometry query (eas_conv_fwd_supported): a tile exists, nothing is launched
     return cands[best].fn(x, wp, bias, y, inexact, best_g, best_lds, st);
 }

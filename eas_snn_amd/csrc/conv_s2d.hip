@@ -107,7 +107,7 @@ int dgrad_s2_plan(const float* gy, const void* packed_w, float* gx, int NI, int 
         }
     }
     if (best < 0) return EAS_ERR_UNSUPPORTED;
-    conv_plan_note("s2c", best, best_vec, best_g, conv_tile_grid(best_g, kS2c[best].wvm), best_lds);
+    conv_plan_note("s2c", best, kS2c[best].wvm, kS2c[best].wvn, kS2c[best].wn, best_vec, best_g, conv_tile_grid(best_g, kS2c[best].wvm), best_lds);
     if (query) return EAS_OK;
     const s2c_fn fn = best_vec == 4 ? kS2c[best].f4 : (best_vec == 2 ? kS2c[best].f2 : kS2c[best].f1);
     return fn(gy, (const bf16x8*)packed_w, gx, best_g, best_lds, st);
@@ -132,6 +132,14 @@ int eas_conv_dgrad_s2(const float* grad_y, const void* packed_w, float* grad_x, 
 int eas_conv_dgrad_s2_supported(int NI, int Cin, int Cout, int Hi, int Wi) {
     if (NI <= 0 || Cin <= 0 || Cout <= 0 || Hi <= 0 || Wi <= 0) return 0;
     return dgrad_s2_plan(nullptr, nullptr, nullptr, NI, Cin, Cout, Hi, Wi, nullptr, true) == EAS_OK ? 1 : 0;
+}
+
+// the tile eas_conv_dgrad_s2 launches for this geometry, as the plan left it at its exit: the launch's status, *out filled when EAS_OK
+int eas_conv_dgrad_s2_plan(int NI, int Cin, int Cout, int Hi, int Wi, EasConvPlan* out) {
+    if (!out || NI <= 0 || Cin <= 0 || Cout <= 0 || Hi <= 0 || Wi <= 0) return EAS_ERR_INVALID_ARG;
+    const int rc = dgrad_s2_plan(nullptr, nullptr, nullptr, NI, Cin, Cout, Hi, Wi, nullptr, true);
+    if (rc == EAS_OK) *out = tl_conv_plan[0];
+    return rc;
 }
 
 }  // extern "C"

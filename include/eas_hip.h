@@ -929,6 +929,32 @@ typedef struct {
 int eas_conv_fwd_group_plan(const EasConvProblem* problems, int n, int ksize, int x_terms, int* nb_out);
 int eas_conv_fwd_group(const EasConvProblem* problems, int n, int ksize, int x_terms, eas_stream_t stream);
 
+/* ---- Which tile a 3x3 geometry gets, without launching -------------------------------------------------------------------------------
+ * The tile planners of the 3x3 family (csrc/conv_mfma_body.h dispatch_tile, conv_s2d.hip, conv_group.hip) choose a kernel instance and its
+ * run-time form from the geometry alone.  These queries run the launch's own planner and hand back what it left at its exit: the return
+ * value is the status the launch would give (EAS_ERR_UNSUPPORTED: no tile), *out is filled when it is EAS_OK.  Nothing is launched and no
+ * GPU is needed.  The suite uses them to tie every compiled instance to a shape that reaches it (tests/conv3x3_cases.py).
+ *   eas_conv_fwd_plan:            eas_conv_fwd / eas_conv_fwd_stats / eas_conv_fwd_act (x_terms 1 / 3) and eas_conv_fwd_planes (x_terms 2),
+ *                                 ksize 3 (ksize 1, whose family has rules of its own in conv1x1_mfma.hip: EAS_ERR_UNSUPPORTED)
+ *   eas_conv_dgrad_s2_plan:       eas_conv_dgrad_s2
+ *   eas_conv_fwd_group_tile_plan: eas_conv_fwd_group with ksize 3; out[n], one entry per problem (the tile shape is the group's, rows and
+ *                                 staging width the problem's; grid_x = the problem's pixel tiles, grid_y the group's, grid_z = the
+ *                                 launch's whole grid.x) */
+typedef struct {
+    int cand;                  /* index in the planner's candidate table */
+    int wvm, wvn, wn;          /* waves along the channels, waves along the pixels, 32-pixel tiles per wave */
+    int threads;               /* 64 * wvm * wvn */
+    int vec;                   /* staging width in pixels: 4, 2 or (stride-2 input gradient) 1 */
+    int single;                /* 1: one LDS buffer for the staged patch although there are several channel chunks */
+    int parts;                 /* column parts of a row: 1, 2, 4, 8 */
+    int RT, bpi, nseg;         /* rows per tile; tiles per image (ragged tiles, else 0); whole images per tile */
+    int grid_x, grid_y, grid_z;
+    int lds_bytes;
+} EasConvPlan;
+int eas_conv_fwd_plan(int NI, int Cin, int Cout, int Hi, int Wi, int ksize, int stride, int x_terms, EasConvPlan* out);
+int eas_conv_dgrad_s2_plan(int NI, int Cin, int Cout, int Hi, int Wi, EasConvPlan* out);
+int eas_conv_fwd_group_tile_plan(const EasConvProblem* problems, int n, int ksize, int x_terms, EasConvPlan* out);
+
 /* eas_conv_bn_act_eval (above) for several layers in one launch: the eval-mode head's stage over its pyramid levels.  Same descriptors, same
  * arithmetic per problem (bit-identical outputs); all problems ksize 1 or all ksize 3, stride 1, x_terms 3.  n <= 8. */
 int eas_conv_bn_act_eval_group(const EasConvBnActEval* problems, int n, eas_stream_t stream);
