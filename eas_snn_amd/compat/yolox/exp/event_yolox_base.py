@@ -29,6 +29,19 @@ _DEFAULTS = dict(
     store_events='dat',      # not the reference's: how a window store of train_input = 'dat_store' keeps its records (data.STORE_EVENTS)
 )
 
+# The values of ``train_input`` that train from recordings resident in HBM (sample indices -> frames and targets on the device), each with the
+# names in ``eas_snn_amd.data`` of its (training loader, evaluation loader, dataset, store factory) and the split it evaluates
+# (plain, with ``testdev``).  The names are looked up when they are used.
+#   'dat_store': Gen1.  ``store_records`` = 'windows': the store keeps only the records its samples read (data.gen1_store_for; the
+#       evaluation store too); ``store_events`` = 'packed' (with 'windows'): those records in packed form, 4 bytes per event where exact
+#   'hist_store': 1 Mpx.  ``store_sums`` = 'packed': the store keeps the bin sums in packed rows (data.hist_store_for; the evaluation store too)
+#   'atis_store': N-Caltech101
+_STORE_INPUTS = {
+    'dat_store': ('Gen1StoreLoader', 'Gen1StoreEvalLoader', 'Gen1StoreDataset', 'gen1_store_for', ('test', 'test')),
+    'hist_store': ('Gen4StoreLoader', 'Gen4StoreEvalLoader', 'Gen4StoreDataset', 'hist_store_for', ('test', 'test')),
+    'atis_store': ('NCaltechStoreLoader', 'NCaltechStoreEvalLoader', 'NCaltechStoreDataset', 'ncaltech_store_for', ('val', 'test')),
+}
+
 
 class EventExp(BaseExp):
     def __init__(self):
@@ -167,6 +180,13 @@ class EventExp(BaseExp):
         return {'aggregation': self.aggregation, 'overlap': 0, 'num_slice': self.Tl, 'micro_slice': self.Tm,
                 'measure': self.measure, 'window': (self.window * 1000, 0)}
 
+    def _store_input(self):
+        """(training loader, evaluation loader, dataset, store factory, evaluation splits) of a ``train_input`` in ``_STORE_INPUTS``, as
+        ``eas_snn_amd.data`` has them now; None for any other input"""
+        from eas_snn_amd import data
+        row = _STORE_INPUTS.get(getattr(self, 'train_input', None))
+        return None if row is None else tuple(getattr(data, name) for name in row[:4]) + row[4:]
+
     def get_dataset(self, cache=False, cache_type='ram'):
         from eas_snn_amd.data import SyntheticEventDataset
         return SyntheticEventDataset(self)
@@ -190,31 +210,17 @@ class EventExp(BaseExp):
         if getattr(self, 'train_input', None) == 'stacked_hist':       # opt-in: the 1 Mpx path (indices into a resident store -> augmented frames)
             from eas_snn_amd.data import SyntheticStackedHistLoader
             return SyntheticStackedHistLoader(self, batch_size)
-        if getattr(self, 'train_input', None) == 'dat_store':          # opt-in: Gen1 from recordings in HBM (sample indices -> frames and targets)
-            # ``store_records`` = 'windows': the store keeps only the records its samples read (data.gen1_store_for; the evaluation store too)
-            # ``store_events`` = 'packed' (with 'windows'): those records in packed form, 4 bytes per event where exact
-            from eas_snn_amd.data import Gen1StoreLoader
-            return Gen1StoreLoader(self, batch_size, **ranks)
-        if getattr(self, 'train_input', None) == 'atis_store':         # opt-in: N-Caltech101 from recordings in HBM (sample indices -> frames and targets)
-            from eas_snn_amd.data import NCaltechStoreLoader
-            return NCaltechStoreLoader(self, batch_size, **ranks)
-        if getattr(self, 'train_input', None) == 'hist_store':         # opt-in: 1 Mpx from recordings in HBM (sample indices -> frames and targets)
-            # ``store_sums`` = 'packed': the store keeps the bin sums in packed rows (data.hist_store_for; the evaluation store too)
-            from eas_snn_amd.data import Gen4StoreLoader
-            return Gen4StoreLoader(self, batch_size, **ranks)
+        store_input = self._store_input()
+        if store_input is not None:
+            return store_input[0](self, batch_size, **ranks)
         return SyntheticEventLoader(self, batch_size)
 
     def get_eval_dataset(self, **kwargs):
         from eas_snn_amd.data import SyntheticEvalDataset
-        if getattr(self, 'train_input', None) == 'dat_store':
-            from eas_snn_amd.data import Gen1StoreDataset, gen1_store_for
-            return Gen1StoreDataset(self, gen1_store_for(self, 'test'))
-        if getattr(self, 'train_input', None) == 'atis_store':
-            from eas_snn_amd.data import NCaltechStoreDataset, ncaltech_store_for
-            return NCaltechStoreDataset(self, ncaltech_store_for(self, 'test' if kwargs.get('testdev', False) else 'val'))
-        if getattr(self, 'train_input', None) == 'hist_store':
-            from eas_snn_amd.data import Gen4StoreDataset, hist_store_for
-            return Gen4StoreDataset(self, hist_store_for(self, 'test'))
+        store_input = self._store_input()
+        if store_input is not None:
+            _, _, Dataset, store_for, splits = store_input
+            return Dataset(self, store_for(self, splits[bool(kwargs.get('testdev', False))]))
         return SyntheticEvalDataset(self, length=int(getattr(self, 'eval_samples', 256)), n_events=int(getattr(self, 'eval_events', 200_000)))
 
     def get_eval_loader(self, batch_size, is_distributed, **kwargs):
@@ -237,15 +243,9 @@ class EventExp(BaseExp):
             # a sharded store: the rank's own samples in ascending order -- no padding, no repeats, every sample once across the ranks
             # under its global id; the ranks run different numbers of batches (``pad_eval_batches`` where an evaluator minds)
             idx = store.owned_samples.tolist()
-        if getattr(self, 'train_input', None) == 'dat_store':
-            from eas_snn_amd.data import Gen1StoreEvalLoader
-            return Gen1StoreEvalLoader(self, batch_size, idx, store)
-        if getattr(self, 'train_input', None) == 'atis_store':
-            from eas_snn_amd.data import NCaltechStoreEvalLoader
-            return NCaltechStoreEvalLoader(self, batch_size, idx, store)
-        if getattr(self, 'train_input', None) == 'hist_store':
-            from eas_snn_amd.data import Gen4StoreEvalLoader
-            return Gen4StoreEvalLoader(self, batch_size, idx, store)
+        store_input = self._store_input()
+        if store_input is not None:
+            return store_input[1](self, batch_size, idx, store)
         # synthetic streams on the Gen1 sensor (or on the canvas itself when that is smaller); ``eval_sensor_hw`` / ``eval_events`` override
         sensor = getattr(self, 'eval_sensor_hw', None) or (min(240, self.test_size[0]), min(304, self.test_size[1]))
         return SyntheticEvalLoader(self, batch_size, idx, n_events=valdataset.n_events, sensor_hw=tuple(sensor), dataset=valdataset)

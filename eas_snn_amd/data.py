@@ -312,6 +312,11 @@ def _atis_choice(exp_or_dims, measure=None, aggregation=None):
     return Tl, Tm, (H, W), (Hc, Wc), window, measure
 
 
+def _atis_kind(exp):
+    """``kind`` of ``_atis_choice`` for the experiment's ``measure`` / ``aggregation`` alone (ValueError for a value no front end has)"""
+    return _atis_choice((1, exp.Tm, (0, 0), (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))[-1]
+
+
 # ------------------------------------------------------------------------------------------------ 1 Mpx (RVT stacked histograms)
 def rvt_first_index(obj2repr_idx, label_index, num_slice, offset=0):
     """Index of the representation that feeds output slice 0 of a sample: RVTGEN4Dataset.generate_slices' ``start_idx`` (rvt_gen4.py:114-116:
@@ -543,25 +548,51 @@ def _store_key(exp, split):
     return (split,) + rank_and_world() + (getattr(exp, 'store_shard', 'none'),)
 
 
-class _Sharded:
-    """What a store knows about the ranks.  ``owned_samples`` int64: the ascending global indices of the samples whose records are
-    present (all of them unless the store was built with ``owned=`` / ``shard=``); ``owns(indices)``: numpy bool, on the host;
-    ``shard``: the ``(rank, world)`` it was built for or None; ``sample_rank`` int32 [G]: the rank that holds every sample's records
-    (None unless built with ``shard=``: with ``owned=`` alone the store knows its own recordings only)."""
+def _default_device():
+    """the current GPU where there is one, else the host: where ``*_store_for`` build a store when no device is given"""
+    return torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+
+
+class _Store:
+    """What every store of recordings is (``Gen1Store``, ``Gen4Store``, ``NCaltechStore`` and their subclasses): label tables built on the
+    host and uploaded once, the samples' names, and what the store knows about the ranks.  A store class states its tables, how it builds
+    them (it ends with ``_set_tables`` and ``_set_owners``) and its ``frames``.
+
+    ``host``: numpy copies of the tables, each also a tensor of the same name on ``device``; among them ``boxes`` float32 [L, 5] rows (x1,
+    y1, x2, y2, class) on the sensor ``sensor_hw`` and ``group_start`` int64 [G + 1]: sample g has the rows ``group_start[g]`` ..
+    ``group_start[g + 1]``.  ``sample_names`` [G]; ``group_rows`` int64 [G] and ``max_group_rows`` (host).  The length is the number of samples.
+
+    The ranks: ``owned_samples`` int64: the ascending global indices of the samples whose records are present (all of them unless the
+    store was built with ``owned=`` / ``shard=``); ``owns(indices)``: numpy bool, on the host; ``shard``: the ``(rank, world)`` it was
+    built for or None; ``sample_rank`` int32 [G]: the rank that holds every sample's records (None unless built with ``shard=``: with
+    ``owned=`` alone the store knows its own recordings only)."""
     shard, sample_rank = None, None
 
-    def _set_owner(self, sample_owned, shard=None, sample_rank=None):
-        self._sample_owned = np.asarray(sample_owned, dtype=bool).reshape(-1)
+    def _set_tables(self, host):
+        """``host`` (a dict of numpy tables with ``group_start`` among them), ``group_rows``, ``max_group_rows``, and every table uploaded
+        to ``self.device`` under its name"""
+        self.host = host
+        self.group_rows = np.diff(host['group_start'])
+        self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
+        for k, v in host.items():
+            setattr(self, k, torch.from_numpy(v).to(self.device))
+
+    def _set_owners(self, names, sample_file, owned=None, ranks=None, shard=None):
+        """the end of every build: ``names``: the recordings in order; ``sample_file``: the recording of every sample; ``owned``: the names
+        whose records are here (None = all); ``ranks``: {name: rank} or None; ``shard``: (rank, world) or None -> ``owned_samples``,
+        ``sample_rank``, ``shard``"""
+        sample_file = np.asarray(sample_file, dtype=np.int64).reshape(-1)
+        self._owner_args = (names, sample_file, owned)
+        self._sample_owned = np.array([owned is None or n in owned for n in names], dtype=bool)[sample_file]
         self.owned_samples = np.flatnonzero(self._sample_owned).astype(np.int64)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
-        self.sample_rank = None if sample_rank is None else np.asarray(sample_rank, dtype=np.int32).reshape(-1)
+        self.sample_rank = None if ranks is None else np.array([ranks[n] for n in names], dtype=np.int32)[sample_file]
 
-    def _adopt(self, shard, ranks, names, sample_file):
+    def _adopt(self, shard, ranks):
         """a store built with ``owned=`` from an assignment made outside (from the sizes of files): take ``shard`` = (rank, world) and the
-        assignment ``ranks`` = {name: rank} over; ``names``: the recordings in order, ``sample_file``: the recording of every sample"""
+        assignment ``ranks`` = {name: rank} over"""
         if shard is not None:
-            by_file = np.array([ranks[n] for n in names], dtype=np.int32)
-            self._set_owner(self._sample_owned, shard, by_file[np.asarray(sample_file, dtype=np.int64)])
+            self._set_owners(*self._owner_args, ranks, shard)
 
     @property
     def sharded(self):
@@ -581,6 +612,68 @@ class _Sharded:
             bad = np.asarray(indices, dtype=np.int64).reshape(-1)[~ok.reshape(-1)]
             raise IndexError(f'samples {bad[:8].tolist()} are not held by this store (shard {self.shard}, {len(self.owned_samples)} of '
                              f'{len(self._sample_owned)} samples owned)')
+
+    def __len__(self):
+        return len(self.sample_names)
+
+    def raw_labels(self, index):
+        """float32 [n, 5] rows (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands them out (``map_val``,
+        ``format='xywh'``: ``xyxy2xywh`` of the raw boxes, gen1.py:191-197, rvt_gen4.py:227-230, ncaltech.py:199-202 -- not truncated, not
+        transformed; 1 Mpx: rescaled by extract_labels; N-Caltech101: the sample's one row)"""
+        a, b = self.host['group_start'][index], self.host['group_start'][index + 1]
+        box = self.host['boxes'][a:b].copy()
+        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        return box
+
+    def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
+        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
+        box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
+        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
+                                 canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
+
+
+class _Arena:
+    """The device allocation that a build fills piece by piece, in units of ``unit`` bytes, and the rule of every store that has one: a
+    piece that finds no room makes the arena ``full``; from then on the build goes on measuring -- every later piece is still sized,
+    nothing more is stored -- and ``close`` raises a ValueError that names the bytes needed.  ``buf`` uint8 [capacity_bytes] (a multiple
+    of the unit), ``units``: stored so far = where the next piece goes, ``needed``: measured so far."""
+
+    def __init__(self, capacity_bytes, unit, device):
+        self.unit, self.capacity_bytes = unit, capacity_bytes // unit * unit
+        self.buf = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=device)
+        self.units, self.needed, self.full = 0, 0, False
+
+    def fits(self, units):
+        """whether a piece of ``units`` units is stored (at ``self.units``) or only measured"""
+        return not self.full and self.units + units <= self.capacity_bytes // self.unit
+
+    def place(self, units):
+        """count the next piece, which takes ``units`` units: -> the unit it starts at, None once the arena is full (the caller that
+        learns from its pack operator that the piece found no room has set ``full``)"""
+        self.needed += units
+        self.full = not self.fits(units)
+        if self.full:
+            return None
+        self.units += units
+        return self.units - units
+
+    @property
+    def used_bytes(self):
+        return self.units * self.unit
+
+    def close(self, what):
+        """after the build: the view of ``buf`` in use; an arena too small is let go and raises ValueError (``what``: the store's pieces)"""
+        if self.full:
+            self.buf = None
+            raise ValueError(f'the {what} of these recordings need {self.needed * self.unit} bytes, the arena holds {self.capacity_bytes} '
+                             '(capacity_bytes)')
+        return self.buf[:self.used_bytes]
+
+    def trim(self):
+        """reallocate to the used size and let the rest go (old and new exist side by side for the time of the copy) -> the new ``buf``"""
+        if self.capacity_bytes != self.used_bytes:
+            self.buf, self.capacity_bytes = self.buf[:self.used_bytes].clone(), self.used_bytes
+        return self.buf
 
 
 def _sharded_iters(store, batch_size, rank):
@@ -664,7 +757,7 @@ def synth_gen1_recordings(n_files, labels_per_file, n_events=50_000, sensor_hw=(
     return out
 
 
-class Gen1Store(_Sharded):
+class Gen1Store(_Store):
     """Gen1 recordings and their labels resident on the device: what GEN1Dataset keeps on disk and in host lists (gen1.py:43-85), as tables
     that the kernels index.  ``recordings``: a list of ``(name, dat_bytes, bbox_rows)`` -- the byte image of ``<name>_td.dat`` and the
     structured array of ``<name>_bbox.npy`` (fields ``t`` or ``ts``, ``x``, ``y``, ``w``, ``h``, ``class_id``); names in ``ignore`` are left
@@ -684,11 +777,10 @@ class Gen1Store(_Sharded):
     is not owned contributes its rows to ``boxes``, ``group_start``, ``group_t``, ``group_file`` and ``sample_names`` -- these, the flat
     sample index, ``raw_labels``, ``targets`` and the length are the same on every rank and the same as the unsharded store's -- and a
     zero-length area to ``records`` / ``file_offsets``; its ``dat_bytes`` may be None and is never touched.  ``owned_samples``, ``owns``,
-    ``shard``, ``sample_rank``: see ``_Sharded``."""
+    ``shard``, ``sample_rank``: see ``_Store``."""
 
     def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), owned=None, shard=None):
-        self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
-        self.device = torch.device(device)
+        self._set_geometry(Tl, window, device, sensor_hw)
         areas = []
 
         def keep(area, times):
@@ -696,32 +788,38 @@ class Gen1Store(_Sharded):
             return len(area) // 8
         self._scan(recordings, ignore, keep, owned, shard)
         self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
-        self._upload_tables()
+        self._set_tables(self.host)
+
+    def _set_geometry(self, Tl, window, device, sensor_hw):
+        self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
+        self.device = torch.device(device)
+
+    @staticmethod
+    def _planned(recordings, ignore, owned, shard):
+        """(recordings, owned names or None = all, {name: rank} or None): ``_memory_plan`` by ``len(dat_bytes)``; with ``shard=`` the
+        recordings are listed first, without those in ``ignore``"""
+        if shard is not None:
+            recordings = [r for r in recordings if r[0] not in ignore]
+        return (recordings,) + _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)
 
     def _scan(self, recordings, ignore, take, owned=None, shard=None):
-        """the label tables (``host``, ``names``, ``sample_names``, ``group_rows``, ``max_group_rows``) of the recordings, taken from the
+        """the label tables (``host``, not uploaded yet, ``names``, ``sample_names``) and the owners of the recordings, taken from the
         iterable one at a time; ``take(record area uint8, label-group times int64)`` is called once per owned recording, in order, and
         returns how many records the store keeps of it (``file_offsets`` is the prefix of those numbers; a recording that is not owned
         adds 0).  Nothing of a recording is held on to here once ``take`` has returned."""
         self.names, self.sample_names = [], []
         tables = dict(file_offsets=[0], boxes=[], group_start=[0], group_t=[], group_file=[])
-        if shard is not None:
-            recordings = [r for r in recordings if r[0] not in ignore]
-        owned, ranks = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)
+        recordings, owned, ranks = self._planned(recordings, ignore, owned, shard)
         for name, dat, rows in recordings:
             if name not in ignore:
                 self._scan_one(name, dat, rows, tables, take if owned is None or name in owned else None)
             del dat, rows                                       # released before the iterable is asked for the next recording
-        file_owned = np.array([owned is None or n in owned for n in self.names], dtype=bool)
-        group_file = np.asarray(tables['group_file'], dtype=np.int64)
-        self._set_owner(file_owned[group_file], shard, None if ranks is None else np.array([ranks[n] for n in self.names], dtype=np.int32)[group_file])
+        self._set_owners(self.names, tables['group_file'], owned, ranks, shard)
         boxes = tables.pop('boxes')
         self.host = dict(file_offsets=np.asarray(tables['file_offsets'], dtype=np.int64),
                          boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
                          group_start=np.asarray(tables['group_start'], dtype=np.int64), group_t=np.asarray(tables['group_t'], dtype=np.int64),
                          group_file=np.asarray(tables['group_file'], dtype=np.int32))
-        self.group_rows = np.diff(self.host['group_start'])
-        self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
 
     def _scan_one(self, name, dat, rows, tables, take):
         """``take=None``: a recording that is not owned -- its labels only; ``dat`` is not looked at"""
@@ -746,10 +844,6 @@ class Gen1Store(_Sharded):
         base = tables['group_start'][-1]                        # rows of the recordings in front
         tables['group_start'] += [base + int(e) for e in np.r_[first[1:], len(t)]] if len(first) else []
 
-    def _upload_tables(self):
-        for k, v in self.host.items():
-            setattr(self, k, torch.from_numpy(v).to(self.device))
-
     @classmethod
     def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), shard=None, read_dat=None):
         """the ``<name>_td.dat`` / ``<name>_bbox.npy`` pairs of the directories ``paths``, every directory in sorted order (the reference
@@ -758,10 +852,8 @@ class Gen1Store(_Sharded):
         ``_bbox.npy`` is read, and of the ``_td.dat`` files only those ``shard_recordings`` gives to ``rank``.  ``read_dat(path)``: the reader
         of a ``_td.dat`` (default ``numpy.fromfile(path, dtype=numpy.uint8)``)."""
         pairs, owned, ranks = cls._listed(paths, ignore, shard)
-        read_dat = read_dat if read_dat is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
-        recs = [(name, read_dat(dat) if owned is None or name in owned else None, np.load(box)) for name, dat, box in pairs]
-        store = cls(recs, Tl, window, device, sensor_hw=sensor_hw, owned=owned)
-        store._adopt(shard, ranks, store.names, store.host['group_file'])
+        store = cls(list(cls._read(pairs, owned, read_dat)), Tl, window, device, sensor_hw=sensor_hw, owned=owned)
+        store._adopt(shard, ranks)
         return store
 
     @staticmethod
@@ -774,18 +866,18 @@ class Gen1Store(_Sharded):
         owned, ranks = _shard_plan([p[0] for p in pairs], [os.path.getsize(p[1]) for p in pairs] if shard is not None else (), shard, None)
         return pairs, owned, ranks
 
+    @staticmethod
+    def _read(pairs, owned, read_dat=None):
+        """the recordings ``(name, dat_bytes or None where not owned, bbox_rows)`` of the listed ``pairs``, read one at a time as they are
+        asked for"""
+        read_dat = read_dat if read_dat is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
+        for name, dat, box in pairs:
+            yield name, read_dat(dat) if owned is None or name in owned else None, np.load(box)
 
-
-    def __len__(self):
-        return len(self.sample_names)
-
-    def raw_labels(self, index):
-        """float32 [n, 5] rows (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands them out (``map_val``,
-        ``format='xywh'``, gen1.py:191-197: ``xyxy2xywh`` of the raw boxes -- not truncated, not transformed)"""
-        a, b = self.host['group_start'][index], self.host['group_start'][index + 1]
-        box = self.host['boxes'][a:b].copy()
-        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
-        return box
+    def _window_times(self, t):
+        """int64 [G * Tl]: the ends of the ``Tl`` windows that end at the label times ``t`` (int64 [G] on the device), a window apart"""
+        shift = torch.arange(-self.Tl + 1, 1, dtype=torch.int64, device=self.device) * (self.window[1] - self.window[0])
+        return (t[:, None] + shift[None, :]).reshape(-1)
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): label time and recording gathered
@@ -795,21 +887,13 @@ class Gen1Store(_Sharded):
         holds the records of every sample asked for (``owns``; the loaders check their indices on the host before they upload them) -- a
         sample that is not owned has no records here and comes out as empty frames, silently."""
         B, Tl = sample_idx.numel(), self.Tl
-        step = self.window[1] - self.window[0]
-        shift = torch.arange(-Tl + 1, 1, dtype=torch.int64, device=self.device) * step
-        t = (self.group_t[sample_idx][:, None] + shift[None, :]).reshape(-1)
+        t = self._window_times(self.group_t[sample_idx])
         f = self.group_file[sample_idx][:, None].expand(B, Tl).reshape(-1)
         ranges = ops.event_window_search(self.records, t, self.window, Tl, self.file_offsets, f)
         par = params_on(params, self.device)[:, None, :].expand(B, Tl, 5).reshape(-1, 5)
         Hc, Wc = canvas_hw if canvas_hw is not None else exp.input_size
         out = dat_ranges_to_frames(self.records, ranges, exp.Tm, self.sensor_hw, (Hc, Wc), par, aggregation=exp_aggregation(exp))
         return out.reshape(B, Tl, exp.Tm, 2, Hc, Wc)
-
-    def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
-        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
-        box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
-        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
-                                 canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
 
 
 class Gen1WindowStore(Gen1Store):
@@ -839,19 +923,19 @@ class Gen1WindowStore(Gen1Store):
 
     def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, source_bytes=None, owned=None,
                  shard=None):
-        self.Tl, self.window, self.sensor_hw = int(Tl), (int(window[0]), int(window[1])), (int(sensor_hw[0]), int(sensor_hw[1]))
-        self.device = torch.device(device)
-        if shard is not None:
-            recordings = [r for r in recordings if r[0] not in ignore]
+        self._set_geometry(Tl, window, device, sensor_hw)
         if capacity_bytes is None:
-            if source_bytes is None and isinstance(recordings, (list, tuple)):
-                mine = _memory_plan(recordings, lambda r: r[0], lambda r: r[1], shard, owned)[0]
-                source_bytes = sum(len(dat) for name, dat, _ in recordings if mine is None or name in mine)
+            if source_bytes is None:
+                recordings, mine, _ = self._planned(recordings, ignore, owned, shard)
+                if isinstance(recordings, (list, tuple)):
+                    source_bytes = sum(len(dat) for name, dat, _ in recordings if mine is None or name in mine)
             capacity_bytes = self._default_capacity(source_bytes)
         self._open_arena(int(capacity_bytes))
-        self.total_records, self.kept_records, self._needed_records, self._ranges = 0, 0, 0, []
+        self.capacity_bytes = self._arena.capacity_bytes
+        self.total_records, self.kept_records, self._ranges = 0, 0, []
         self._scan(recordings, ignore, self._compact, owned, shard)
         self._close_arena()
+        self.used_bytes = self._arena.used_bytes
         ranges, self._ranges = self._ranges, None
         if self.sharded:                                                # the rows of the owned samples, in their order; the others stay empty
             self.sample_ranges = torch.zeros((len(self.sample_names), self.Tl, 2), dtype=torch.int64, device=self.device)
@@ -859,19 +943,14 @@ class Gen1WindowStore(Gen1Store):
                 self.sample_ranges[torch.from_numpy(self.owned_samples).to(self.device)] = torch.cat(ranges)
         else:
             self.sample_ranges = torch.cat(ranges) if ranges else torch.zeros((0, self.Tl, 2), dtype=torch.int64, device=self.device)
-        self._upload_tables()
+        self._set_tables(self.host)
 
     def _open_arena(self, capacity_bytes):
-        self.capacity_bytes = capacity_bytes // 8 * 8
-        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
+        self._arena = _Arena(capacity_bytes, 8, self.device)            # a unit is a record
 
     def _close_arena(self):
-        """after the scan: ``used_bytes`` and the view of the arena that holds the records, or the ValueError of an arena too small"""
-        needed, self.used_bytes = self._needed_records * 8, self.kept_records * 8
-        if needed > self.capacity_bytes:
-            del self._arena
-            raise ValueError(f'the windows of these recordings need {needed} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
-        self.records = self._arena[:self.used_bytes]
+        """after the scan: the view of the arena that holds the records, or the ValueError of an arena too small"""
+        self.records = self._arena.close('windows')
 
     def _default_capacity(self, source_bytes):
         free = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if self.device.type == 'cuda' else None
@@ -886,22 +965,26 @@ class Gen1WindowStore(Gen1Store):
         with warnings.catch_warnings():
             warnings.simplefilter('ignore', UserWarning)                # a read-only host array is only read
             rec = torch.from_numpy(area).to(self.device)
-        step = self.window[1] - self.window[0]
-        shift = torch.arange(-self.Tl + 1, 1, dtype=torch.int64, device=self.device) * step
-        t = (torch.from_numpy(times).to(self.device)[:, None] + shift[None, :]).reshape(-1)
-        ranges = ops.event_window_search(rec, t, self.window, self.Tl)
+        ranges = ops.event_window_search(rec, self._window_times(torch.from_numpy(times).to(self.device)), self.window, self.Tl)
         return (rec,) + ops.record_ranges_union(ranges)
 
     def _window_ranges(self, area, times):
         """(ranges int64 [G * Tl, 2] into the arena from record 0 of this recording's kept area, records kept): the device steps of one
-        recording, up to the gather"""
+        recording, the gather into the arena -- where it still has room -- among them"""
         rec, segments, seg_dst, mapped = self._window_union(area, times)
         kept = int(seg_dst[-1])
-        if self._needed_records + kept <= self.capacity_bytes // 8:
-            ops.records_gather(rec, segments, seg_dst, self._arena, self.kept_records)
+        if self._arena.fits(kept):
+            ops.records_gather(rec, segments, seg_dst, self._arena.buf, self._arena.units)
         return mapped, kept
 
+    def _placed(self, kept):
+        """(index of the first, number) of the records that ``records`` / ``file_offsets`` / ``sample_ranges`` count for a recording of
+        ``kept`` kept records, None once the arena is full"""
+        at = self._arena.place(kept)
+        return None if at is None else (at, kept)
+
     def _compact(self, area, times):
+        """``_scan``'s ``take``: one recording measured and, while the arena has room, stored"""
         self.total_records += len(area) // 8
         if len(times) == 0:
             return 0
@@ -909,12 +992,12 @@ class Gen1WindowStore(Gen1Store):
             mapped, kept = torch.zeros((len(times) * self.Tl, 2), dtype=torch.int64, device=self.device), 0
         else:
             mapped, kept = self._window_ranges(area, np.ascontiguousarray(times, dtype=np.int64))
-        self._needed_records += kept
-        if self._needed_records > self.capacity_bytes // 8:             # too small: go on counting, store nothing more
+        placed = self._placed(kept)
+        if placed is None:                                              # too small: go on measuring, store nothing more
             return 0
-        self._ranges.append((mapped + self.kept_records).reshape(len(times), self.Tl, 2))
+        self._ranges.append((mapped + placed[0]).reshape(len(times), self.Tl, 2))
         self.kept_records += kept
-        return kept
+        return placed[1]
 
     @classmethod
     def from_directories(cls, paths, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, shard=None, read_dat=None):
@@ -923,21 +1006,15 @@ class Gen1WindowStore(Gen1Store):
         ``_td.dat`` files are read (their size is the weight -- a proxy for what the windows keep, see the class)."""
         import os
         pairs, owned, ranks = cls._listed(paths, ignore, shard)
-        read_dat = read_dat if read_dat is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
-
-        def read():
-            for name, dat, box in pairs:
-                yield name, read_dat(dat) if owned is None or name in owned else None, np.load(box)
         size = sum(os.path.getsize(dat) for name, dat, _ in pairs if owned is None or name in owned)
-        store = cls(read(), Tl, window, device, sensor_hw=sensor_hw, capacity_bytes=capacity_bytes, source_bytes=size, owned=owned)
-        store._adopt(shard, ranks, store.names, store.host['group_file'])
+        store = cls(cls._read(pairs, owned, read_dat), Tl, window, device, sensor_hw=sensor_hw, capacity_bytes=capacity_bytes, source_bytes=size,
+                    owned=owned)
+        store._adopt(shard, ranks)
         return store
 
     def trim(self):
-        """reallocate ``records`` to the used size and let the arena go (the two exist side by side for the time of the copy)"""
-        if self.capacity_bytes != self.used_bytes:
-            self.records = self.records.clone()
-            self._arena, self.capacity_bytes = self.records, self.used_bytes
+        """give back what the arena does not use: its bytes in use are reallocated at their size (``_Arena.trim``)"""
+        self.records, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
         return self
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
@@ -979,54 +1056,44 @@ class Gen1PackedWindowStore(Gen1WindowStore):
     def _open_arena(self, capacity_bytes):
         ops.records_widths(*self.sensor_hw)
         self.records = None
-        self.capacity_bytes = capacity_bytes // ops.RECORDS_UNIT * ops.RECORDS_UNIT
-        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
-        self._table = torch.empty((self.capacity_bytes // ops.RECORDS_UNIT, 2), dtype=torch.int32, device=self.device)  # a block takes a unit at least
-        self._blocks, self._units, self._needed_units, self._full = 0, 0, 0, False
+        self._arena = _Arena(capacity_bytes, ops.RECORDS_UNIT, self.device)
+        self._table = torch.empty((self._arena.capacity_bytes // ops.RECORDS_UNIT, 2), dtype=torch.int32, device=self.device)  # a block takes a unit at least
+        self._blocks = 0
 
     def _window_ranges(self, area, times):
-        """(ranges int64 [G * Tl, 2] of logical records from this recording's first block, records kept, blocks taken)"""
+        """(ranges int64 [G * Tl, 2] of logical records from this recording's first block, records kept); the kept records are gathered
+        into a scratch and packed behind the arena's current unit, or only measured once the arena is full"""
         rec, segments, seg_dst, mapped = self._window_union(area, times)
         kept = int(seg_dst[-1])
-        if kept == 0:
-            return mapped, 0, 0
-        scratch = torch.empty(8 * kept, dtype=torch.uint8, device=self.device)
-        ops.records_gather(rec, segments, seg_dst, scratch)
-        nb = (kept + ops.RECORDS_BLOCK - 1) // ops.RECORDS_BLOCK
-        full = self._full or self._blocks + nb > self._table.shape[0]      # (more blocks than the arena has units: it cannot take them either)
-        table = torch.empty((nb, 2), dtype=torch.int32, device=self.device) if full else self._table[self._blocks:self._blocks + nb]
-        try:
-            took = ops.records_pack(scratch, table, self._arena, self._units, *self.sensor_hw, dry_run=full)
-        except ops.PackedArenaFull as e:                                    # too small: go on measuring, store nothing more
-            took, full = e.units, True
-        self._full = full
-        self._needed_units += took
-        self._units += 0 if self._full else took
-        return mapped, kept, nb
+        if kept:
+            scratch = torch.empty(8 * kept, dtype=torch.uint8, device=self.device)
+            ops.records_gather(rec, segments, seg_dst, scratch)
+            arena, nb = self._arena, self._blocks_of(kept)
+            arena.full = arena.full or self._blocks + nb > self._table.shape[0]      # (more blocks than the arena has units: it cannot take them either)
+            table = torch.empty((nb, 2), dtype=torch.int32, device=self.device) if arena.full else self._table[self._blocks:self._blocks + nb]
+            try:
+                took = ops.records_pack(scratch, table, arena.buf, arena.units, *self.sensor_hw, dry_run=arena.full)
+            except ops.PackedArenaFull as e:                                # too small: go on measuring, store nothing more
+                took, arena.full = e.units, True
+            arena.place(took)
+        return mapped, kept
 
-    def _compact(self, area, times):
-        self.total_records += len(area) // 8
-        if len(times) == 0:
-            return 0
-        if len(area) == 0:                                              # no events: every window is empty
-            mapped, kept, nb = torch.zeros((len(times) * self.Tl, 2), dtype=torch.int64, device=self.device), 0, 0
-        else:
-            mapped, kept, nb = self._window_ranges(area, np.ascontiguousarray(times, dtype=np.int64))
-        if self._full:
-            return 0
-        self._ranges.append((mapped + self._blocks * ops.RECORDS_BLOCK).reshape(len(times), self.Tl, 2))
+    @staticmethod
+    def _blocks_of(kept):
+        return (kept + ops.RECORDS_BLOCK - 1) // ops.RECORDS_BLOCK
+
+    def _placed(self, kept):
+        """the parent's, in logical records: every recording starts on a fresh block (``_window_ranges`` has placed its units already)"""
+        if self._arena.full:
+            return None
+        first, nb = self._blocks * ops.RECORDS_BLOCK, self._blocks_of(kept)
         self._blocks += nb
-        self.kept_records += kept
-        return nb * ops.RECORDS_BLOCK
+        return first, nb * ops.RECORDS_BLOCK
 
     def _close_arena(self):
-        if self._full:
-            del self._arena, self._table
-            raise ValueError(f'the packed records of these recordings need {self._needed_units * ops.RECORDS_UNIT} bytes, the arena holds '
-                             f'{self.capacity_bytes} (capacity_bytes)')
-        self.used_bytes = self._units * ops.RECORDS_UNIT
-        self.payload, self.table = self._arena[:self.used_bytes], self._table[:self._blocks]
-        self.wide_blocks = self._units - self._blocks                   # a narrow block takes one unit, a wide block two
+        self.payload = self._arena.close('packed records')
+        self.table = self._table[:self._blocks]
+        self.wide_blocks = self._arena.units - self._blocks             # a narrow block takes one unit, a wide block two
         self.narrow_blocks = self._blocks - self.wide_blocks
 
     def nbytes(self):
@@ -1034,10 +1101,10 @@ class Gen1PackedWindowStore(Gen1WindowStore):
         return self.used_bytes + self.table.numel() * 4
 
     def trim(self):
-        """reallocate ``payload`` and ``table`` to the used size and let the arena go (old and new exist side by side for the time of the copy)"""
+        """the parent's, for ``payload``; the table is reallocated at its used size with it"""
         if self.capacity_bytes != self.used_bytes:
-            self.payload, self.table = self.payload.clone(), self.table.clone()
-            self._arena, self._table, self.capacity_bytes = self.payload, self.table, self.used_bytes
+            self.table = self._table = self.table.clone()
+        self.payload, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
         return self
 
     def unpacked(self, a, e):
@@ -1052,6 +1119,28 @@ STORE_RECORDS = ('all', 'windows')          # ``exp.store_records``: every recor
 STORE_EVENTS = ('dat', 'packed')            # ``exp.store_events``: the kept records as 8-byte .dat records / packed (Gen1PackedWindowStore)
 
 
+def _data_dirs(exp, split):
+    """[``exp.data_dir``/train, /val] (``split='test'``: [/test]) when every one of them is a directory, else None"""
+    import os
+    root = str(getattr(exp, 'data_dir', '') or '')
+    dirs = [os.path.join(root, d) for d in (('test',) if split == 'test' else ('train', 'val'))]
+    return dirs if root and all(os.path.isdir(d) for d in dirs) else None
+
+
+def _store_for(exp, attr, split, device, find, from_data, synthetic, more=()):
+    """What the three ``*_store_for`` share: the stores kept on the experiment in the dict ``attr``, one per ``_store_key(exp, split)`` +
+    ``more``; a store that is not there yet is built on ``device`` (None: ``_default_device()``) with the shard of the
+    experiment (``exp_store_shard``) -- ``from_data(found, device, shard)`` if ``find()`` finds the dataset, else ``synthetic(device, shard)``"""
+    cache = exp.__dict__.setdefault(attr, {})
+    shard = exp_store_shard(exp)
+    key = _store_key(exp, split) + more
+    if key not in cache:
+        device = _default_device() if device is None else device
+        found = find()
+        cache[key] = from_data(found, device, shard) if found else synthetic(device, shard)
+    return cache[key]
+
+
 def gen1_store_for(exp, split='train', device=None):
     """The store of an experiment with ``train_input = 'dat_store'``: ``Gen1Store.from_directories`` over ``exp.data_dir``/train + /val
     (``split='test'``: /test) when that directory exists, seeded synthetic recordings otherwise (``exp.store_recordings`` = (files, labels
@@ -1061,7 +1150,6 @@ def gen1_store_for(exp, split='train', device=None):
     ``exp.store_events`` (default ``'dat'``) = ``'packed'`` with ``store_records = 'windows'``: a ``Gen1PackedWindowStore``, trimmed;
     ``'packed'`` with ``store_records = 'all'``, or any other value, raises ValueError before any device work.  Kept on the experiment: one
     store per (split, rank, world, store_shard), the three kinds of store apart."""
-    import os
     kind, events = getattr(exp, 'store_records', 'all'), getattr(exp, 'store_events', 'dat')
     if kind not in STORE_RECORDS:
         raise ValueError(f'store_records must be one of {STORE_RECORDS}, got {kind!r}')
@@ -1070,42 +1158,149 @@ def gen1_store_for(exp, split='train', device=None):
     if events == 'packed' and kind != 'windows':
         raise ValueError(f"store_events = 'packed' packs the records a window store keeps: it needs store_records = 'windows', got {kind!r}")
     cls = (Gen1PackedWindowStore if events == 'packed' else Gen1WindowStore) if kind == 'windows' else Gen1Store
-    cache = exp.__dict__.setdefault('_dat_stores' if kind == 'all' else '_dat_packed_stores' if events == 'packed' else '_dat_window_stores', {})
-    shard = exp_store_shard(exp)
-    split, name = _store_key(exp, split), split
-    if split not in cache:
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
-        window = (exp.window * 1000, 0)
-        root = str(getattr(exp, 'data_dir', '') or '')
-        dirs = [os.path.join(root, d) for d in (('test',) if name == 'test' else ('train', 'val'))]
-        if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = cls.from_directories(dirs, exp.Tl, window, device, shard=shard)
-        else:
-            n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
-            size = exp.test_size if name == 'test' else exp.input_size
-            sensor = (min(240, size[0]), min(304, size[1]))
-            recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(name == 'test'))
-            cache[split] = cls(recs, exp.Tl, window, device, sensor_hw=sensor, shard=shard)
-        if kind == 'windows':
-            cache[split].trim()
-    return cache[split]
+    window = (exp.window * 1000, 0)
+    made = (lambda store: store.trim()) if kind == 'windows' else (lambda store: store)
+
+    def synthetic(device, shard):
+        n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
+        size = exp.test_size if split == 'test' else exp.input_size
+        sensor = (min(240, size[0]), min(304, size[1]))
+        recs = synth_gen1_recordings(n_files, n_labels, n_events, sensor, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
+        return made(cls(recs, exp.Tl, window, device, sensor_hw=sensor, shard=shard))
+    return _store_for(exp, '_dat_stores' if kind == 'all' else '_dat_packed_stores' if events == 'packed' else '_dat_window_stores',
+                      split, device, lambda: _data_dirs(exp, split),
+                      lambda dirs, device, shard: made(cls.from_directories(dirs, exp.Tl, window, device, shard=shard)), synthetic)
 
 
-class Gen1StoreDataset:
-    """what the trainer and the evaluators ask of a dataset, over a ``Gen1Store``: length, ``sample_names`` (they carry the label time the
-    Prophesee protocol reads), ``class_names``, ``map_val`` without random augmentation"""
+class _StoreDataset:
+    """what the trainer and the evaluators ask of a dataset, over a store: length, ``sample_names``, ``class_names`` (the class indices
+    as strings unless the class says otherwise), ``map_val`` without random augmentation"""
     map_val, random_aug = True, False
 
     def __init__(self, exp, store):
         self.exp, self.store, self.sample_names = exp, store, store.sample_names
-        self.class_names = [str(i) for i in range(exp.num_classes)]
+        self.class_names = self._class_names()
+
+    def _class_names(self):
+        return [str(i) for i in range(self.exp.num_classes)]
 
     def __len__(self):
         return len(self.store)
 
 
-class Gen1StoreLoader:
+class _StoreLoader:
+    """The training loader over a store (``Gen1StoreLoader`` says what it does, on one rank and on N).  A class states: ``jitter`` of
+    ``jitter_params``; ``permutes``: whether a sample's boxes are permuted -- where not, nothing is drawn for them and ``batches`` holds
+    (indices, params) only; ``what``: its samples, in the message of a store smaller than a batch; ``Dataset``; ``make_store(exp)``: the
+    store when none is given; ``check(exp)``: what it asks of the experiment (ValueError), before it looks at the store."""
+    jitter, permutes, what, Dataset = .3, True, 'labels', _StoreDataset
+
+    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
+        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
+        self.check(exp)
+        self.store = store if store is not None else self.make_store(exp)
+        self._plan(rank, world)
+        self.dataset = self.Dataset(exp, self.store)
+        self.epoch = 0
+
+    def check(self, exp):
+        pass
+
+    def _plan(self, rank, world):
+        """``rank``, ``world``, ``sharded`` and ``iters`` of a training loader over ``self.store``"""
+        self.rank, self.world = (int(rank), int(world)) if self.store.shard is None else self.store.shard
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f'rank {rank} of a world of {world}')
+        self.sharded = self.store.sharded
+        if self.sharded:
+            self.iters = _sharded_iters(self.store, self.batch_size, self.rank)
+        else:
+            self.iters = len(self.store) // (self.batch_size * self.world)
+            assert self.iters >= 1, f'fewer {self.what} than one batch'
+
+    def _epoch(self, epoch):
+        """(random state, sample order, samples drawn per step, the rows of a step that this rank keeps) of an epoch"""
+        if self.sharded:
+            rs = _shard_state(self.seed, epoch, self.rank)
+            return rs, self.store.owned_samples[rs.permutation(len(self.store.owned_samples))], self.batch_size, slice(None)
+        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
+        return rs, rs.permutation(len(self.store)), self.batch_size * self.world, slice(self.rank, None, self.world)
+
+    def __len__(self):
+        return self.iters
+
+    def close_mosaic(self):
+        pass
+
+    def batches(self, epoch):
+        """[(sample indices int64 [B], params int32 [B, 5], box permutations int32 [B, P])] of an epoch; P = the store's largest group (at
+        least 1), a row of a smaller group is filled up with the identity.  A loader that does not permute: [(indices, params)]."""
+        rs, order, drawn, keep = self._epoch(epoch)
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
+        P = max(self.store.max_group_rows, 1)
+        out = []
+        for i in range(self.iters):
+            idx = order[i * drawn:(i + 1) * drawn].astype(np.int64)
+            par = np.empty((len(idx), 5), dtype=np.int32)
+            perm = np.tile(np.arange(P, dtype=np.int32), (len(idx), 1))
+            for b, s in enumerate(idx):
+                par[b] = jitter_params(H, W, Hc, Wc, jitter=self.jitter, rng=rs)
+                if self.permutes:
+                    n = int(self.store.group_rows[s])
+                    perm[b, :n] = rs.permutation(n)
+            out.append(tuple(np.ascontiguousarray(a[keep]) for a in ((idx, par, perm) if self.permutes else (idx, par))))
+        return out
+
+    def __iter__(self):
+        dev = self.store.device
+        draws = self.batches(self.epoch)
+        self.epoch += 1
+        for batch in draws:
+            self.store.check_owned(batch[0])
+            idx, par, *perm = (torch.from_numpy(a).to(dev) for a in batch)      # (``perm``: one tensor, or none for a store whose ``targets`` takes none)
+            yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, *perm, self.exp.input_size, self.max_labels)
+
+
+class _StoreEvalLoader:
+    """The evaluation loader over a store (``Gen1StoreEvalLoader`` says what it does).  A class states its ``Dataset`` and ``check(exp)``."""
+    Dataset = _StoreDataset
+
+    def __init__(self, exp, batch_size, indices, store, min_batches=0):
+        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
+        self.check(exp)
+        store.check_owned(self.indices)
+        self.dataset = self.Dataset(exp, store)
+        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
+
+    def check(self, exp):
+        pass
+
+    def __len__(self):
+        return max((len(self.indices) + self.batch_size - 1) // self.batch_size, self.min_batches)
+
+    def _empty(self):
+        """a batch without samples"""
+        frames = torch.zeros((0, getattr(self.store, 'Tl', 1), self.exp.Tm, 2) + tuple(self.exp.test_size), device=self.store.device)
+        return frames, [], (torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)), torch.zeros(0, dtype=torch.int64)
+
+    def __iter__(self):
+        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
+        row = letterbox_params(H, W, Hc, Wc)
+        for b in range(len(self)):
+            ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
+            if not ids:
+                yield self._empty()
+                continue
+            idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
+            frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
+            yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
+
+
+class Gen1StoreDataset(_StoreDataset):
+    """``_StoreDataset`` over a ``Gen1Store``: the sample names carry the label time the Prophesee protocol reads"""
+
+
+class Gen1StoreLoader(_StoreLoader):
     """Training loader of Gen1 from a ``Gen1Store``: iterable of (frames [B, Tl, Tm, 2, Hc, Wc] fp32 on the GPU, targets [B, 50, 5] rows
     (cls, cx, cy, w, h), zero padded).  An epoch is a permutation of the samples; per sample the draws come in the reference's order
     (get_random_data, gen1.py:485-511): ``jitter_params(..., jitter=.3)``, then the permutation of its boxes, ``rng.permutation(n)`` -- the
@@ -1128,69 +1323,16 @@ class Gen1StoreLoader:
     Before a step uploads its indices they are checked against ``store.owns`` on the host: IndexError for a sample whose records are
     not here."""
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
-        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
+    Dataset = Gen1StoreDataset
+
+    def check(self, exp):
         exp_aggregation(exp)
-        self.store = store if store is not None else gen1_store_for(exp)
-        self._plan(rank, world, 'labels')
-        self.dataset = Gen1StoreDataset(exp, self.store)
-        self.epoch = 0
 
-    def _plan(self, rank, world, what):
-        """``rank``, ``world``, ``sharded`` and ``iters`` of a training loader over ``self.store``"""
-        self.rank, self.world = (int(rank), int(world)) if self.store.shard is None else self.store.shard
-        if not 0 <= self.rank < self.world:
-            raise ValueError(f'rank {rank} of a world of {world}')
-        self.sharded = self.store.sharded
-        if self.sharded:
-            self.iters = _sharded_iters(self.store, self.batch_size, self.rank)
-        else:
-            self.iters = len(self.store) // (self.batch_size * self.world)
-            assert self.iters >= 1, f'fewer {what} than one batch'
-
-    def _epoch(self, epoch):
-        """(random state, sample order, samples drawn per step, the rows of a step that this rank keeps) of an epoch"""
-        if self.sharded:
-            rs = _shard_state(self.seed, epoch, self.rank)
-            return rs, self.store.owned_samples[rs.permutation(len(self.store.owned_samples))], self.batch_size, slice(None)
-        rs = np.random.RandomState((self.seed * 1_000_003 + epoch) % (1 << 32))
-        return rs, rs.permutation(len(self.store)), self.batch_size * self.world, slice(self.rank, None, self.world)
-
-    def __len__(self):
-        return self.iters
-
-    def close_mosaic(self):
-        pass
-
-    def batches(self, epoch):
-        """[(sample indices int64 [B], params int32 [B, 5], box permutations int32 [B, P])] of an epoch; P = the store's largest group (at
-        least 1), a row of a smaller group is filled up with the identity"""
-        rs, order, drawn, keep = self._epoch(epoch)
-        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
-        P = max(self.store.max_group_rows, 1)
-        out = []
-        for i in range(self.iters):
-            idx = order[i * drawn:(i + 1) * drawn].astype(np.int64)
-            par = np.empty((len(idx), 5), dtype=np.int32)
-            perm = np.tile(np.arange(P, dtype=np.int32), (len(idx), 1))
-            for b, s in enumerate(idx):
-                par[b] = jitter_params(H, W, Hc, Wc, jitter=.3, rng=rs)
-                n = int(self.store.group_rows[s])
-                perm[b, :n] = rs.permutation(n)
-            out.append(tuple(np.ascontiguousarray(a[keep]) for a in (idx, par, perm)))
-        return out
-
-    def __iter__(self):
-        dev = self.store.device
-        draws = self.batches(self.epoch)
-        self.epoch += 1
-        for idx, par, perm in draws:
-            self.store.check_owned(idx)
-            idx, par, perm = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev), torch.from_numpy(perm).to(dev)
-            yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, perm, self.exp.input_size, self.max_labels)
+    def make_store(self, exp):
+        return gen1_store_for(exp)
 
 
-class Gen1StoreEvalLoader:
+class Gen1StoreEvalLoader(_StoreEvalLoader):
     """Evaluation loader over a ``Gen1Store``: iterable of the tuple ``SyntheticEvalLoader`` yields -- ``(frames [B, Tl, Tm, 2, H, W] fp32
     on the GPU, labels [B][n, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
     get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``); the labels are the raw float32 rows of the store
@@ -1199,32 +1341,10 @@ class Gen1StoreEvalLoader:
     the batches behind the last sample are empty (B = 0: no frames, no labels, no ids) -- what the ranks of a sharded evaluation, which
     own different numbers of samples, are padded with where an evaluator meets the other ranks once per batch."""
 
-    def __init__(self, exp, batch_size, indices, store, min_batches=0):
-        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
+    Dataset = Gen1StoreDataset
+
+    def check(self, exp):
         exp_aggregation(exp)
-        store.check_owned(self.indices)
-        self.dataset = Gen1StoreDataset(exp, store)
-        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
-
-    def __len__(self):
-        return max((len(self.indices) + self.batch_size - 1) // self.batch_size, self.min_batches)
-
-    def _empty(self):
-        """a batch without samples"""
-        frames = torch.zeros((0, getattr(self.store, 'Tl', 1), self.exp.Tm, 2) + tuple(self.exp.test_size), device=self.store.device)
-        return frames, [], (torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)), torch.zeros(0, dtype=torch.int64)
-
-    def __iter__(self):
-        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
-        row = letterbox_params(H, W, Hc, Wc)
-        for b in range(len(self)):
-            ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
-            if not ids:
-                yield self._empty()
-                continue
-            idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
-            frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
-            yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
 
 
 # ------------------------------------------------------------------------------------------------ 1 Mpx from recordings resident in HBM
@@ -1271,7 +1391,7 @@ def _h5_representations(rep_dir):
     return h5py.File(os.path.join(rep_dir, 'event_representations_ds2_nearest.h5'), 'r')['data']
 
 
-class Gen4Store(_Sharded):
+class Gen4Store(_Store):
     """1 Mpx (Gen4, RVT pre-processed) recordings and their labels resident on the device: what RVTGEN4Dataset keeps on disk and in host lists
     (rvt_gen4.py:93-97, 365-409), as tables that the kernels index.  ``recordings``: a list of ``(name, representations,
     objframe_idx_2_repr_idx, label_rows, objframe_idx_2_label_idx, label_times)`` -- ``representations`` is anything that has a length and
@@ -1304,7 +1424,7 @@ class Gen4Store(_Sharded):
     ``held_lo`` int64 [G] that ``frames`` gathers: ``group_first`` / ``group_lo`` moved to the recording's place in ``sums``; a sample that
     is not owned has ``held_first = -num_slice``, ``held_lo = 0``: every slice lies in front of its recording and is zero.  Without
     ``owned`` / ``shard`` the held tables are the group tables themselves.  ``owned_samples``, ``owns``, ``shard``, ``sample_rank``: see
-    ``_Sharded``."""
+    ``_Store``."""
 
     def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, owned=None, shard=None):
         self.num_slice, self.sensor_hw, self.nbins = int(num_slice), (int(sensor_hw[0]), int(sensor_hw[1])), int(nbins)
@@ -1345,18 +1465,13 @@ class Gen4Store(_Sharded):
                 group_first.append(int(rvt_first_index(obj2repr, k, self.num_slice, offset)))
                 group_lo.append(offset)
                 self.sample_names.append(f'{name}_n{self.num_slice}_a{int(label_times[k])}')
-        self.host = dict(rep_offsets=np.asarray(rep_offsets, dtype=np.int64), group_first=np.asarray(group_first, dtype=np.int64),
-                         group_lo=np.asarray(group_lo, dtype=np.int64),
-                         boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
-                         group_start=np.asarray(group_start, dtype=np.int64))
-        self.group_rows = np.diff(self.host['group_start'])
-        self.max_group_rows = int(self.group_rows.max()) if len(self.group_rows) else 0
         self.device = torch.device(device)
-        for k, v in self.host.items():
-            setattr(self, k, torch.from_numpy(v).to(self.device))
-        file_owned = np.array([owned is None or n in owned for n in self.names], dtype=bool)
+        self._set_tables(dict(rep_offsets=np.asarray(rep_offsets, dtype=np.int64), group_first=np.asarray(group_first, dtype=np.int64),
+                              group_lo=np.asarray(group_lo, dtype=np.int64),
+                              boxes=np.concatenate(boxes).astype(np.float32) if boxes else np.zeros((0, 5), np.float32),
+                              group_start=np.asarray(group_start, dtype=np.int64)))
         self.group_file = group_file = np.asarray(group_file, dtype=np.int64)                # (host: the recording of every sample)
-        self._set_owner(file_owned[group_file], shard, None if ranks is None else np.array([ranks[n] for n in self.names], dtype=np.int32)[group_file])
+        self._set_owners(self.names, group_file, owned, ranks, shard)
         self.held_offsets = np.asarray(held_offsets, dtype=np.int64)
         self.held_first, self.held_lo = self.group_first, self.group_lo
         if self.sharded:
@@ -1403,19 +1518,8 @@ class Gen4Store(_Sharded):
         owned, ranks = _shard_plan([r[0] for r in listed], [int(r[2][-1]) + 1 if len(r[2]) else 0 for r in listed], shard, None)
         recs = [(r[0], read(r[1]) if owned is None or r[0] in owned else None) + r[2:] for r in listed]
         store = cls(recs, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk, owned=owned)
-        store._adopt(shard, ranks, store.names, store.group_file)
+        store._adopt(shard, ranks)
         return store
-
-    def __len__(self):
-        return len(self.sample_names)
-
-    def raw_labels(self, index):
-        """float32 [n, 5] rows (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands them out (``map_val``,
-        ``format='xywh'``, rvt_gen4.py:227-230: ``xyxy2xywh`` of the raw boxes -- rescaled by extract_labels, not transformed)"""
-        a, b = self.host['group_start'][index], self.host['group_start'][index + 1]
-        box = self.host['boxes'][a:b].copy()
-        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
-        return box
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, 1, num_slice, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): ``group_first`` and
@@ -1434,12 +1538,6 @@ class Gen4Store(_Sharded):
     def _frames_from(self, first, lo, Hc, Wc, params):
         """the frame operator of this store's form on gathered indices"""
         return ops.count_store_frames(self.sums, first, self.num_slice, Hc, Wc, lo=lo, params=params)
-
-    def targets(self, sample_idx, params, perm, canvas_hw, max_labels=50, return_info=False):
-        """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params`` and the
-        box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
-        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
-                                 canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
 
 
 class Gen4PackedStore(Gen4Store):
@@ -1471,11 +1569,10 @@ class Gen4PackedStore(Gen4Store):
         if self.capacity_bytes is None:
             u16_bytes = R * 2 * H * ((W + 15) // 16) * 32
             self.capacity_bytes = min(u16_bytes, int(0.8 * torch.cuda.mem_get_info(self.device)[0]))
-        self.capacity_bytes = max(self.capacity_bytes, 0) // 16 * 16
+        arena = self._arena = _Arena(max(self.capacity_bytes, 0), 16, self.device)
+        self.capacity_bytes = arena.capacity_bytes
         self.rows = torch.empty((R, 2, H, 3), dtype=torch.int64, device=self.device)
-        self._arena = torch.empty(self.capacity_bytes, dtype=torch.uint8, device=self.device)
         scratch = torch.empty((min(chunk, max([len(r) for r in reps], default=0)), 2, H, W), dtype=torch.uint16, device=self.device)
-        units, needed, full = 0, 0, False
         for rep, offset in zip(reps, held_offsets):
             for a in range(0, len(rep), chunk):
                 part = torch.from_numpy(np.ascontiguousarray(rep[a:a + chunk], dtype=np.uint8)).to(self.device)
@@ -1483,17 +1580,14 @@ class Gen4PackedStore(Gen4Store):
                 sums = ops.stacked_hist_bin_sums(part, self.nbins, out=scratch[:n])
                 del part
                 try:
-                    took = ops.count_rows_pack(sums, self.rows[offset + a:offset + a + n], self._arena, units, dry_run=full)
+                    took = ops.count_rows_pack(sums, self.rows[offset + a:offset + a + n], arena.buf, arena.units, dry_run=arena.full)
                 except ops.PackedArenaFull as e:                # too small: go on measuring, store nothing more
-                    took, full = e.units, True
-                needed += took
-                units += 0 if full else took
-        if full:
-            del self._arena, self.rows
+                    took, arena.full = e.units, True
+                arena.place(took)
+        if arena.full:
             self.rows = None
-            raise ValueError(f'the packed rows of these recordings need {needed * 16} bytes, the arena holds {self.capacity_bytes} (capacity_bytes)')
-        self.used_bytes = units * 16
-        self.payload = self._arena[:self.used_bytes]
+        self.payload = arena.close('packed rows')
+        self.used_bytes = arena.used_bytes
 
     @property
     def nbytes(self):
@@ -1501,10 +1595,8 @@ class Gen4PackedStore(Gen4Store):
         return self.rows.numel() * 8 + self.used_bytes
 
     def trim(self):
-        """reallocate ``payload`` to the used size and let the arena go (the two exist side by side for the time of the copy)"""
-        if self.capacity_bytes != self.used_bytes:
-            self.payload = self.payload.clone()
-            self._arena, self.capacity_bytes = self.payload, self.used_bytes
+        """give back what the arena does not use: ``payload`` is reallocated at its size (``_Arena.trim``)"""
+        self.payload, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
         return self
 
     def unpacked(self, a, b):
@@ -1528,37 +1620,28 @@ def hist_store_for(exp, split='train', device=None):
     ``exp.store_shard`` = ``'recordings'``: the store of this rank.  ``exp.store_sums`` (default ``'u16'``) = ``'packed'``: a
     ``Gen4PackedStore``; any other value raises ValueError.  Kept on the experiment: one store per (split, rank, world, store_shard,
     store_sums)."""
-    import os
     kind = getattr(exp, 'store_sums', 'u16')
     if kind not in STORE_SUMS:
         raise ValueError(f'store_sums must be one of {STORE_SUMS}, got {kind!r}')
     cls = Gen4PackedStore if kind == 'packed' else Gen4Store
-    cache = exp.__dict__.setdefault('_hist_stores', {})
-    shard = exp_store_shard(exp)
-    split, name = _store_key(exp, split) + (kind,), split
-    if split not in cache:
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
-        nbins, factor = int(getattr(exp, 'nbins', 10)), getattr(exp, 'down_sample_factor', 2)
-        root = str(getattr(exp, 'data_dir', '') or '')
-        dirs = [os.path.join(root, d) for d in (('test',) if name == 'test' else ('train', 'val'))]
-        if root and all(os.path.isdir(d) for d in dirs):
-            cache[split] = cls.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard)
-        else:
-            n_files, n_reps = getattr(exp, 'store_recordings', (2, 24))[:2]
-            size = exp.test_size if name == 'test' else exp.input_size
-            sensor = (min(360, size[0]), min(640, size[1]))
-            recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(name == 'test'))
-            cache[split] = cls(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
-    return cache[split]
+    nbins, factor = int(getattr(exp, 'nbins', 10)), getattr(exp, 'down_sample_factor', 2)
+
+    def synthetic(device, shard):
+        n_files, n_reps = getattr(exp, 'store_recordings', (2, 24))[:2]
+        size = exp.test_size if split == 'test' else exp.input_size
+        sensor = (min(360, size[0]), min(640, size[1]))
+        recs = synth_gen4_recordings(n_files, n_reps, sensor, nbins, num_classes=max(int(exp.num_classes), 1), seed=int(split == 'test'))
+        return cls(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
+    return _store_for(exp, '_hist_stores', split, device, lambda: _data_dirs(exp, split),
+                      lambda dirs, device, shard: cls.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard),
+                      synthetic, more=(kind,))
 
 
-class Gen4StoreDataset(Gen1StoreDataset):
-    """what the trainer and the evaluators ask of a dataset, over a ``Gen4Store`` (``Gen1StoreDataset`` as it is: the sample names carry
-    the label time)"""
+class Gen4StoreDataset(_StoreDataset):
+    """``_StoreDataset`` over a ``Gen4Store``: the sample names carry the label time, as Gen1's do"""
 
 
-class Gen4StoreLoader(Gen1StoreLoader):
+class Gen4StoreLoader(_StoreLoader):
     """Training loader of the 1 Mpx path from a ``Gen4Store``: iterable of (frames [B, 1, Tm, 2, Hc, Wc] fp32 on the GPU, targets [B, 50, 5]
     rows (cls, cx, cy, w, h), zero padded).  The epochs, the draws and the step are ``Gen1StoreLoader``'s: an epoch is a permutation of the
     samples; per sample ``jitter_params(..., jitter=.3)``, then ``rng.permutation(n)`` of its boxes, in get_random_data's order
@@ -1566,25 +1649,19 @@ class Gen4StoreLoader(Gen1StoreLoader):
     else.  ``exp.aggregation`` is not consulted, as in ``SyntheticStackedHistLoader``.  ``store=None``: ``hist_store_for(exp)``.  ``rank``,
     ``world`` and a sharded store: as in ``Gen1StoreLoader``."""
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
-        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
-        self.store = store if store is not None else hist_store_for(exp)
-        self._plan(rank, world, 'labels')
-        self.dataset = Gen4StoreDataset(exp, self.store)
-        self.epoch = 0
+    Dataset = Gen4StoreDataset
+
+    def make_store(self, exp):
+        return hist_store_for(exp)
 
 
-class Gen4StoreEvalLoader(Gen1StoreEvalLoader):
+class Gen4StoreEvalLoader(_StoreEvalLoader):
     """Evaluation loader over a ``Gen4Store``: iterable of the tuple ``Gen1StoreEvalLoader`` yields -- ``(frames [B, 1, Tm, 2, H, W] fp32 on
     the GPU, labels [B][n, 5] rows (x, y, w, h, cls), (heights, widths), ids)`` -- by that loader's own loop: ``letterbox_params`` of the
     sensor on ``exp.test_size``, the raw float32 rows of ``Gen4Store.raw_labels``, the sensor's sizes.  ``exp.aggregation`` is not
     consulted."""
 
-    def __init__(self, exp, batch_size, indices, store, min_batches=0):
-        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
-        store.check_owned(self.indices)
-        self.dataset = Gen4StoreDataset(exp, store)
-        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
+    Dataset = Gen4StoreDataset
 
 
 # ------------------------------------------------------------------------------------------------ N-Caltech101 from recordings resident in HBM
@@ -1631,7 +1708,7 @@ def synth_ncaltech_recordings(n_files, n_events, sensor_hw=(180, 240), n_classes
     return out
 
 
-class NCaltechStore(_Sharded):
+class NCaltechStore(_Store):
     """N-Caltech101 recordings and their boxes resident on the device: what NCaltech keeps on disk (ncaltech.py:43-61, 172-178), as tables that
     the kernels index.  ``recordings``: a list of ``(class_name, stem, atis_bytes, annotation_bytes)`` -- the byte images of
     ``Caltech101/<class>/<stem>.bin`` and its ``annotation`` file; recordings of ``BACKGROUND_Google`` are left out.  ``Tl``: macro slices per
@@ -1648,7 +1725,7 @@ class NCaltechStore(_Sharded):
     owned contributes its box, its name and a zero-length area to ``records`` / ``file_offsets``; its ``atis_bytes`` may be None and is
     never touched.  ``boxes``, ``group_start``, ``sample_names``, ``class_names``, ``raw_labels``, ``targets`` and the length are the same
     on every rank and the same as the unsharded store's; ``max_file_records`` is that of the owned recordings.  ``owned_samples``,
-    ``owns``, ``shard``, ``sample_rank``: see ``_Sharded``."""
+    ``owns``, ``shard``, ``sample_rank``: see ``_Store``."""
 
     def __init__(self, recordings, Tl, window, device, class_names=None, sensor_hw=(180, 240), owned=None, shard=None):
         self.Tl, self.sensor_hw = int(Tl), (int(sensor_hw[0]), int(sensor_hw[1]))
@@ -1672,15 +1749,12 @@ class NCaltechStore(_Sharded):
             file_offsets.append(file_offsets[-1] + len(buf) // 5)
             boxes.append(parse_ncaltech_annotation(ann) + (name_to_idx[cls],))
         F = len(self.sample_names)
-        self.host = dict(file_offsets=np.asarray(file_offsets, dtype=np.int64), boxes=np.asarray(boxes, dtype=np.float32).reshape(F, 5),
-                         group_start=np.arange(F + 1, dtype=np.int64))
-        self.max_file_records = int(np.diff(self.host['file_offsets']).max()) if F else 0
-        self._set_owner([owned is None or n in owned for n in self.sample_names], shard,
-                        None if ranks is None else [ranks[n] for n in self.sample_names])
         self.device = torch.device(device)
         self.records = torch.from_numpy(np.concatenate(areas) if areas else np.zeros(0, np.uint8)).to(self.device)
-        for k, v in self.host.items():
-            setattr(self, k, torch.from_numpy(v).to(self.device))
+        self._set_tables(dict(file_offsets=np.asarray(file_offsets, dtype=np.int64), boxes=np.asarray(boxes, dtype=np.float32).reshape(F, 5),
+                              group_start=np.arange(F + 1, dtype=np.int64)))
+        self.max_file_records = int(np.diff(self.host['file_offsets']).max()) if F else 0
+        self._set_owners(self.sample_names, np.arange(F), owned, ranks, shard)             # a recording is a sample
         # a store kept on the host is its tables only (names, boxes, offsets: what needs no GPU); the operators refuse its tensors
         self.index = ops.atis_store_index(self.records) if self.device.type == 'cuda' else None
 
@@ -1707,18 +1781,8 @@ class NCaltechStore(_Sharded):
         owned, ranks = _shard_plan(names, [os.path.getsize(r[2]) for r in listed] if shard is not None else (), shard, None)
         recs = [(c, stem, read_bin(path) if owned is None or n in owned else None, ann) for n, (c, stem, path, ann) in zip(names, listed)]
         store = cls(recs, Tl, window, device, class_names=class_names, sensor_hw=sensor_hw, owned=owned)
-        store._adopt(shard, ranks, store.sample_names, np.arange(len(store)))
+        store._adopt(shard, ranks)
         return store
-
-    def __len__(self):
-        return len(self.sample_names)
-
-    def raw_labels(self, index):
-        """float32 [1, 5] row (x, y, w, h, class) of sample ``index`` as the reference's evaluation hands it out (``map_val``,
-        ``format='xywh'``, ncaltech.py:199-202: ``xyxy2xywh`` of the raw box -- not transformed)"""
-        box = self.host['boxes'][index:index + 1].copy()
-        box[:, 2], box[:, 3] = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
-        return box
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): the store operator that
@@ -1726,18 +1790,16 @@ class NCaltechStore(_Sharded):
         letterbox; ``params``: (nw, nh, dx, dy, flip) per sample; ``canvas_hw``: ``exp.input_size`` unless given.  Nothing is read back
         (graph-capturable).  Precondition: the store holds the records of every sample asked for (``owns``; the loaders check their
         indices on the host before they upload them) -- a sample that is not owned has no records here."""
-        kind = _atis_choice((self.Tl, exp.Tm, self.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))[-1]
         op = {'latest': ops.event_latest_surface_atis_store, 'timesurface': ops.event_timesurface_atis_store,
-              'count': ops.event_histogram_atis_store}[kind]
+              'count': ops.event_histogram_atis_store}[_atis_kind(exp)]
         frames = op(self.records, self.file_offsets, self.index, sample_idx, self.Tl, exp.Tm, *self.sensor_hw, window=self.window,
                     max_file_records=self.max_file_records)
         return _letterboxed(frames, params, canvas_hw if canvas_hw is not None else exp.input_size, 'cubic')
 
     def targets(self, sample_idx, params, canvas_hw, max_labels=50, return_info=False):
         """[B, max_labels, 5] fp32 rows (cls, cx, cy, w, h), zero padded, of the samples ``sample_idx`` under the draws ``params``:
-        ``ops.label_targets`` on the store's box table (one box per sample: no permutation), one launch, nothing read back"""
-        return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
-                                 canvas_hw[0], canvas_hw[1], max_labels=max_labels, return_info=return_info)
+        ``_Store.targets`` without a permutation (one box per sample), one launch, nothing read back"""
+        return super().targets(sample_idx, params, None, canvas_hw, max_labels, return_info)
 
 
 def ncaltech_store_for(exp, split='train', device=None):
@@ -1746,108 +1808,50 @@ def ncaltech_store_for(exp, split='train', device=None):
     the sensor is N-Caltech101's, or the canvas where that is smaller).  ``exp.store_shard`` = ``'recordings'``: the store of this rank.
     Kept on the experiment: one store per (split, rank, world, store_shard)."""
     import os
-    cache = exp.__dict__.setdefault('_atis_stores', {})
-    shard = exp_store_shard(exp)
-    split, name = _store_key(exp, split), split
-    if split not in cache:
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
-        window = (exp.window * 1000, 0) if getattr(exp, 'window', None) is not None else None
-        root = str(getattr(exp, 'data_dir', '') or '')
-        if root and os.path.isfile(os.path.join(root, name + '.txt')):
-            cache[split] = NCaltechStore.from_directory(root, name, exp.Tl, window, device, shard=shard)
-        else:
-            n_files, n_events = getattr(exp, 'atis_store_recordings', (16, 20_000))
-            size = exp.input_size if name == 'train' else exp.test_size
-            sensor = (min(180, size[0]), min(240, size[1]))
-            n_classes = max(int(exp.num_classes), 1)
-            recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(name != 'train'))
-            cache[split] = NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor,
-                                         shard=shard)
-    return cache[split]
+    window = (exp.window * 1000, 0) if getattr(exp, 'window', None) is not None else None
+    root = str(getattr(exp, 'data_dir', '') or '')
+
+    def synthetic(device, shard):
+        n_files, n_events = getattr(exp, 'atis_store_recordings', (16, 20_000))
+        size = exp.input_size if split == 'train' else exp.test_size
+        sensor = (min(180, size[0]), min(240, size[1]))
+        n_classes = max(int(exp.num_classes), 1)
+        recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(split != 'train'))
+        return NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor, shard=shard)
+    return _store_for(exp, '_atis_stores', split, device, lambda: root and os.path.isfile(os.path.join(root, split + '.txt')) and root,
+                      lambda root, device, shard: NCaltechStore.from_directory(root, split, exp.Tl, window, device, shard=shard), synthetic)
 
 
-class NCaltechStoreDataset:
-    """what the trainer and the evaluators ask of a dataset, over an ``NCaltechStore``: length, ``sample_names``, ``class_names``, ``map_val``
-    without random augmentation"""
-    map_val, random_aug = True, False
+class NCaltechStoreDataset(_StoreDataset):
+    """``_StoreDataset`` over an ``NCaltechStore``: the class names are the store's"""
 
-    def __init__(self, exp, store):
-        self.exp, self.store, self.sample_names, self.class_names = exp, store, store.sample_names, store.class_names
-
-    def __len__(self):
-        return len(self.store)
+    def _class_names(self):
+        return self.store.class_names
 
 
-class NCaltechStoreLoader:
+class NCaltechStoreLoader(_StoreLoader):
     """Training loader of N-Caltech101 from an ``NCaltechStore``: iterable of (frames [B, Tl, Tm, 2, Hc, Wc] fp32 on the GPU, targets
     [B, 50, 5] rows (cls, cx, cy, w, h), zero padded).  An epoch is a permutation of the samples; per sample the draws come in the reference's
-    order (NCaltech.get_random_data, ncaltech.py:330-350): ``jitter_params(..., jitter=.1)`` and nothing else -- ``np.random.shuffle`` of the
-    sample's single box consumes no random state.  ``batches(epoch)`` returns the draws of an epoch, a function of (seed, epoch) alone; a
-    step uploads them -- sample indices and params -- and everything else happens on the device (``store.frames``, ``store.targets``): no
-    host read, no per-sample work.  ``store=None``: ``ncaltech_store_for(exp)``.  ``rank``, ``world`` and a sharded store: the rules of
+    order (NCaltech.get_random_data, ncaltech.py:330-350): ``jitter_params(..., jitter=.1)`` and nothing else (``permutes`` is False:
+    the reference's ``np.random.shuffle`` of the sample's single box consumes no random state, so none is drawn here).
+    ``batches(epoch)`` returns the draws of an epoch, a function of (seed, epoch) alone; a step uploads them -- sample indices and
+    params -- and everything else happens on the device (``store.frames``, ``store.targets``): no host read, no per-sample work.  ``store=None``: ``ncaltech_store_for(exp)``.  ``rank``, ``world`` and a sharded store: the rules of
     ``Gen1StoreLoader`` (rows ``rank::world`` of the global batch / a permutation of the owned samples from ``_shard_state``; the index
     check before the upload)."""
-    _plan, _epoch = Gen1StoreLoader._plan, Gen1StoreLoader._epoch
+    jitter, permutes, what, Dataset = .1, False, 'recordings', NCaltechStoreDataset
 
-    def __init__(self, exp, batch_size, store=None, seed=0, max_labels=50, rank=0, world=1):
-        self.exp, self.batch_size, self.seed, self.max_labels = exp, batch_size, seed, max_labels
-        self.store = store if store is not None else ncaltech_store_for(exp)
-        _atis_choice((self.store.Tl, exp.Tm, self.store.sensor_hw, (0, 0)), getattr(exp, 'measure', None), getattr(exp, 'aggregation', None))
-        self._plan(rank, world, 'recordings')
-        self.dataset = NCaltechStoreDataset(exp, self.store)
-        self.epoch = 0
+    def check(self, exp):
+        _atis_kind(exp)
 
-    def __len__(self):
-        return self.iters
-
-    def close_mosaic(self):
-        pass
-
-    def batches(self, epoch):
-        """[(sample indices int64 [B], params int32 [B, 5])] of an epoch"""
-        rs, order, drawn, keep = self._epoch(epoch)
-        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.input_size
-        out = []
-        for i in range(self.iters):
-            idx = order[i * drawn:(i + 1) * drawn].astype(np.int64)
-            par = np.array([jitter_params(H, W, Hc, Wc, jitter=.1, rng=rs) for _ in idx], dtype=np.int32).reshape(len(idx), 5)
-            out.append(tuple(np.ascontiguousarray(a[keep]) for a in (idx, par)))
-        return out
-
-    def __iter__(self):
-        dev = self.store.device
-        draws = self.batches(self.epoch)
-        self.epoch += 1
-        for idx, par in draws:
-            self.store.check_owned(idx)
-            idx, par = torch.from_numpy(idx).to(dev), torch.from_numpy(par).to(dev)
-            yield self.store.frames(idx, par, self.exp), self.store.targets(idx, par, self.exp.input_size, self.max_labels)
+    def make_store(self, exp):
+        return ncaltech_store_for(exp)
 
 
-class NCaltechStoreEvalLoader:
+class NCaltechStoreEvalLoader(_StoreEvalLoader):
     """Evaluation loader over an ``NCaltechStore``: iterable of the tuple ``Gen1StoreEvalLoader`` yields -- ``(frames [B, Tl, Tm, 2, H, W]
     fp32 on the GPU, labels [B][1, 5] rows (x, y, w, h, cls), (heights, widths), ids)``.  The frames go through the deterministic branch of
     get_random_data (``letterbox_params`` of the sensor on ``exp.test_size``, the cubic resize: N-Caltech101 resizes in evaluation too); the
     labels are the raw float32 rows of the store (``NCaltechStore.raw_labels``), prepared on the host once; the sizes are the sensor's and
     the ids index ``sample_names``.  ``indices`` are this rank's samples; the last batch may be short.  The index check and ``min_batches``
     are ``Gen1StoreEvalLoader``'s."""
-    __len__, _empty = Gen1StoreEvalLoader.__len__, Gen1StoreEvalLoader._empty
-
-    def __init__(self, exp, batch_size, indices, store, min_batches=0):
-        self.exp, self.batch_size, self.indices, self.store, self.min_batches = exp, batch_size, list(indices), store, int(min_batches)
-        store.check_owned(self.indices)
-        self.dataset = NCaltechStoreDataset(exp, store)
-        self.labels = {i: torch.from_numpy(store.raw_labels(i)) for i in set(self.indices)}
-
-    def __iter__(self):
-        (H, W), (Hc, Wc) = self.store.sensor_hw, self.exp.test_size
-        row = letterbox_params(H, W, Hc, Wc)
-        for b in range(len(self)):
-            ids = self.indices[b * self.batch_size:(b + 1) * self.batch_size]
-            if not ids:
-                yield self._empty()
-                continue
-            idx = torch.tensor(ids, dtype=torch.int64).to(self.store.device)
-            frames = self.store.frames(idx, [row] * len(ids), self.exp, canvas_hw=(Hc, Wc))
-            yield frames, [self.labels[i] for i in ids], (torch.full((len(ids),), H), torch.full((len(ids),), W)), torch.tensor(ids)
+    Dataset = NCaltechStoreDataset
