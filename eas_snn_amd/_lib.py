@@ -170,6 +170,7 @@ PROTOTYPES = {
     'eas_event_window_search': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P]),
     'eas_event_histogram_dat_ranges': (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P, _P]),
     'eas_records_gather': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    'eas_bytes_digest': (C.c_int, [_P, C.c_longlong, _P, _P]),
     'eas_records_pack_measure': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     'eas_records_pack': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_int64, _P]),
     'eas_records_unpack': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),

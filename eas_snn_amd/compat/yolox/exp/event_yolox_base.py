@@ -27,6 +27,8 @@ _DEFAULTS = dict(
     save_history_ckpt=False,
     test_size=(640, 640), test_conf=0.01, nmsthre=0.65,
     store_events='dat',      # not the reference's: how a window store of train_input = 'dat_store' keeps its records (data.STORE_EVENTS)
+    store_cache=None,        # not the reference's: a directory that keeps the stores of train_input = '*_store' as snapshots, read back instead of
+                             # built where they are current (data._store_for, data.load_store); None: every run builds its stores
 )
 
 # The values of ``train_input`` that train from recordings resident in HBM (sample indices -> frames and targets on the device), each with the

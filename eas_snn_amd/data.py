@@ -567,6 +567,10 @@ class _Store:
     built for or None; ``sample_rank`` int32 [G]: the rank that holds every sample's records (None unless built with ``shard=``: with
     ``owned=`` alone the store knows its own recordings only)."""
     shard, sample_rank = None, None
+    # what a snapshot (``save`` / ``load_store``) keeps of a store beside ``host``, the names and the owners: the names of its attributes
+    # that are ``scalars`` (numbers, None, tuples of numbers), ``lists`` (of strings), ``host`` (numpy arrays) and ``device`` (the tensors on
+    # ``self.device`` its ``frames`` reads; one that is None is left out).  A class states its own; ``_loaded`` sets what follows from them.
+    _snapshot_fields = dict(scalars=(), lists=(), host=(), device=())
 
     def _set_tables(self, host):
         """``host`` (a dict of numpy tables with ``group_start`` among them), ``group_rows``, ``max_group_rows``, and every table uploaded
@@ -582,7 +586,7 @@ class _Store:
         whose records are here (None = all); ``ranks``: {name: rank} or None; ``shard``: (rank, world) or None -> ``owned_samples``,
         ``sample_rank``, ``shard``"""
         sample_file = np.asarray(sample_file, dtype=np.int64).reshape(-1)
-        self._owner_args = (names, sample_file, owned)
+        self._owner_args, self._owner_ranks = (names, sample_file, owned), ranks
         self._sample_owned = np.array([owned is None or n in owned for n in names], dtype=bool)[sample_file]
         self.owned_samples = np.flatnonzero(self._sample_owned).astype(np.int64)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
@@ -630,6 +634,232 @@ class _Store:
         box permutations ``perm`` (int32 [B, P] or None): ``ops.label_targets`` on the store's box table, one launch, nothing read back"""
         return ops.label_targets(self.boxes, self.group_start, sample_idx, params_on(params, self.device), self.sensor_hw[0], self.sensor_hw[1],
                                  canvas_hw[0], canvas_hw[1], perm=perm, max_labels=max_labels, return_info=return_info)
+
+    def _snapshot_sections(self):
+        """[(name, 'host' | 'device', numpy array | tensor)]: the arrays of ``host``, the host arrays the class names, the recording of every
+        sample (``_set_owners``' argument), then the device tensors the class names, each at its used size"""
+        fields = self._snapshot_fields
+        out = [(k, 'host', np.ascontiguousarray(v)) for k, v in self.host.items()]
+        out += [(k, 'host', np.ascontiguousarray(getattr(self, k))) for k in fields['host']]
+        out.append(('sample_file', 'host', np.ascontiguousarray(self._owner_args[1])))
+        return out + [(k, 'device', getattr(self, k)) for k in fields['device'] if getattr(self, k) is not None]
+
+    def save(self, path, key=None, chunk_bytes=None):
+        """The store as one snapshot file that ``load_store`` reads back without any of the build's kernels (DESIGN section 3l states the
+        format): the magic, a format version, the length of the header, a JSON header -- class, geometry, counters, names, owners, ``key``
+        (what ``exp.store_cache`` compares; None outside it) and per section name, dtype, shape, file offset, byte length, place and
+        digest -- and the sections as raw little-endian bytes, each on a ``SNAPSHOT_ALIGN`` boundary.  A device section is digested on
+        the device (``ops.bytes_digest``), then copied out through one pinned staging buffer of at most ``chunk_bytes`` (None:
+        ``SNAPSHOT_CHUNK``).  Written to ``path + '.tmp'`` and moved over ``path`` when complete: a run that is killed leaves no half file
+        under the final name.  Returns ``path``."""
+        import json
+        import os
+        import struct
+        chunk_bytes = SNAPSHOT_CHUNK if chunk_bytes is None else int(chunk_bytes)
+        if chunk_bytes < 1:
+            raise ValueError(f'chunk_bytes = {chunk_bytes}')
+        fields, sections, entries = self._snapshot_fields, self._snapshot_sections(), []
+        for name, where, v in sections:
+            flat = torch.from_numpy(v).reshape(-1).view(torch.uint8) if where == 'host' else v.reshape(-1).view(torch.uint8)
+            dtype = v.dtype.str if where == 'host' else _snapshot_dtype_name(v.dtype)
+            entries.append(dict(name=name, where=where, dtype=dtype, shape=list(v.shape), offset=0, nbytes=flat.numel(),
+                                digest=[f'0x{w:016x}' for w in ops.bytes_digest_host(flat)]))
+        owner_names, _, owned = self._owner_args
+        header = {'class': type(self).__name__, 'format': SNAPSHOT_VERSION,
+                  'scalars': {k: getattr(self, k) for k in fields['scalars']}, 'lists': {k: list(getattr(self, k)) for k in fields['lists']},
+                  'host_tables': list(self.host), 'host_attrs': list(fields['host']),
+                  'names': getattr(self, 'names', None), 'sample_names': list(self.sample_names), 'shard': self.shard,
+                  'owners': dict(names=list(owner_names), owned=None if owned is None else sorted(owned), ranks=self._owner_ranks),
+                  'key': key, 'sections': entries}
+        base = SNAPSHOT_ALIGN
+        while True:                                             # the offsets stand in the header whose length moves them
+            at = base
+            for e in entries:
+                e['offset'] = at
+                at = _snapshot_aligned(at + e['nbytes'])
+            blob = json.dumps(header).encode('utf-8')
+            if len(SNAPSHOT_MAGIC) + 12 + len(blob) <= base:
+                break
+            base += SNAPSHOT_ALIGN
+        device_bytes = [e['nbytes'] for e, (_, where, v) in zip(entries, sections) if where == 'device' and v.is_cuda]
+        stage = torch.empty(min(chunk_bytes, max(device_bytes)), dtype=torch.uint8, pin_memory=True) if any(device_bytes) else None
+        with open(path + '.tmp', 'wb') as f:                    # (a ``.tmp`` an interrupted save left behind is overwritten)
+            f.write(SNAPSHOT_MAGIC + struct.pack('<IQ', SNAPSHOT_VERSION, len(blob)) + blob)
+            for e, (_, where, v) in zip(entries, sections):
+                if e['nbytes'] == 0:
+                    continue
+                f.seek(e['offset'])
+                if where == 'host' or not v.is_cuda:
+                    f.write((v if where == 'host' else v.reshape(-1).view(torch.uint8).numpy()).data)
+                    continue
+                flat = v.reshape(-1).view(torch.uint8)
+                for a in range(0, flat.numel(), stage.numel()):
+                    n = min(stage.numel(), flat.numel() - a)
+                    stage[:n].copy_(flat[a:a + n])              # (blocking: the buffer is read by the write that follows)
+                    f.write(stage[:n].numpy().data)
+        os.replace(path + '.tmp', path)
+        return path
+
+    def _loaded(self):
+        """the end of ``load_store``: what follows from the fields a snapshot holds (a class adds its own)"""
+
+
+SNAPSHOT_MAGIC, SNAPSHOT_VERSION, SNAPSHOT_ALIGN = b'EASSTORE', 1, 4096
+SNAPSHOT_CHUNK = 256 << 20                     # bytes of a pinned staging buffer of ``save`` / ``load_store`` unless ``chunk_bytes`` says otherwise
+_SNAPSHOT_DTYPES = {'|u1': torch.uint8, '<u2': torch.uint16, '<i4': torch.int32, '<i8': torch.int64, '<f4': torch.float32}
+
+
+class SnapshotError(ValueError):
+    """a snapshot file that is not what was written: a wrong magic or version, a file shorter than its header says, a byte length or a
+    digest that does not match.  The message names the file and, where one is at fault, the section."""
+
+
+def _snapshot_aligned(n):
+    return (n + SNAPSHOT_ALIGN - 1) // SNAPSHOT_ALIGN * SNAPSHOT_ALIGN
+
+
+def _snapshot_dtype_name(dtype):
+    for name, t in _SNAPSHOT_DTYPES.items():
+        if t == dtype:
+            return name
+    raise ValueError(f'a snapshot holds no tensors of {dtype}')
+
+
+def _store_classes(base=None):
+    """{name: class} of ``_Store``'s subclasses"""
+    out = {}
+    for c in (_Store if base is None else base).__subclasses__():
+        out[c.__name__] = c
+        out.update(_store_classes(c))
+    return out
+
+
+def read_snapshot_header(path):
+    """the JSON header of the snapshot ``path`` as a dict, checked as far as it goes without reading a section: magic, version, the
+    header's own length, every section's byte length against its dtype and shape and its place against the file's size; ``SnapshotError``
+    otherwise"""
+    import json
+    import os
+    import struct
+    size = os.path.getsize(path)
+    with open(path, 'rb') as f:
+        head = f.read(len(SNAPSHOT_MAGIC) + 12)
+        if len(head) < len(SNAPSHOT_MAGIC) + 12 or head[:len(SNAPSHOT_MAGIC)] != SNAPSHOT_MAGIC:
+            raise SnapshotError(f'{path}: not a store snapshot (the magic is {head[:len(SNAPSHOT_MAGIC)]!r}, not {SNAPSHOT_MAGIC!r})')
+        version, length = struct.unpack('<IQ', head[len(SNAPSHOT_MAGIC):])
+        if version != SNAPSHOT_VERSION:
+            raise SnapshotError(f'{path}: snapshot format version {version}, this code reads version {SNAPSHOT_VERSION}')
+        if len(head) + length > size:
+            raise SnapshotError(f'{path}: the file holds {size} bytes, its header alone needs {len(head) + length}')
+        try:
+            header = json.loads(f.read(length).decode('utf-8'))
+        except ValueError as e:
+            raise SnapshotError(f'{path}: the header is not JSON ({e})') from e
+    missing = [k for k in ('class', 'scalars', 'lists', 'host_tables', 'host_attrs', 'names', 'sample_names', 'shard', 'owners', 'key', 'sections')
+               if not isinstance(header, dict) or k not in header]
+    if missing:
+        raise SnapshotError(f'{path}: the header lacks {missing}')
+    for e in header['sections']:
+        want = int(np.prod(e['shape'], dtype=np.int64)) * np.dtype(e['dtype']).itemsize
+        if e['nbytes'] != want:
+            raise SnapshotError(f"{path}: section {e['name']!r} states {e['nbytes']} bytes, {e['dtype']} {e['shape']} takes {want}")
+        if e['nbytes'] and (e['offset'] % SNAPSHOT_ALIGN or e['offset'] + e['nbytes'] > size):
+            raise SnapshotError(f"{path}: section {e['name']!r} lies at {e['offset']} .. {e['offset'] + e['nbytes']}, the file holds {size} bytes")
+    return header
+
+
+def _read_host_section(f, path, e):
+    """a section as a numpy array, read in one piece and digested by the numpy path"""
+    raw = np.empty(e['nbytes'], dtype=np.uint8)
+    f.seek(e['offset'])
+    if e['nbytes'] and f.readinto(raw.data) != e['nbytes']:
+        raise SnapshotError(f"{path}: section {e['name']!r} ends before its {e['nbytes']} bytes")
+    return raw.view(np.dtype(e['dtype'])).reshape(e['shape'])
+
+
+def _read_device_section(f, path, e, device, chunk_bytes):
+    """a section as a tensor on the GPU ``device``, allocated at its exact size and filled from two pinned staging buffers used alternately:
+    the file read of chunk k + 1 overlaps the upload of chunk k (``copy_(non_blocking=True)`` on a side stream; the event of a buffer's
+    last upload is waited for before the buffer is read into again).  Peak host memory: two chunks."""
+    n = e['nbytes']
+    flat = torch.empty(n, dtype=torch.uint8, device=device)
+    if n:
+        chunk = min(int(chunk_bytes), n)
+        stage = [torch.empty(chunk, dtype=torch.uint8, pin_memory=True) for _ in range(min(2, (n + chunk - 1) // chunk))]
+        done = [None] * len(stage)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))     # (the allocation's earlier life on the current stream is over first)
+        f.seek(e['offset'])
+        for k, a in enumerate(range(0, n, chunk)):
+            b, m = k % len(stage), min(chunk, n - a)
+            if done[b] is not None:
+                done[b].synchronize()
+            if f.readinto(stage[b][:m].numpy().data) != m:
+                raise SnapshotError(f"{path}: section {e['name']!r} ends before its {n} bytes")
+            with torch.cuda.stream(side):
+                flat[a:a + m].copy_(stage[b][:m], non_blocking=True)
+                done[b] = torch.cuda.Event()
+                done[b].record(side)
+        torch.cuda.current_stream(device).wait_stream(side)
+        for ev in done:                                         # the staging buffers go back to the allocator: their uploads are over first
+            if ev is not None:
+                ev.synchronize()
+    return flat.view(_SNAPSHOT_DTYPES[e['dtype']]).reshape(e['shape'])
+
+
+def load_store(path, device, chunk_bytes=None, expect_shard='any'):
+    """The store that ``save`` wrote to ``path``, on ``device``, without any of the build's kernels: the class is the header's; the host
+    tables are read with numpy and uploaded as ``_set_tables`` uploads them; every device section is allocated at its exact size, filled
+    through two pinned staging buffers of at most ``chunk_bytes`` (None: ``SNAPSHOT_CHUNK``; ``_read_device_section``), digested on the
+    device and compared with the header.  Peak device memory is the store itself.  ``device='cpu'``: every section is read with numpy and
+    digested by the numpy path.  The store equals the built and trimmed one in everything the loaders, the evaluators, ``frames``,
+    ``targets``, ``raw_labels``, ``owns`` and ``check_owned`` read; ``capacity_bytes == used_bytes``, ``trim()`` returns the store, there
+    is no arena.  It keeps the ``shard`` and the owners it was built with: ``expect_shard`` = a ``(rank, world)`` or None raises
+    ``SnapshotError`` when they differ.  ``SnapshotError`` (a ValueError) as well for a file that is not what ``save`` wrote."""
+    path, device = str(path), torch.device(device)
+    chunk_bytes = SNAPSHOT_CHUNK if chunk_bytes is None else int(chunk_bytes)
+    if chunk_bytes < 1:
+        raise ValueError(f'chunk_bytes = {chunk_bytes}')
+    header = read_snapshot_header(path)
+    cls = _store_classes().get(header['class'])
+    if cls is None:
+        raise SnapshotError(f"{path}: the snapshot of a {header['class']!r}, which is no store class")
+    shard = None if header['shard'] is None else (int(header['shard'][0]), int(header['shard'][1]))
+    if expect_shard != 'any' and shard != (None if expect_shard is None else (int(expect_shard[0]), int(expect_shard[1]))):
+        raise SnapshotError(f'{path}: the snapshot of shard {shard}, expected {expect_shard}')
+    store = cls.__new__(cls)
+    store.device = device
+    for k, v in header['scalars'].items():
+        setattr(store, k, tuple(v) if isinstance(v, list) else v)
+    for k, v in header['lists'].items():
+        setattr(store, k, list(v))
+    if header['names'] is not None:
+        store.names = list(header['names'])
+    store.sample_names = list(header['sample_names'])
+    got = {}
+    with open(path, 'rb') as f:
+        for e in header['sections']:
+            on_gpu = e['where'] == 'device' and device.type == 'cuda'
+            if on_gpu:
+                got[e['name']] = _read_device_section(f, path, e, device, chunk_bytes)
+                words = ops.bytes_digest_host(got[e['name']])
+            else:
+                got[e['name']] = _read_host_section(f, path, e)
+                words = ops.bytes_digest_host(torch.from_numpy(got[e['name']]).reshape(-1).view(torch.uint8))
+                if e['where'] == 'device':
+                    got[e['name']] = torch.from_numpy(got[e['name']].view(np.uint8)).view(_SNAPSHOT_DTYPES[e['dtype']]).reshape(e['shape'])
+            if [f'0x{w:016x}' for w in words] != e['digest']:
+                raise SnapshotError(f"{path}: section {e['name']!r} has the digest {[f'0x{w:016x}' for w in words]}, the header states "
+                                    f"{e['digest']}: these are not the bytes that were written")
+    store._set_tables({k: got[k] for k in header['host_tables']})
+    for k in header['host_attrs']:
+        setattr(store, k, got[k])
+    own = header['owners']
+    store._set_owners(own['names'], got['sample_file'], None if own['owned'] is None else set(own['owned']), own['ranks'], shard)
+    for k in cls._snapshot_fields['device']:
+        setattr(store, k, got.get(k))
+    store._loaded()
+    return store
 
 
 class _Arena:
@@ -778,6 +1008,7 @@ class Gen1Store(_Store):
     sample index, ``raw_labels``, ``targets`` and the length are the same on every rank and the same as the unsharded store's -- and a
     zero-length area to ``records`` / ``file_offsets``; its ``dat_bytes`` may be None and is never touched.  ``owned_samples``, ``owns``,
     ``shard``, ``sample_rank``: see ``_Store``."""
+    _snapshot_fields = dict(scalars=('Tl', 'window', 'sensor_hw'), lists=(), host=(), device=('records',))
 
     def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), owned=None, shard=None):
         self._set_geometry(Tl, window, device, sensor_hw)
@@ -866,6 +1097,12 @@ class Gen1Store(_Store):
         owned, ranks = _shard_plan([p[0] for p in pairs], [os.path.getsize(p[1]) for p in pairs] if shard is not None else (), shard, None)
         return pairs, owned, ranks
 
+    @classmethod
+    def _source_files(cls, paths, ignore, shard):
+        """the files ``from_directories`` with these arguments would open, from the listing alone: every ``_bbox.npy``, the owned ``_td.dat``"""
+        pairs, owned, _ = cls._listed(paths, ignore, shard)
+        return [box for _, _, box in pairs] + [dat for name, dat, _ in pairs if owned is None or name in owned]
+
     @staticmethod
     def _read(pairs, owned, read_dat=None):
         """the recordings ``(name, dat_bytes or None where not owned, bbox_rows)`` of the listed ``pairs``, read one at a time as they are
@@ -920,6 +1157,8 @@ class Gen1WindowStore(Gen1Store):
     ``kept_records`` count the owned recordings, so the ranks' ``kept_records`` add up to the unsharded store's.  ``shard=`` weighs a
     recording by ``len(dat_bytes)``, which is only a proxy for what its windows keep: the balance bound of ``shard_recordings`` holds
     for the bytes read at build time, not for the bytes held."""
+    _snapshot_fields = dict(Gen1Store._snapshot_fields, scalars=Gen1Store._snapshot_fields['scalars'] + ('total_records', 'kept_records', 'used_bytes'),
+                            device=('records', 'sample_ranges'))
 
     def __init__(self, recordings, Tl, window, device, ignore=(), sensor_hw=(240, 304), capacity_bytes=None, source_bytes=None, owned=None,
                  shard=None):
@@ -1012,8 +1251,14 @@ class Gen1WindowStore(Gen1Store):
         store._adopt(shard, ranks)
         return store
 
+    def _loaded(self):
+        self.capacity_bytes = self.used_bytes                           # every section was allocated at its size: there is no arena
+
     def trim(self):
-        """give back what the arena does not use: its bytes in use are reallocated at their size (``_Arena.trim``)"""
+        """give back what the arena does not use: its bytes in use are reallocated at their size (``_Arena.trim``); a store that
+        ``load_store`` made has nothing to give back"""
+        if getattr(self, '_arena', None) is None:
+            return self
         self.records, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
         return self
 
@@ -1052,6 +1297,12 @@ class Gen1PackedWindowStore(Gen1WindowStore):
     ``used_bytes``: the payload in use; ``nbytes()``: payload + table; ``narrow_blocks`` / ``wide_blocks``; ``kept_records`` and
     ``total_records`` count records as the parent does; ``unpacked(a, e)``: logical records [a, e) as 8-byte records; ``trim()`` gives the
     rest of the arena and of the table back.  A sensor that leaves fewer than 8 bits for the time raises ValueError."""
+    _snapshot_fields = dict(Gen1WindowStore._snapshot_fields, scalars=Gen1WindowStore._snapshot_fields['scalars'] + ('narrow_blocks', 'wide_blocks'),
+                            device=('table', 'payload', 'sample_ranges'))
+
+    def _loaded(self):
+        super()._loaded()
+        self.records, self._table, self._blocks = None, self.table, self.table.shape[0]
 
     def _open_arena(self, capacity_bytes):
         ops.records_widths(*self.sensor_hw)
@@ -1102,6 +1353,8 @@ class Gen1PackedWindowStore(Gen1WindowStore):
 
     def trim(self):
         """the parent's, for ``payload``; the table is reallocated at its used size with it"""
+        if getattr(self, '_arena', None) is None:
+            return self
         if self.capacity_bytes != self.used_bytes:
             self.table = self._table = self.table.clone()
         self.payload, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
@@ -1127,18 +1380,71 @@ def _data_dirs(exp, split):
     return dirs if root and all(os.path.isdir(d) for d in dirs) else None
 
 
-def _store_for(exp, attr, split, device, find, from_data, synthetic, more=()):
+def _store_for(exp, attr, split, device, find, from_data, synthetic, more=(), snapshot=None):
     """What the three ``*_store_for`` share: the stores kept on the experiment in the dict ``attr``, one per ``_store_key(exp, split)`` +
     ``more``; a store that is not there yet is built on ``device`` (None: ``_default_device()``) with the shard of the
-    experiment (``exp_store_shard``) -- ``from_data(found, device, shard)`` if ``find()`` finds the dataset, else ``synthetic(device, shard)``"""
+    experiment (``exp_store_shard``) -- ``from_data(found, device, shard)`` if ``find()`` finds the dataset, else ``synthetic(device, shard)``.
+    With ``exp.store_cache`` (a directory; None, the default: no cache) a store of a dataset that was found comes from its snapshot there
+    where that is current, and leaves one where it is not (``_store_from_cache``; ``snapshot(found, shard)`` -> (``train_input``, the store
+    class, the constructor arguments that shape the store, the directory the source paths are relative to, the source files)).  Synthetic
+    stores are never cached."""
     cache = exp.__dict__.setdefault(attr, {})
     shard = exp_store_shard(exp)
     key = _store_key(exp, split) + more
     if key not in cache:
         device = _default_device() if device is None else device
         found = find()
-        cache[key] = from_data(found, device, shard) if found else synthetic(device, shard)
+        if not found:
+            cache[key] = synthetic(device, shard)
+        elif snapshot is None or not getattr(exp, 'store_cache', None):
+            cache[key] = from_data(found, device, shard)
+        else:
+            cache[key] = _store_from_cache(str(exp.store_cache), split, device, shard, *snapshot(found, shard),
+                                           lambda: from_data(found, device, shard))
     return cache[key]
+
+
+def snapshot_key(cls, args, shard, root, files):
+    """What a snapshot of ``exp.store_cache`` is current by, computed without reading a source file: the format version, the store class,
+    the constructor arguments that shape the store, the shard, and (path relative to ``root``, size, ``mtime_ns``) of every source file;
+    in the form JSON gives it back (lists, no tuples), so that it compares equal to the ``key`` of a header"""
+    import json
+    import os
+    sources = []
+    for p in files:
+        st = os.stat(p)
+        sources.append([os.path.relpath(p, root), st.st_size, st.st_mtime_ns])
+    return json.loads(json.dumps(dict(format=SNAPSHOT_VERSION, cls=cls.__name__, args=args, shard=shard, sources=sources)))
+
+
+def snapshot_name(train_input, split, key, shard):
+    """``<train_input>_<split>_<first 16 hex digits of the sha256 of the key>[_r<rank>of<world>].eas``; the rank only for a sharded store"""
+    import hashlib
+    import json
+    digest = hashlib.sha256(json.dumps(key, sort_keys=True).encode('utf-8')).hexdigest()[:16]
+    return f'{train_input}_{split}_{digest}' + ('' if shard is None else f'_r{int(shard[0])}of{int(shard[1])}') + '.eas'
+
+
+def _store_from_cache(directory, split, device, shard, train_input, cls, args, root, files, build):
+    """The store from its snapshot in ``directory`` if a file of the key's name is there, its header carries the key and ``load_store``
+    accepts it; otherwise ``build()`` and, from the rank that writes, ``save`` under that name.  A ``SnapshotError`` is warned about once,
+    then the store is built and the file overwritten.  Every rank of a sharded world (``shard``) writes its own file; in replica mode only
+    rank 0 writes, and another rank that finds no file builds without waiting -- the process group may not exist yet, so no collective."""
+    import os
+    import warnings
+    key = snapshot_key(cls, args, shard, root, files)
+    path = os.path.join(directory, snapshot_name(train_input, split, key, shard))
+    if os.path.exists(path):
+        try:
+            if read_snapshot_header(path).get('key') == key:
+                return load_store(path, device, expect_shard=shard)
+        except SnapshotError as e:
+            warnings.warn(f'{e}; the store is built from the dataset and the snapshot written again')
+    store = build()
+    if shard is not None or rank_and_world()[0] == 0:
+        os.makedirs(directory, exist_ok=True)
+        store.save(path, key=key)
+    return store
 
 
 def gen1_store_for(exp, split='train', device=None):
@@ -1160,6 +1466,7 @@ def gen1_store_for(exp, split='train', device=None):
     cls = (Gen1PackedWindowStore if events == 'packed' else Gen1WindowStore) if kind == 'windows' else Gen1Store
     window = (exp.window * 1000, 0)
     made = (lambda store: store.trim()) if kind == 'windows' else (lambda store: store)
+    ignore = tuple(getattr(exp, 'store_ignore', ()))        # recordings left out (the reference's ``dirs_to_ignore``); none unless the experiment names some
 
     def synthetic(device, shard):
         n_files, n_labels, n_events = getattr(exp, 'store_recordings', (4, 16, 50_000))
@@ -1169,7 +1476,10 @@ def gen1_store_for(exp, split='train', device=None):
         return made(cls(recs, exp.Tl, window, device, sensor_hw=sensor, shard=shard))
     return _store_for(exp, '_dat_stores' if kind == 'all' else '_dat_packed_stores' if events == 'packed' else '_dat_window_stores',
                       split, device, lambda: _data_dirs(exp, split),
-                      lambda dirs, device, shard: made(cls.from_directories(dirs, exp.Tl, window, device, shard=shard)), synthetic)
+                      lambda dirs, device, shard: made(cls.from_directories(dirs, exp.Tl, window, device, ignore=ignore, shard=shard)), synthetic,
+                      snapshot=lambda dirs, shard: ('dat_store', cls, dict(Tl=int(exp.Tl), window=window, sensor_hw=(240, 304), ignore=sorted(ignore),
+                                                                           store_records=kind, store_events=events),
+                                                    str(exp.data_dir), cls._source_files(dirs, ignore, shard)))
 
 
 class _StoreDataset:
@@ -1425,6 +1735,7 @@ class Gen4Store(_Store):
     is not owned has ``held_first = -num_slice``, ``held_lo = 0``: every slice lies in front of its recording and is zero.  Without
     ``owned`` / ``shard`` the held tables are the group tables themselves.  ``owned_samples``, ``owns``, ``shard``, ``sample_rank``: see
     ``_Store``."""
+    _snapshot_fields = dict(scalars=('num_slice', 'sensor_hw', 'nbins', 'down_sample_factor'), lists=(), host=('held_offsets',), device=('sums',))
 
     def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, owned=None, shard=None):
         self.num_slice, self.sensor_hw, self.nbins = int(num_slice), (int(sensor_hw[0]), int(sensor_hw[1])), int(nbins)
@@ -1473,15 +1784,23 @@ class Gen4Store(_Store):
         self.group_file = group_file = np.asarray(group_file, dtype=np.int64)                # (host: the recording of every sample)
         self._set_owners(self.names, group_file, owned, ranks, shard)
         self.held_offsets = np.asarray(held_offsets, dtype=np.int64)
-        self.held_first, self.held_lo = self.group_first, self.group_lo
-        if self.sharded:
-            move = (self.held_offsets[:-1] - self.host['rep_offsets'][:-1])[group_file]
-            first = np.where(self._sample_owned, self.host['group_first'] + move, -self.num_slice)
-            lo = np.where(self._sample_owned, self.host['group_lo'] + move, 0)
-            self.held_first, self.held_lo = (torch.from_numpy(v.astype(np.int64)).to(self.device) for v in (first, lo))
+        self._set_held()
         self.sums = None
         if self.device.type != 'cpu':
             self._sum_recordings(reps, held_offsets, int(chunk))
+
+    def _set_held(self):
+        """``held_first`` / ``held_lo`` from the group tables, ``held_offsets``, ``group_file`` and the owners"""
+        self.held_first, self.held_lo = self.group_first, self.group_lo
+        if self.sharded:
+            move = (self.held_offsets[:-1] - self.host['rep_offsets'][:-1])[self.group_file]
+            first = np.where(self._sample_owned, self.host['group_first'] + move, -self.num_slice)
+            lo = np.where(self._sample_owned, self.host['group_lo'] + move, 0)
+            self.held_first, self.held_lo = (torch.from_numpy(v.astype(np.int64)).to(self.device) for v in (first, lo))
+
+    def _loaded(self):
+        self.group_file = self._owner_args[1]
+        self._set_held()
 
     def _sum_recordings(self, reps, held_offsets, chunk):
         """the device side of the build: ``sums`` at its final size, every recording uploaded ``chunk`` representations at a time and summed
@@ -1508,18 +1827,34 @@ class Gen4Store(_Store):
         import os
         read = read_representations if read_representations is not None else _h5_representations
         listed = []
-        for path in ([paths] if isinstance(paths, str) else paths):
-            for stream in sorted(os.listdir(path)):
-                label_dir = os.path.join(path, stream, 'labels_v2')
-                rep_dir = os.path.join(path, stream, 'event_representations_v2', rep_name)
-                labels = np.load(os.path.join(label_dir, 'labels.npz'))
-                listed.append((stream, rep_dir, np.load(os.path.join(rep_dir, 'objframe_idx_2_repr_idx.npy')), labels['labels'],
-                               labels['objframe_idx_2_label_idx'], np.load(os.path.join(label_dir, 'timestamps_us.npy'))))
+        for stream, label_dir, rep_dir in cls._listed(paths, rep_name):
+            labels = np.load(os.path.join(label_dir, 'labels.npz'))
+            listed.append((stream, rep_dir, np.load(os.path.join(rep_dir, 'objframe_idx_2_repr_idx.npy')), labels['labels'],
+                           labels['objframe_idx_2_label_idx'], np.load(os.path.join(label_dir, 'timestamps_us.npy'))))
         owned, ranks = _shard_plan([r[0] for r in listed], [int(r[2][-1]) + 1 if len(r[2]) else 0 for r in listed], shard, None)
         recs = [(r[0], read(r[1]) if owned is None or r[0] in owned else None) + r[2:] for r in listed]
         store = cls(recs, num_slice, device, down_sample_factor=down_sample_factor, sensor_hw=sensor_hw, nbins=nbins, chunk=chunk, owned=owned)
         store._adopt(shard, ranks)
         return store
+
+    @staticmethod
+    def _listed(paths, rep_name=GEN4_REP_NAME):
+        """[(stream, its label directory, its representation directory)] in the order of ``from_directories``; nothing is read"""
+        import os
+        return [(stream, os.path.join(path, stream, 'labels_v2'), os.path.join(path, stream, 'event_representations_v2', rep_name))
+                for path in ([paths] if isinstance(paths, str) else paths) for stream in sorted(os.listdir(path))]
+
+    @classmethod
+    def _source_files(cls, paths, rep_name=GEN4_REP_NAME):
+        """the files ``from_directories`` can open, from the listing alone: of every stream the two label files and every file of its
+        representation directory (the index and whatever ``read_representations`` reads) -- of every stream on every rank, since which
+        streams a shard owns is known only once their index files have been read"""
+        import os
+        out = []
+        for _, label_dir, rep_dir in cls._listed(paths, rep_name):
+            out += [os.path.join(label_dir, 'labels.npz'), os.path.join(label_dir, 'timestamps_us.npy')]
+            out += [os.path.join(rep_dir, fn) for fn in sorted(os.listdir(rep_dir)) if os.path.isfile(os.path.join(rep_dir, fn))]
+        return out
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, 1, num_slice, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): ``group_first`` and
@@ -1553,6 +1888,11 @@ class Gen4PackedStore(Gen4Store):
     exceeds -- and 0.8 of the free device memory); recordings that need more raise ValueError naming the bytes needed, after everything was
     measured.  ``used_bytes``: what the rows take; ``nbytes``: table + used payload; ``trim()`` gives the rest of the arena back.  A sensor
     wider than 1024 pixels raises ValueError (64 groups per row).  ``device='cpu'`` builds the tables and leaves ``rows`` / ``payload`` None."""
+    _snapshot_fields = dict(Gen4Store._snapshot_fields, scalars=Gen4Store._snapshot_fields['scalars'] + ('used_bytes',), device=('rows', 'payload'))
+
+    def _loaded(self):
+        super()._loaded()
+        self.sums, self.capacity_bytes = None, self.used_bytes
 
     def __init__(self, recordings, num_slice, device, down_sample_factor=2, sensor_hw=(360, 640), nbins=10, chunk=64, owned=None, shard=None,
                  capacity_bytes=None):
@@ -1595,7 +1935,10 @@ class Gen4PackedStore(Gen4Store):
         return self.rows.numel() * 8 + self.used_bytes
 
     def trim(self):
-        """give back what the arena does not use: ``payload`` is reallocated at its size (``_Arena.trim``)"""
+        """give back what the arena does not use: ``payload`` is reallocated at its size (``_Arena.trim``); a store that ``load_store``
+        made has nothing to give back"""
+        if getattr(self, '_arena', None) is None:
+            return self
         self.payload, self.capacity_bytes = self._arena.trim(), self._arena.used_bytes
         return self
 
@@ -1634,7 +1977,10 @@ def hist_store_for(exp, split='train', device=None):
         return cls(recs, exp.Tm, device, down_sample_factor=2, sensor_hw=sensor, nbins=nbins, shard=shard)
     return _store_for(exp, '_hist_stores', split, device, lambda: _data_dirs(exp, split),
                       lambda dirs, device, shard: cls.from_directories(dirs, exp.Tm, device, down_sample_factor=factor, nbins=nbins, shard=shard),
-                      synthetic, more=(kind,))
+                      synthetic, more=(kind,),
+                      snapshot=lambda dirs, shard: ('hist_store', cls, dict(num_slice=int(exp.Tm), nbins=nbins, down_sample_factor=factor,
+                                                                            sensor_hw=(360, 640), rep_name=GEN4_REP_NAME, store_sums=kind),
+                                                    str(exp.data_dir), cls._source_files(dirs)))
 
 
 class Gen4StoreDataset(_StoreDataset):
@@ -1726,6 +2072,7 @@ class NCaltechStore(_Store):
     never touched.  ``boxes``, ``group_start``, ``sample_names``, ``class_names``, ``raw_labels``, ``targets`` and the length are the same
     on every rank and the same as the unsharded store's; ``max_file_records`` is that of the owned recordings.  ``owned_samples``,
     ``owns``, ``shard``, ``sample_rank``: see ``_Store``."""
+    _snapshot_fields = dict(scalars=('Tl', 'window', 'sensor_hw', 'max_file_records'), lists=('class_names',), host=(), device=('records', 'index'))
 
     def __init__(self, recordings, Tl, window, device, class_names=None, sensor_hw=(180, 240), owned=None, shard=None):
         self.Tl, self.sensor_hw = int(Tl), (int(sensor_hw[0]), int(sensor_hw[1]))
@@ -1766,23 +2113,44 @@ class NCaltechStore(_Store):
         ``<root>/Caltech101`` without ``BACKGROUND_Google`` (ncaltech.py:129-134).  ``shard=(rank, world)``: every line is listed and every
         annotation read; a recording weighs the size of its ``.bin`` (``os.path.getsize``), and only the recordings ``shard_recordings``
         gives to ``rank`` are read.  ``read_bin(path)``: the reader of a recording (default ``numpy.fromfile(path, dtype=numpy.uint8)``)."""
-        import os
         read_bin = read_bin if read_bin is not None else (lambda p: np.fromfile(p, dtype=np.uint8))
-        with open(os.path.join(root, split + '.txt')) as f:
-            lines = [ln for ln in f.readlines() if NCALTECH_BACKGROUND not in ln]
         if class_names is None:
-            class_names = [n.strip() for n in sorted(os.listdir(os.path.join(root, 'Caltech101'))) if NCALTECH_BACKGROUND not in n]
-        listed = []
-        for ln in lines:
-            data_path, label_path = ln.strip().split(' ')
-            listed.append((label_path.split('/')[-2], data_path.split('/')[-1].split('.')[0], os.path.join(root, data_path),
-                           np.fromfile(os.path.join(root, label_path), dtype=np.uint8)))
-        names = [f'{c}-{stem}' for c, stem, _, _ in listed]
-        owned, ranks = _shard_plan(names, [os.path.getsize(r[2]) for r in listed] if shard is not None else (), shard, None)
+            class_names = cls._listed_classes(root)
+        listed, names, owned, ranks = cls._listed(root, split, shard)
+        listed = [(c, stem, path, np.fromfile(label, dtype=np.uint8)) for c, stem, path, label in listed]
         recs = [(c, stem, read_bin(path) if owned is None or n in owned else None, ann) for n, (c, stem, path, ann) in zip(names, listed)]
         store = cls(recs, Tl, window, device, class_names=class_names, sensor_hw=sensor_hw, owned=owned)
         store._adopt(shard, ranks)
         return store
+
+    @staticmethod
+    def _listed_classes(root):
+        import os
+        return [n.strip() for n in sorted(os.listdir(os.path.join(root, 'Caltech101'))) if NCALTECH_BACKGROUND not in n]
+
+    @staticmethod
+    def _listed(root, split, shard):
+        """([(class, stem, path of the recording, path of its annotation)] of ``<root>/<split>.txt`` in its order, their sample names, owned
+        names or None, {name: rank} or None): the split file is the listing; no recording and no annotation is read"""
+        import os
+        with open(os.path.join(root, split + '.txt')) as f:
+            lines = [ln for ln in f.readlines() if NCALTECH_BACKGROUND not in ln]
+        listed = []
+        for ln in lines:
+            data_path, label_path = ln.strip().split(' ')
+            listed.append((label_path.split('/')[-2], data_path.split('/')[-1].split('.')[0], os.path.join(root, data_path),
+                           os.path.join(root, label_path)))
+        names = [f'{c}-{stem}' for c, stem, _, _ in listed]
+        owned, ranks = _shard_plan(names, [os.path.getsize(r[2]) for r in listed] if shard is not None else (), shard, None)
+        return listed, names, owned, ranks
+
+    @classmethod
+    def _source_files(cls, root, split, shard):
+        """the files ``from_directory`` with these arguments would open: the split file, every annotation, the owned recordings"""
+        import os
+        listed, names, owned, _ = cls._listed(root, split, shard)
+        return ([os.path.join(root, split + '.txt')] + [label for _, _, _, label in listed]
+                + [path for n, (_, _, path, _) in zip(names, listed) if owned is None or n in owned])
 
     def frames(self, sample_idx, params, exp, canvas_hw=None):
         """model input [B, Tl, Tm, 2, Hc, Wc] fp32 of the samples ``sample_idx`` (int64 [B] on the device): the store operator that
@@ -1819,7 +2187,10 @@ def ncaltech_store_for(exp, split='train', device=None):
         recs = synth_ncaltech_recordings(n_files, n_events, sensor, n_classes=n_classes, seed=int(split != 'train'))
         return NCaltechStore(recs, exp.Tl, window, device, class_names=[f'class_{i:03d}' for i in range(n_classes)], sensor_hw=sensor, shard=shard)
     return _store_for(exp, '_atis_stores', split, device, lambda: root and os.path.isfile(os.path.join(root, split + '.txt')) and root,
-                      lambda root, device, shard: NCaltechStore.from_directory(root, split, exp.Tl, window, device, shard=shard), synthetic)
+                      lambda root, device, shard: NCaltechStore.from_directory(root, split, exp.Tl, window, device, shard=shard), synthetic,
+                      snapshot=lambda root, shard: ('atis_store', NCaltechStore, dict(Tl=int(exp.Tl), window=window, sensor_hw=(180, 240),
+                                                                                      class_names=NCaltechStore._listed_classes(root)),
+                                                    root, NCaltechStore._source_files(root, split, shard)))
 
 
 class NCaltechStoreDataset(_StoreDataset):

@@ -113,6 +113,55 @@ def records_gather(src, segments, seg_dst, dst, dst_offset=0):
     return last - first
 
 
+_DIGEST_GOLDEN, _DIGEST_M1, _DIGEST_M2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+_DIGEST_HOST_WORDS = 1 << 20         # words per step of the host evaluation (8 MiB of the buffer, a few arrays of that size beside it)
+
+
+def _bytes_digest_numpy(raw):
+    """(sum, xor) of ``eas_bytes_digest``'s definition (include/eas_hip.h) on the uint8 numpy array ``raw``, with numpy: what a store kept
+    on the host is digested by.  The same function as the kernel's, word for word; evaluated ``_DIGEST_HOST_WORDS`` words at a time."""
+    import numpy as np
+    raw = np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+    n = (raw.size + 7) // 8
+    s, x = np.uint64(0), np.uint64(0)
+    for a in range(0, n, _DIGEST_HOST_WORDS):
+        e = min(a + _DIGEST_HOST_WORDS, n)
+        part = raw[8 * a:8 * e]
+        if part.size != 8 * (e - a):                        # the last word: its missing bytes are zero
+            part = np.concatenate([part, np.zeros(8 * (e - a) - part.size, np.uint8)])
+        z = part.view('<u8').astype(np.uint64) + np.arange(a + 1, e + 1, dtype=np.uint64) * np.uint64(_DIGEST_GOLDEN)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(_DIGEST_M1)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(_DIGEST_M2)
+        z = z ^ (z >> np.uint64(31))
+        s, x = s + np.add.reduce(z, dtype=np.uint64), x ^ np.bitwise_xor.reduce(z)
+    return int(s), int(x)
+
+
+def bytes_digest(t):
+    """``torch.uint64`` [2] on ``t.device``: the 128-bit digest (sum, xor) of the bytes of the contiguous tensor ``t``
+    (``eas_bytes_digest``, include/eas_hip.h: a corruption check, not a cryptographic hash; the byte length is not part of it).  One reading
+    pass on the device, nothing read back (graph-capturable); a view that does not start on 16 bytes is cloned first.  A CPU tensor is
+    digested by the same definition with numpy -- the one operator that takes one: the stores that are built on the host need it."""
+    assert t.is_contiguous(), 'bytes_digest reads the bytes of a contiguous tensor'
+    flat = t.reshape(-1).view(torch.uint8)
+    if not t.is_cuda:
+        import numpy as np
+        with np.errstate(over='ignore'):
+            words = _bytes_digest_numpy(flat.numpy())
+        return torch.from_numpy(np.array(words, dtype=np.uint64).view(np.int64)).view(torch.uint64)
+    if flat.data_ptr() % 16:
+        flat = flat.clone()
+    out = torch.empty(2, dtype=torch.uint64, device=t.device)
+    _call('eas_bytes_digest', flat.numel(), _lib.lib().eas_bytes_digest, ptr(flat) if flat.numel() else None, flat.numel(), ptr(out), stream())
+    return out
+
+
+def bytes_digest_host(t):
+    """``bytes_digest(t)`` as two Python ints (sum, xor): the one place that reads the two words back"""
+    words = bytes_digest(t).view(torch.int64).cpu().numpy().view('<u8')
+    return int(words[0]), int(words[1])
+
+
 def _dat_ranges_frames(timer, entry, dtype, out_bytes, records, ranges, ns, H, W, tau, return_oob):
     """the two .dat-range wrappers: checks, allocations, the call (``tau``: a tuple, empty for the counts) and the return tuple"""
     _dev(records, ranges)

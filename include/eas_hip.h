@@ -277,6 +277,21 @@ int eas_records_pack(const void* records, int64_t n, int H, int W, const uint32_
                      eas_stream_t stream);
 int eas_records_unpack(const uint32_t* table, int64_t nb, const uint8_t* payload, int64_t units, int64_t a, int64_t e, int H, int W, void* out,
                        uint32_t* flags, eas_stream_t stream);
+/* A 128-bit digest of a device buffer in one reading pass (additive, ABI 9; what a store snapshot, data._Store.save / data.load_store, is
+ * checked by once its bytes are back in HBM).  A CORRUPTION CHECK, NOT A CRYPTOGRAPHIC HASH: truncation, bit flips and swapped words
+ * change it, an adversary can forge it.  Definition: the buffer is read as little-endian 64-bit words q_0 .. q_{n-1}, n = ceil(nbytes / 8),
+ * the missing bytes of the last word zero; for word i, all arithmetic mod 2^64,
+ *     z = q_i + (i + 1) * 0x9E3779B97F4A7C15
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31)
+ * out2[0] = the sum of all z, out2[1] = the XOR of all z (the empty buffer: 0, 0).  Both are order-independent: the words bit-identical
+ * from run to run whatever the grid.  The byte length is not part of the digest (a buffer and the same buffer with zero bytes behind it
+ * inside one word agree): whoever stores a digest stores the length beside it.  out2 (device, 8-byte aligned) is zeroed by the call on
+ * `stream`, then one 64-bit atomic add and one atomic xor per block; nothing is read back (graph-capturable).  buf 16-byte aligned (two
+ * words per load), nbytes <= 2^40; nbytes == 0: buf may be NULL, no kernel.  A NULL or misaligned pointer, nbytes < 0 or > 2^40:
+ * EAS_ERR_INVALID_ARG before any HIP call. */
+int eas_bytes_digest(const void* buf, long long nbytes, unsigned long long* out2, eas_stream_t stream);
 /* eas_event_histogram_dat_ranges / eas_event_latest_surface_dat_ranges on packed records: ``ranges`` holds LOGICAL record indices into a
  * store of nb blocks (table) and ``units`` payload units; out, oob_count, tau, the bound on B and every rule of the frames are those
  * entries' (the same kernels with another record source), so the frames are bit-identical to theirs on the records that were packed.
